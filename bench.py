@@ -22,6 +22,10 @@ IS the one-GPU rate of the same run), and the N = 1 point of the same workload i
 Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel against HBM with the ALGORITHMIC bytes (sizeof(T)·(nq + 3·nv)
 per evaluation + q̇, SURVEY.md §8 d); `alu` gives the binding roof (vector ALU).  The result of the timed launches is compared with
 the oracle over the WHOLE batch.  `cpu_baseline` times the oracle's restatement of the reference route on the host cores (N = 1 only).
+
+`--dump-outputs DIR` writes what the timed leg's last step computed (v̇ and q̇ for dynamics!, τ for inverse_dynamics!, x and the lower triangle of M for
+the solve; the final q, v of --op-sim; the by-products of --op-kin) as DIR/<name>.npy, state-major, at most 64 MB in all (beyond that a seeded sample of
+the states).  The inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
@@ -53,6 +57,7 @@ FP64_VECTOR_PEAK_TF = 78.6  # MI355X public spec (256 CU x 4 SIMD x 16 lanes x 2
 FP32_VECTOR_PEAK_TF = 157.3
 ABA_FLOPS_PER_EVAL = 27.0e3  # fused world-frame ABA, Atlas floating
 PMC_FILE = "r06_pmc_traffic.json"  # written by scripts/gpu_measure.sh
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all files together
 KERNELS = {"inverse_dynamics": "rnea_bank_kernel (<= one resident round of workgroups) / rnea_walk_kernel"}
 CONFIGS = {
     2: dict(model="atlas_floating", batch=4096, dtype="f64", op="dynamics", label="BASELINE configs[1]"),
@@ -70,6 +75,22 @@ def kernel_source_hash():
         if f.endswith((".hip", ".hpp")):
             h.update(open(os.path.join(d, f), "rb").read())
     return h.hexdigest()[:12]
+
+
+def dump_outputs(out_dir, arrays, B):
+    """--dump-outputs: every (B, ...) device tensor of `arrays` as out_dir/<name>.npy in its own dtype (fp32 / fp64).  Above DUMP_LIMIT_BYTES in all, the
+    same seeded sample of states (ascending) is taken from every array, so that two builds run with the same arguments write comparable files."""
+    import numpy as np
+    import torch
+    per_state = sum(t[0].numel() * t.element_size() for t in arrays.values())
+    n = min(B, DUMP_LIMIT_BYTES // per_state)
+    idx = None if n == B else torch.as_tensor(np.sort(np.random.default_rng(0).choice(B, n, replace=False)))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        if idx is not None:
+            t = t.index_select(0, idx.to(t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+    print(f"bench.py: wrote {', '.join(arrays)} ({n} of {B} states) to {out_dir}", file=sys.stderr)
 
 
 def free_port():
@@ -111,7 +132,11 @@ def parse_args():
     ap.add_argument("--op-sim", action="store_true", help="ONE leg: K RK4 steps of rbd_simulate at --batch / --dtype (what scripts/gpu_measure.sh profiles as sim64 / sim32)")
     ap.add_argument("--op-kin", action="store_true", help="ONE leg: the kinematics by-products at --batch / --dtype (gpu_measure.sh: kin)")
     ap.add_argument("--selftest-launch", action="store_true", help="only exercise the N-rank launcher (gloo on CPU): prints the world size the ranks saw")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed leg's last step computed as DIR/<name>.npy (rank 0's states, state-major)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
     world = max(args.gpus, int(os.environ.get("WORLD_SIZE", "1")))
     args.config_given = args.config is not None
     if args.config is None:
@@ -124,6 +149,8 @@ def parse_args():
     if args.no_extra_legs:
         args.no_pipelined = True
     args.solve_only_leg = not args.no_extra_legs
+    if args.op_sim or args.op_kin:  # one leg of its own for a profiler run: short unless asked otherwise
+        args.steps, args.warmup = args.steps or 60, 10 if args.warmup is None else args.warmup
     if args.steps is None:
         args.steps = 2000 if args.batch <= 8192 else 200
     if args.warmup is None:
@@ -323,6 +350,24 @@ def run(args, env):
     headline_fext = bool(args.wrenches)
     step = make_step(headline_fext, emit_M=not args.no_emit_M)
     wall, kernel_ms = timed(step, args.gather_every_step and world > 1)
+    if args.dump_outputs and rank == 0:  # now: the legs below write into the same buffers
+        sm = (lambda t: t) if args.layout == "aos" else (lambda t: t.t())  # state-major
+        if args.op == "mass_matrix_solve":
+            outs = {"x": sm(x_out)}
+            if packed_M:
+                outs["massmatrix_packed"] = sm(d_packed)
+            elif not args.no_emit_M:  # only the lower triangle is defined: LAPACK's packed 'L' order (column by column), as rbd_mass_matrix_solve_packed writes it
+                iu = torch.triu_indices(model.nv, model.nv, device=device)
+                outs["massmatrix_lower"] = sm(result.massmatrix).reshape(B, model.nv, model.nv)[:, iu[0], iu[1]]
+        elif args.op == "inverse_dynamics":
+            outs = {"tau": sm(x_out)}
+            if bodies:
+                outs.update(jointwrenches=sm(d_jw), accelerations=sm(d_acc))
+        else:
+            outs = {"vd": sm(result.vd), "qd": sm(result.qd)}
+            if model.nc > 0:
+                outs["lambda"] = sm(result.lambda_)
+        dump_outputs(args.dump_outputs, outs, B)
     per_rank = None
     if dist is not None:  # every rank's own rate over the same K steps (no data-path collective: this IS the one-GPU rate of this run)
         mine = torch.tensor([B * args.steps / (timed.own_ms * 1e-3)], dtype=torch.float64, device=device)
@@ -567,7 +612,7 @@ def run(args, env):
     return out
 
 
-def sim_leg(env, B, dtype, steps=12, warm=2, dt=1e-3):
+def sim_leg(env, B, dtype, steps=12, warm=2, dt=1e-3, dump=None):
     """One RK4 step of the batched `simulate` (src/simulate.jl:36-55, MuntheKaasIntegrator.step src/ode_integrators.jl:233-299; rbd_simulate, the stage folded
     into the dynamics kernel): K steps between HIP events on Atlas at B states, then — from the same initial state — two steps of EVERY state compared with the
     numpy restatement of the integrator (oracle/simulate_np.py, its batch-vectorised form).  One step = four dynamics! evaluations: `alu` prices 4 x 27 kflop,
@@ -609,6 +654,8 @@ def sim_leg(env, B, dtype, steps=12, warm=2, dt=1e-3):
     ev1.record(stream)
     torch.cuda.synchronize(device)
     wall = time.perf_counter() - t0
+    if dump:
+        dump_outputs(dump, {"q": state.q, "v": state.v}, B)
     kernel = (L.rbd_workspace_last_kernel(state.ws.handle) or b"").decode()
     # parity: two steps from the initial state, EVERY state against the integrator's numpy restatement (fp64)
     reset()
@@ -663,7 +710,7 @@ def sim_traffic(dtype, B):
     return pmc_traffic(f"atlas_floating_{dtype}_B{B}_simulate")[0]
 
 
-def kin_leg(env, B, dtype, steps=40, warm=8, model_name="atlas_floating"):
+def kin_leg(env, B, dtype, steps=40, warm=8, model_name="atlas_floating", dump=None):
     """The kinematics by-products the reference benchmarks beside the dynamics (perf/runbenchmarks.jl:69-110: momentum_matrix!, geometric_jacobian!, momentum,
     kinetic_energy, center_of_mass — SURVEY.md §8 f3): one step = rbd_kinematics (momentum matrix + centre of mass + both energies) + rbd_geometric_jacobian (world ->
     the last body: a hand) + rbd_momentum (momentum, momentum_rate_bias) over the batch, each also timed on its own by HIP events; parity of every output against
@@ -722,6 +769,8 @@ def kin_leg(env, B, dtype, steps=40, warm=8, model_name="atlas_floating"):
         return time.perf_counter() - t0, e0.elapsed_time(e1) / steps * 1e3
 
     wall, us = time_of(list(calls))
+    if dump:
+        dump_outputs(dump, {"momentum_matrix": A, "center_of_mass": com, "energies": en, "geometric_jacobian": J, "momentum": mom}, B)
     each, kernels = {}, []
     for n_ in calls:
         each[n_] = time_of([n_])[1]
@@ -769,6 +818,7 @@ def sub_args(args, config, **over):
     a.wrenches = a.graph = a.no_emit_M = a.bodies = a.packed_M = False
     a.solve_only_leg = True
     a.algorithm = "aba"
+    a.dump_outputs = None  # --dump-outputs is the headline's
     for k, v in over.items():
         setattr(a, k, v)
     return a
@@ -842,8 +892,8 @@ def main():
         return selftest_launch(args)
     env = setup(args)
     if args.op_sim or args.op_kin:  # one leg of its own for a profiler run
-        d = sim_leg(env, args.batch, args.dtype, steps=min(args.steps, 60), warm=min(args.warmup, 10)) if args.op_sim else \
-            kin_leg(env, args.batch, args.dtype, steps=min(args.steps, 60), warm=min(args.warmup, 10), model_name=args.model)
+        d = sim_leg(env, args.batch, args.dtype, steps=args.steps, warm=args.warmup, dump=args.dump_outputs) if args.op_sim else \
+            kin_leg(env, args.batch, args.dtype, steps=args.steps, warm=args.warmup, model_name=args.model, dump=args.dump_outputs)
         print(json.dumps(d))
         return
     out = run(args, env)

@@ -1,8 +1,8 @@
 """Generates tests/golden/models/*.json — flattened mechanisms (rbd_flat_model_t images) so that tests,
-smoke() and bench.py can run where /root/reference does not exist (the GPU box).
+smoke() and bench.py load a mechanism without parsing URDF.
 
-Run in the build container:  python tests/golden/make_models.py
-Sources: /root/reference/test/urdf/atlas.urdf (the vendored Atlas v5 fixture used instead of the
+Run:  python tests/golden/make_models.py
+Sources: tests/golden/urdf/ holds the reference's test/urdf fixtures: atlas.urdf (the vendored Atlas v5 fixture used instead of the
 benchmark's downloaded atlas_minimal_contact.urdf — SURVEY.md F7), Acrobot.urdf and valkyrie.urdf,
 parsed with rigidbodydynamics.jl_amd/urdf.py (parse_urdf semantics: src/urdf/parse.jl:162-221).
 tests/test_golden_vectors.py::test_model_fixtures_regenerate_from_the_reference_urdfs re-runs build_all() and compares every array
@@ -11,7 +11,7 @@ import os
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF = "/root/reference/test/urdf"
+REF = os.path.join(HERE, "urdf")
 OUT = os.path.join(HERE, "models")
 
 SPECS = {

@@ -2,8 +2,8 @@
 Featherstone implementation oracle/featherstone_np.py): the C oracle and the HIP path must both reproduce them.
 
   CPU: the C restatement of the reference (rbd_oracle) vs the vectors at 1e-11; the vectors regenerate from the generator script
-       (neither implementation can drift unnoticed); the model fixtures regenerate from the reference's URDF files when those are
-       present (this container; not on the GPU box).
+       (neither implementation can drift unnoticed); the model fixtures regenerate from the reference's URDF files
+       (stored under tests/golden/urdf/).
   GPU: every hot-path entry point through the C ABI vs the vectors at the reference's own atol 1e-10
        (test/test_mechanism_algorithms.jl:739)."""
 import importlib.util
@@ -68,7 +68,6 @@ def test_vectors_regenerate(rbd):
         sys.argv = argv
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/test/urdf"), reason="the reference checkout exists only in the build container")
 def test_model_fixtures_regenerate_from_the_reference_urdfs(rbd):
     """tests/golden/models/*.json are flattened images of the reference's own URDF fixtures: parse them again and compare every array."""
     spec = importlib.util.spec_from_file_location("make_models", os.path.join(ROOT, "tests", "golden", "make_models.py"))

@@ -1,13 +1,14 @@
 """write_urdf round trip — the reference's test/test_urdf.jl:105-168 ("URDF write / Basics"): every fixture URDF, floating or not, fixed
 joints removed before and/or after, is written, parsed back, and must give the same inverse dynamics (atol 1e-10) with the same joint
-layout.  Needs the reference's URDF fixtures, i.e. the build container."""
+layout.  The fixtures are the reference's test/urdf files, stored under tests/golden/urdf/."""
 import os
 
 import numpy as np
 import pytest
 
-URDF_DIR = "/root/reference/test/urdf"
-pytestmark = pytest.mark.skipif(not os.path.isdir(URDF_DIR), reason="the reference checkout exists only in the build container")
+from conftest import ROOT
+
+URDF_DIR = os.path.join(ROOT, "tests", "golden", "urdf")
 
 
 @pytest.mark.parametrize("basename", ["Acrobot.urdf", "Acrobot_with_limits.urdf", "planar_slider.urdf", "atlas.urdf", "valkyrie.urdf"])
