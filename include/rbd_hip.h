@@ -387,6 +387,37 @@ int rbd_gather(rbd_comm_t* comm, int32_t dtype, const void* shard, void* gathere
 int rbd_gatherv(rbd_comm_t* comm, int32_t dtype, const void* shard, void* gathered, const int64_t* counts, int32_t root /* < 0: every rank */, void* stream);
 const char* rbd_comm_last_error(void);
 
+/* ---- forward-mode derivatives of inverse_dynamics! and dynamics! (since 700) ---------------------------------------------------------------------------
+ * What ForwardDiff.jacobian / Dual numbers through the reference compute (its own test suite: test/test_mechanism_algorithms.jl:600-652), on tree
+ * mechanisms of any size, every tree joint type, fp32 and fp64, both layouts:
+ *  - the derivatives are those of the function the library evaluates, in the RAW coordinates q: a quaternion joint's transform is the unnormalised
+ *    rotation(jt, q, false) (src/joint_types/quaternion_floating.jl:81-83), so a direction dq need not be tangent to the unit sphere, and a SinCosRevolute's
+ *    (s, c) are two independent coordinates.  Lie-algebra (tangent-space) derivatives are not offered: compose with the q̇ = Q(q) v map
+ *    (velocity_to_configuration_derivative!) yourself;
+ *  - loop joints: RBD_ERR_HAS_LOOPS (as inverse_dynamics!, src/mechanism_algorithms.jl:549); contact points with an environment: RBD_ERR_UNSUPPORTED (as
+ *    rbd_dynamics); RBD_MEM_HOST: RBD_ERR_UNSUPPORTED (device pointers only);
+ *  - the value outputs equal rbd_inverse_dynamics / the CRBA + Cholesky route of rbd_dynamics (dynamics_solve! :764, :819) to rounding;
+ *  - allocation: the first derivative call of a workspace allocates its buffers (M, its factor, the tangent right-hand sides and scratch) for
+ *    max_batch states and nq + nv directions, a JVP call with more directions than any before allocates again; no other call allocates or synchronises;
+ *  - rbd_workspace_last_kernel names the tangent kernel afterwards.
+ * Tangents (JVPs): ntan directions per state (ntan <= 0: RBD_ERR_INVALID_ARGUMENT).  A tangent argument of n coordinates holds n·ntan values per state,
+ * direction d of state b at rows d·n … d·n+n−1 of that state's n·ntan (layout per opts, as every batch buffer).  Every tangent input is nullable
+ * (= zero direction); every value output is nullable.  dfext: 6·n_bodies per direction. */
+int rbd_inverse_dynamics_jvp(rbd_ws_t* ws, int32_t B, int32_t ntan, const void* q, const void* v, const void* vdot,
+                             const void* fext, const void* dq, const void* dv, const void* dvdot, const void* dfext,
+                             void* tau_out, void* dtau_out, const rbd_opts_t* opts);
+/* dv̇ by the implicit-function identity M(q) dv̇ = dτ − ∂ID(q, v, v̇)·(dq, dv, 0, dfext) at the v̇ of the same call: one Cholesky factor per state,
+ * ntan triangular solves against it. */
+int rbd_dynamics_jvp(rbd_ws_t* ws, int32_t B, int32_t ntan, const void* q, const void* v, const void* tau,
+                     const void* fext, const void* dq, const void* dv, const void* dtau, const void* dfext,
+                     void* vdot_out, void* dvdot_out, const rbd_opts_t* opts);
+/* Full Jacobians, column-major per state like rbd_geometric_jacobian: nv×nq (∂/∂q), nv×nv (∂/∂v, ∂/∂v̇, ∂/∂τ); fext held fixed.  Every output
+ * nullable; M_out = ∂τ/∂v̇ = M (the full square), dvdot_dtau = M⁻¹ (the full square).  Column j is the JVP along the j-th coordinate unit vector. */
+int rbd_inverse_dynamics_derivatives(rbd_ws_t* ws, int32_t B, const void* q, const void* v, const void* vdot, const void* fext,
+                                     void* tau_out, void* dtau_dq, void* dtau_dv, void* M_out, const rbd_opts_t* opts);
+int rbd_dynamics_derivatives(rbd_ws_t* ws, int32_t B, const void* q, const void* v, const void* tau, const void* fext,
+                             void* vdot_out, void* dvdot_dq, void* dvdot_dv, void* dvdot_dtau, const rbd_opts_t* opts);
+
 /* ---- diagnostics ------------------------------------------------------------ */
 const char* rbd_status_string(int status);
 const char* rbd_last_hip_error(void);   /* thread-local text of the last HIP failure     */
@@ -399,8 +430,9 @@ int rbd_workspace_last_kernel_ms(rbd_ws_t* ws, float* ms);
 const char* rbd_workspace_last_kernel(const rbd_ws_t* ws);
 /* 100·round + revision of this header.  rbd_flat_model_t grew its four contact fields at 200; a caller built against an older header must
  * not call a newer library (the Python and Julia loaders compare this with the value they were written for).  400: rbd_workspace_set_loop_gains.
- * 500: rbd_mass_matrix_solve_packed, rbd_gatherv.  600: rbd_jit_check_walk_object; no size limit left on any entry point; program family 11; family 1 in fp64. */
-#define RBD_HIP_H_VERSION 600
+ * 500: rbd_mass_matrix_solve_packed, rbd_gatherv.  600: rbd_jit_check_walk_object; no size limit left on any entry point; program family 11; family 1 in fp64.
+ * 700: forward-mode derivatives — rbd_inverse_dynamics_jvp, rbd_dynamics_jvp, rbd_inverse_dynamics_derivatives, rbd_dynamics_derivatives. */
+#define RBD_HIP_H_VERSION 700
 int rbd_version(void);
 /* Run-time specialisation.  The one-lane-per-state kernels (mass_matrix! and mass_matrix! + Cholesky at large batches) exist in a second form
  * that is compiled for the mechanism at hand with hiprtc the first time a workspace needs it (the walk of the tree, joint types, offsets and

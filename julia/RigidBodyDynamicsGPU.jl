@@ -28,7 +28,8 @@ import RigidBodyDynamics: dynamics!, inverse_dynamics!, mass_matrix!, dynamics_b
     kinetic_energy, gravitational_potential_energy, momentum, momentum_rate_bias, simulate
 using LinearAlgebra
 
-export BatchedMechanismState, BatchedDynamicsResult, DeviceMatrix, RbdComm, gather!, gatherv!, mass_matrix_solve_packed!, synchronize, librbd_hip, TorqueTable, PDControl
+export BatchedMechanismState, BatchedDynamicsResult, DeviceMatrix, RbdComm, gather!, gatherv!, mass_matrix_solve_packed!, synchronize, librbd_hip, TorqueTable, PDControl,
+    inverse_dynamics_jvp!, dynamics_jvp!, inverse_dynamics_derivatives!, dynamics_derivatives!
 
 const librbd_hip = Ref("librbd_hip.so")   # set to <repo>/rigidbodydynamics.jl_amd/csrc/librbd_hip.so
 const libhip = Ref("libamdhip64.so")
@@ -141,7 +142,7 @@ mutable struct FlatModelHandle
 end
 
 const WAIT_HOOK = Ref(false)
-const HEADER_VERSION = 600    # RBD_HIP_H_VERSION of the include/rbd_hip.h these structs mirror (rbd_flat_model_t grew its contact fields at 200; 400: rbd_workspace_set_loop_gains; 500: rbd_mass_matrix_solve_packed, rbd_gatherv; 600: rbd_jit_check_walk_object)
+const HEADER_VERSION = 700    # RBD_HIP_H_VERSION of the include/rbd_hip.h these structs mirror (rbd_flat_model_t grew its contact fields at 200; 400: rbd_workspace_set_loop_gains; 500: rbd_mass_matrix_solve_packed, rbd_gatherv; 600: rbd_jit_check_walk_object; 700: the derivative entry points)
 
 function FlatModelHandle(mechanism::Mechanism)
     ccall((:rbd_version, librbd_hip[]), Cint, ()) == HEADER_VERSION ||
@@ -417,6 +418,78 @@ function mass_matrix!(M::Buffer{T}, state::BatchedMechanismState{T}) where {T}
     M
 end
 mass_matrix!(result::BatchedDynamicsResult, state::BatchedMechanismState) = mass_matrix!(result.massmatrix, state)
+
+# ---- forward-mode derivatives (header 700): what `ForwardDiff.jacobian` / `Dual` numbers through the reference give (test/test_mechanism_algorithms.jl:600-652),
+# in the raw coordinates q.  Tangent buffers are (n·ntan) × B (direction d of a state at rows d·n+1 … d·n+n); Jacobians (nv·ncols) × B, column-major per
+# state (`reshape(J[:, b], nv, :)`); every tangent input and every output may be `nothing`.
+
+"""`inverse_dynamics_jvp!(dτ, state, v̇, ntan; dq, dv, dv̇, externalwrenches, dexternalwrenches, torquesout)` — `inverse_dynamics!` pushed forward along
+`ntan` directions per state (`rbd_inverse_dynamics_jvp`)."""
+function inverse_dynamics_jvp!(dτ, state::BatchedMechanismState{T}, v̇::Buffer{T}, ntan::Integer; dq = nothing, dv = nothing, dv̇ = nothing,
+        externalwrenches = nothing, dexternalwrenches = nothing, torquesout = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, B = state.model.nq, state.model.nv, batchsize(state)
+    ntan > 0 || throw(ArgumentError("ntan must be positive"))
+    for (x, n) in ((dτ, nv), (dq, nq), (dv, nv), (dv̇, nv))
+        x === nothing || size(x) == (n * ntan, B) || throw(DimensionMismatch("tangent buffer has wrong size"))
+    end
+    check(ccall((:rbd_inverse_dynamics_jvp, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, ntan, state.q, state.v, v̇, nullable(densewrenches(state, externalwrenches)), nullable(dq), nullable(dv), nullable(dv̇),
+        nullable(dexternalwrenches), nullable(torquesout), nullable(dτ), opts(state)), "rbd_inverse_dynamics_jvp")
+    finish(state)
+    dτ
+end
+
+"""`dynamics_jvp!(dv̇, state, ntan; torques, dq, dv, dτ, externalwrenches, dexternalwrenches, v̇out)` — `dynamics!` pushed forward along `ntan` directions
+per state: M dv̇ = dτ − ∂ID·(dq, dv, 0, dfext) at the v̇ of the same call (`rbd_dynamics_jvp`)."""
+function dynamics_jvp!(dv̇, state::BatchedMechanismState{T}, ntan::Integer; torques = nothing, dq = nothing, dv = nothing, dτ = nothing,
+        externalwrenches = nothing, dexternalwrenches = nothing, v̇out = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, B = state.model.nq, state.model.nv, batchsize(state)
+    ntan > 0 || throw(ArgumentError("ntan must be positive"))
+    for (x, n) in ((dv̇, nv), (dq, nq), (dv, nv), (dτ, nv))
+        x === nothing || size(x) == (n * ntan, B) || throw(DimensionMismatch("tangent buffer has wrong size"))
+    end
+    check(ccall((:rbd_dynamics_jvp, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, ntan, state.q, state.v, nullable(torques), nullable(densewrenches(state, externalwrenches)), nullable(dq), nullable(dv), nullable(dτ),
+        nullable(dexternalwrenches), nullable(v̇out), nullable(dv̇), opts(state)), "rbd_dynamics_jvp")
+    finish(state)
+    dv̇
+end
+
+"""`inverse_dynamics_derivatives!(∂τ∂q, ∂τ∂v, M, state, v̇; externalwrenches, torquesout)` — the Jacobians of `inverse_dynamics!` (fext fixed): (nv·nq) × B,
+(nv·nv) × B, and M = ∂τ/∂v̇ as the full square (`rbd_inverse_dynamics_derivatives`)."""
+function inverse_dynamics_derivatives!(dτdq, dτdv, M, state::BatchedMechanismState{T}, v̇::Buffer{T}; externalwrenches = nothing, torquesout = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, B = state.model.nq, state.model.nv, batchsize(state)
+    for (x, n) in ((dτdq, nv * nq), (dτdv, nv * nv), (M, nv * nv))
+        x === nothing || size(x) == (n, B) || throw(DimensionMismatch("Jacobian buffer has wrong size"))
+    end
+    check(ccall((:rbd_inverse_dynamics_derivatives, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, state.q, state.v, v̇, nullable(densewrenches(state, externalwrenches)), nullable(torquesout), nullable(dτdq), nullable(dτdv), nullable(M),
+        opts(state)), "rbd_inverse_dynamics_derivatives")
+    finish(state)
+    dτdq, dτdv, M
+end
+
+"""`dynamics_derivatives!(∂v̇∂q, ∂v̇∂v, ∂v̇∂τ, state; torques, externalwrenches, v̇out)` — the Jacobians of `dynamics!` (fext fixed); ∂v̇/∂τ = M⁻¹
+(`rbd_dynamics_derivatives`)."""
+function dynamics_derivatives!(dv̇dq, dv̇dv, dv̇dτ, state::BatchedMechanismState{T}; torques = nothing, externalwrenches = nothing, v̇out = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, B = state.model.nq, state.model.nv, batchsize(state)
+    for (x, n) in ((dv̇dq, nv * nq), (dv̇dv, nv * nv), (dv̇dτ, nv * nv))
+        x === nothing || size(x) == (n, B) || throw(DimensionMismatch("Jacobian buffer has wrong size"))
+    end
+    check(ccall((:rbd_dynamics_derivatives, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, state.q, state.v, nullable(torques), nullable(densewrenches(state, externalwrenches)), nullable(v̇out), nullable(dv̇dq), nullable(dv̇dv),
+        nullable(dv̇dτ), opts(state)), "rbd_dynamics_derivatives")
+    finish(state)
+    dv̇dq, dv̇dv, dv̇dτ
+end
 
 """`mass_matrix_solve_packed!(x, Mpacked, state, rhs)` — `mass_matrix!` + the potrf!/potrs! of `dynamics_solve!` (:764, :819) with M as LAPACK's packed lower
 triangle: `Mpacked` is nv(nv+1)/2 × B, element (i, j), i ≥ j (0-based), of a state at i + j(2nv − j − 1)/2 — what `Symmetric(M, :L)` defines, half the bytes of

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RBD_LIB") or os.path.join(_HERE, "csrc", "librbd_hip.so")  # RBD_LIB: A/B kernel variants (experiments only)
 
 RBD_OK = 0
-HEADER_VERSION = 600  # RBD_HIP_H_VERSION of the include/rbd_hip.h this binding was written against
+HEADER_VERSION = 700  # RBD_HIP_H_VERSION of the include/rbd_hip.h this binding was written against
 F64, F32 = 0, 1
 LAYOUT_SOA, LAYOUT_AOS = 0, 1
 MEM_DEVICE, MEM_HOST = 0, 1
@@ -24,6 +24,7 @@ SYMBOLS = (
     "rbd_workspace_enable_timing", "rbd_workspace_last_kernel_ms", "rbd_version", "rbd_simulate", "rbd_mk_stage", "rbd_cholesky_solve", "rbd_kinematics", "rbd_model_chain_plan", "rbd_workspace_last_kernel", "rbd_geometric_jacobian", "rbd_momentum", "rbd_model_bank_plan", "rbd_model_track_plan", "rbd_inverse_dynamics_bodies", "rbd_dynamics_bias_bodies",
     "rbd_model_reroot_plan", "rbd_model_contact_dims", "rbd_contact_dynamics", "rbd_dynamics_contact", "rbd_simulate_contact",
     "rbd_workspace_bind_result", "rbd_workspace_set_loop_gains", "rbd_jit_precompile", "rbd_jit_source", "rbd_jit_status", "rbd_jit_wait_idle", "rbd_simulate_controlled", "rbd_comm_unique_id", "rbd_comm_create", "rbd_comm_destroy", "rbd_comm_info", "rbd_gather", "rbd_gatherv", "rbd_mass_matrix_solve_packed", "rbd_comm_last_error", "rbd_jit_check_walk_object",
+    "rbd_inverse_dynamics_jvp", "rbd_dynamics_jvp", "rbd_inverse_dynamics_derivatives", "rbd_dynamics_derivatives",
 )
 
 
@@ -80,6 +81,10 @@ def lib():
         L.rbd_mass_matrix_solve_packed.argtypes = [vp, i32, vp, vp, vp, vp, ctypes.POINTER(Opts)]
         L.rbd_dynamics_result.argtypes = [vp, i32, vp, vp, vp, vp, ctypes.POINTER(Opts)]
         L.rbd_cholesky_solve.argtypes = [vp, i32, vp, vp, vp, vp, ctypes.POINTER(Opts)]
+        L.rbd_inverse_dynamics_jvp.argtypes = [vp, i32, i32] + [vp] * 10 + [ctypes.POINTER(Opts)]
+        L.rbd_dynamics_jvp.argtypes = [vp, i32, i32] + [vp] * 10 + [ctypes.POINTER(Opts)]
+        L.rbd_inverse_dynamics_derivatives.argtypes = [vp, i32] + [vp] * 8 + [ctypes.POINTER(Opts)]
+        L.rbd_dynamics_derivatives.argtypes = [vp, i32] + [vp] * 8 + [ctypes.POINTER(Opts)]
         L.rbd_model_chain_plan.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), i32]
         L.rbd_model_track_plan.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(ctypes.c_double), i32]
         L.rbd_comm_unique_id.argtypes = [vp]

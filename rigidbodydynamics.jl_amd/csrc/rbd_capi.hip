@@ -23,6 +23,7 @@
 #include "rbd_state_plan.hpp"
 #include "rbd_jit.hpp"
 #include "rbd_mk_fuse.hpp"
+#include "rbd_tangent.hpp"
 enum { BANK_LDS_PAIRS_HOST = 30 };  // = BANK_LDS_PAIRS of rbd_bank.hpp (16 parked + 14 exchange pairs per lane; checked in rbd_bank_kernels.hip)
 
 using namespace rbd;
@@ -166,6 +167,12 @@ struct rbd_ws {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool ev_pending = false;
   const char* last_kernel = "";  // dominant kernel of the last rbd_dynamics / rbd_simulate / rbd_mass_matrix_solve call
+  // the derivative entry points (rbd_tangent_kernels.hip): the tree in the reference's order for every mechanism (BigModel tables), the tangent scratch
+  // (tan_threads (state, chunk) threads per launch) and the dynamics! buffers — M, its factor, c, v̇, tangent right-hand sides for tan_ntan directions,
+  // and for more than 64 coordinates the solve's own vectors — allocated by the first derivative call and when ntan grows
+  bool tan_ready = false; BigModel tan{}; void* d_tan_tbl = nullptr; void* d_tan_rb = nullptr; void* d_tan_scratch = nullptr; size_t d_tan_scratch_bytes = 0; long tan_threads = 0; int tan_ntan = 0;
+  void* d_tan_M = nullptr; void* d_tan_L = nullptr; void* d_tan_c = nullptr; void* d_tan_vd = nullptr; void* d_tan_rhs = nullptr; void* d_tan_x = nullptr;
+  size_t d_tan_M_bytes = 0, d_tan_L_bytes = 0, d_tan_c_bytes = 0, d_tan_vd_bytes = 0, d_tan_rhs_bytes = 0, d_tan_x_bytes = 0;
 };
 
 // RBD_TUNE="key=value,key=value,...": the developer knobs of the tests and sweep scripts in ONE environment variable (batch thresholds between the lane
@@ -1082,7 +1089,8 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
 int rbd_workspace_destroy(rbd_ws_t* w) {
   if (!w) return RBD_OK;
   (void)hipSetDevice(w->device);
-  void* ptrs[] = {w->d_big_L, w->d_big_tbl, w->d_big_rb, w->d_big_scratch, w->d_fused_i, w->d_tauwork, w->d_rr_chain_i, w->d_rr_chain_r, w->d_rrtrack_ri, w->d_rrtrack_rr, w->d_rrwalk_wk, w->d_cp_body, w->d_cp_r, w->d_hs_r, w->d_tw, w->d_cw, w->d_s0, w->d_sacc, w->d_sdot, w->d_rows, w->d_walk_wk, w->d_state_ops, w->d_state_cols, w->d_state_sr, w->d_Msoa, w->d_track_ri, w->d_track_rr, w->d_bank_ib[0], w->d_bank_ib[1], w->d_bank_rb[0], w->d_bank_rb[1], w->d_ib, w->d_rb, w->d_nslots, w->d_dof_body, w->d_anc, w->d_row_mask, w->d_M, w->d_c, w->d_K, w->d_k, (void*)w->d_notpd, w->d_body, w->d_scratch, w->d_loop_i, w->d_loop_r, w->d_loop_path, w->d_jt_ref, w->d_voff_ref, w->d_axis_ref, w->d_axis2_ref};
+  void* ptrs[] = {w->d_big_L, w->d_big_tbl, w->d_big_rb, w->d_big_scratch, w->d_fused_i, w->d_tauwork, w->d_rr_chain_i, w->d_rr_chain_r, w->d_rrtrack_ri, w->d_rrtrack_rr, w->d_rrwalk_wk, w->d_cp_body, w->d_cp_r, w->d_hs_r, w->d_tw, w->d_cw, w->d_s0, w->d_sacc, w->d_sdot, w->d_rows, w->d_walk_wk, w->d_state_ops, w->d_state_cols, w->d_state_sr, w->d_Msoa, w->d_track_ri, w->d_track_rr, w->d_bank_ib[0], w->d_bank_ib[1], w->d_bank_rb[0], w->d_bank_rb[1], w->d_ib, w->d_rb, w->d_nslots, w->d_dof_body, w->d_anc, w->d_row_mask, w->d_M, w->d_c, w->d_K, w->d_k, (void*)w->d_notpd, w->d_body, w->d_scratch, w->d_loop_i, w->d_loop_r, w->d_loop_path, w->d_jt_ref, w->d_voff_ref, w->d_axis_ref, w->d_axis2_ref,
+                  w->d_tan_tbl, w->d_tan_rb, w->d_tan_scratch, w->d_tan_M, w->d_tan_L, w->d_tan_c, w->d_tan_vd, w->d_tan_rhs, w->d_tan_x};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (void* p : w->stage) if (p) (void)hipFree(p);
   {
@@ -2751,6 +2759,259 @@ int rbd_momentum(rbd_ws_t* w, int32_t B, const void* q, const void* v, void* out
   }
   if (o.memory == RBD_MEM_HOST) return stage_out_copy(w, out12, dout, es * 12 * B);
   return RBD_OK;
+}
+
+}  // extern "C"
+
+// ---- forward-mode derivatives of inverse_dynamics! and dynamics! (header 700; kernels: rbd_tangent_kernels.hip) --------------------------------------------
+namespace rbd {
+size_t tangent_scratch_elems_per_thread(const BigModel& M, int es);
+int tangent_chunk(int es);
+template <typename T> hipError_t launch_tangent_rnea(const BigModel& M, const TanArgs<T>& A, void* scratch, long max_threads, hipStream_t s);
+template <typename T>
+hipError_t launch_tangent_solve(int nv, long B, int c0, int ncol, const void* L, Layout Ll, const void* rhs, int identity, const ColOut<T>& out, void* xmem, hipStream_t s);
+template <typename T> hipError_t launch_symmetrize(int nv, long B, void* M, Layout Lm, hipStream_t s);
+}  // namespace rbd
+
+namespace {
+enum : long { TAN_SCRATCH_CAP = 1L << 30 };  // bytes of tangent scratch at most: larger calls run in slabs of (state, chunk) threads
+
+// the first derivative call of a workspace (and one with more directions than before) allocates; every later call only launches
+int tan_ensure(rbd_ws* w, int ntan) {
+  const rbd_model* m = w->model;
+  const size_t es = esize(w);
+  const long B = w->max_batch;
+  int st;
+  if (!w->tan_ready) {
+    if (m->big) {
+      w->tan = w->big;
+      if ((st = big_scratch(w, w->max_batch))) return st;
+    } else {  // the slot-ordered tables back in the reference's order (parents first: rbd_model_create checks it)
+      const int nb = m->nb;
+      std::vector<int32_t> tbl(4 * (size_t)nb);
+      std::vector<double> rb((size_t)nb * RB_STRIDE);
+      for (int i = 0; i < nb; ++i) {
+        const int s = m->slot_of[i];
+        const int32_t* ib = &m->ib[(size_t)s * IB_STRIDE];
+        tbl[4 * i] = ib[IB_PARENT] < 0 ? -1 : m->order[ib[IB_PARENT]];
+        tbl[4 * i + 1] = ib[IB_JTYPE]; tbl[4 * i + 2] = ib[IB_QOFF]; tbl[4 * i + 3] = ib[IB_VOFF];
+        memcpy(&rb[(size_t)i * RB_STRIDE], &m->rb[(size_t)s * RB_STRIDE], sizeof(double) * RB_STRIDE);
+      }
+      if (w->dtype == RBD_F64) st = upload(&w->d_tan_rb, rb.data(), rb.size() * sizeof(double));
+      else { std::vector<float> f(rb.begin(), rb.end()); st = upload(&w->d_tan_rb, f.data(), f.size() * sizeof(float)); }
+      if (st) return st;
+      w->tan.nb = nb; w->tan.nq = m->nq; w->tan.nv = m->nv; w->tan.rb = w->d_tan_rb;
+      memcpy(w->tan.gravity, m->gravity, sizeof w->tan.gravity);
+      if ((st = upload(&w->d_tan_tbl, tbl.data(), tbl.size() * sizeof(int32_t)))) return st;
+      w->tan.tbl = (const int32_t*)w->d_tan_tbl;
+    }
+    const size_t nv = (size_t)m->nv;
+    if ((st = ensure(&w->d_tan_M, &w->d_tan_M_bytes, es * nv * nv * B)) || (st = ensure(&w->d_tan_L, &w->d_tan_L_bytes, es * nv * nv * B)) ||
+        (st = ensure(&w->d_tan_c, &w->d_tan_c_bytes, es * nv * B)) || (st = ensure(&w->d_tan_vd, &w->d_tan_vd_bytes, es * nv * B)))
+      return st;
+    w->tan_ready = true;
+  }
+  ntan = std::max(ntan, m->nq + m->nv);  // (the Jacobians' directions: a JVP call after a derivatives call allocates nothing)
+  if (ntan > w->tan_ntan) {
+    const int N = tangent_chunk((int)es);
+    const size_t per = std::max<size_t>(1, tangent_scratch_elems_per_thread(w->tan, (int)es) * es);
+    const long want = B * ((ntan + N - 1) / N);
+    const long cap = std::max<long>(64, (long)(TAN_SCRATCH_CAP / per) / 64 * 64);
+    const long threads = std::min(want, cap);
+    if ((st = ensure(&w->d_tan_scratch, &w->d_tan_scratch_bytes, per * threads))) return st;
+    w->tan_threads = threads;
+    if ((st = ensure(&w->d_tan_rhs, &w->d_tan_rhs_bytes, es * std::max<size_t>(1, (size_t)m->nv * ntan * B)))) return st;
+    if (m->nv > 64 && (st = ensure(&w->d_tan_x, &w->d_tan_x_bytes, es * (size_t)m->nv * ntan * B))) return st;
+    w->tan_ntan = ntan;
+  }
+  return RBD_OK;
+}
+
+// the checks every derivative call shares
+int tan_check(rbd_ws* w, int32_t B, const Opts& o) {
+  int st = check_common(w, B, o);
+  if (st != RBD_OK) return st;
+  if (w->model->nloops > 0) return RBD_ERR_HAS_LOOPS;  // (inverse_dynamics!: src/mechanism_algorithms.jl:549)
+  if (w->model->ncp > 0 && w->model->nhs > 0) return RBD_ERR_UNSUPPORTED;  // (as rbd_dynamics: the contact wrenches need the additional state)
+  if (o.memory != RBD_MEM_DEVICE) return RBD_ERR_UNSUPPORTED;
+  return RBD_OK;
+}
+
+template <typename T> TanArgs<T> tan_args(rbd_ws* w, int32_t B, int layout, int ntan, const void* q, const void* v, const void* vdot, const void* fext) {
+  const rbd_model* m = w->model;
+  TanArgs<T> A{};
+  A.B = B; A.ntan = ntan; A.unit = 0; A.g0 = 0;
+  A.q = (const T*)q; A.v = (const T*)v; A.vdot = (const T*)vdot; A.fext = (const T*)fext;
+  A.Lq = layout_of(layout, m->nq, B); A.Lv = layout_of(layout, m->nv, B); A.Lf = layout_of(layout, 6L * m->nb, B);
+  A.Ldq = layout_of(layout, (long)m->nq * ntan, B); A.Ldv = layout_of(layout, (long)m->nv * ntan, B); A.Ldf = layout_of(layout, 6L * m->nb * ntan, B);
+  A.sign = T(1);
+  A.out = ColOut<T>{nullptr, Layout{0, 0}, nullptr, Layout{0, 0}, INT32_MAX, m->nv};
+  return A;
+}
+
+// dynamics!'s value the reference's way (dynamics_solve! :764, :819): c = dynamics_bias!, M = mass_matrix!, L = chol(M) into the workspace, v̇ = L⁻ᵀ L⁻¹ (τ − c)
+template <typename T> int tan_dynamics_value(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, const void* tau, const void* fext, void* vd) {
+  const rbd_model* m = w->model;
+  const Layout Lq = layout_of(layout, m->nq, B), Lv = layout_of(layout, m->nv, B), Lf = layout_of(layout, 6L * m->nb, B), Lm{B, 1};
+  if (m->big) {
+    HIP_TRY(launch_big_rnea<T>(w->big, B, q, v, nullptr, fext, w->d_tan_c, nullptr, w->d_big_scratch, nullptr, nullptr, Lq, Lv, Lf, w->stream));
+    HIP_TRY(launch_big_crba<T>(w->big, B, q, w->d_tan_M, w->d_big_scratch, Lq, Lm, w->stream));
+  } else {
+    HIP_TRY(launch_rnea<T>(w->dm, B, q, v, nullptr, fext, w->d_tan_c, nullptr, nullptr, Lq, Lv, Lf, w->stream));
+    HIP_TRY(launch_crba<T>(w->dm, B, q, w->d_tan_M, Lq, Lm, 1, w->stream));
+  }
+  // (the wavefront Cholesky kernels hold one row per lane: beyond 64 coordinates the one-thread-per-state factorisation of the any-size route)
+  if (m->nv > 64) HIP_TRY(launch_big_chol_solve<T>(m->nv, B, w->d_tan_M, w->d_tan_L, tau, w->d_tan_c, vd, Lm, Lv, w->d_notpd, w->stream));
+  else HIP_TRY(launch_chol_solve<T>(m->nv, B, w->d_tan_M, tau, w->d_tan_c, vd, w->d_tan_L, Lm, Lv, w->d_notpd, w->stream));
+  return RBD_OK;
+}
+
+template <typename T>
+int tan_id_jvp(rbd_ws* w, int32_t B, int32_t ntan, int layout, const void* q, const void* v, const void* vdot, const void* fext, const void* dq, const void* dv,
+               const void* dvdot, const void* dfext, void* tau_out, void* dtau_out) {
+  TanArgs<T> A = tan_args<T>(w, B, layout, ntan, q, v, vdot, fext);
+  A.dq = (const T*)dq; A.dv = (const T*)dv; A.dvdot = (const T*)dvdot; A.dfext = (const T*)dfext;
+  A.tau = (T*)tau_out;
+  A.out.a = (T*)dtau_out; A.out.La = A.Ldv;
+  HIP_TRY(launch_tangent_rnea<T>(w->tan, A, w->d_tan_scratch, w->tan_threads, w->stream));
+  return RBD_OK;
+}
+
+template <typename T>
+int tan_dyn_jvp(rbd_ws* w, int32_t B, int32_t ntan, int layout, const void* q, const void* v, const void* tau, const void* fext, const void* dq, const void* dv,
+                const void* dtau, const void* dfext, void* vdot_out, void* dvdot_out) {
+  const rbd_model* m = w->model;
+  void* vd = vdot_out ? vdot_out : w->d_tan_vd;
+  int st;
+  if ((st = tan_dynamics_value<T>(w, B, layout, q, v, tau, fext, vd))) return st;
+  if (!dvdot_out) return RBD_OK;
+  // M dv̇ = dτ − ∂ID(q, v, v̇)·(dq, dv, 0, dfext): the right-hand sides (batch-innermost) in one tangent pass, then ntan solves against the one factor
+  TanArgs<T> A = tan_args<T>(w, B, layout, ntan, q, v, vd, fext);
+  A.dq = (const T*)dq; A.dv = (const T*)dv; A.dfext = (const T*)dfext;
+  A.out.a = (T*)w->d_tan_rhs; A.out.La = Layout{B, 1};
+  A.sign = T(-1); A.dadd = (const T*)dtau;
+  HIP_TRY(launch_tangent_rnea<T>(w->tan, A, w->d_tan_scratch, w->tan_threads, w->stream));
+  const ColOut<T> out{(T*)dvdot_out, A.Ldv, nullptr, Layout{0, 0}, INT32_MAX, m->nv};
+  HIP_TRY(launch_tangent_solve<T>(m->nv, B, 0, ntan, w->d_tan_L, Layout{B, 1}, w->d_tan_rhs, 0, out, w->d_tan_x, w->stream));
+  return RBD_OK;
+}
+
+template <typename T>
+int tan_id_derivs(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, const void* vdot, const void* fext, void* tau_out, void* dtau_dq, void* dtau_dv,
+                  void* M_out) {
+  const rbd_model* m = w->model;
+  // the directions asked for: the columns of ∂/∂q (e_0 … e_nq−1 of (q; v)), then those of ∂/∂v
+  const int g0 = dtau_dq ? 0 : m->nq, g1 = dtau_dv ? m->nq + m->nv : m->nq;
+  if (g1 > g0 || tau_out) {
+    TanArgs<T> A = tan_args<T>(w, B, layout, std::max(1, g1 - g0), q, v, vdot, fext);
+    A.unit = 1; A.g0 = g0;
+    A.tau = (T*)tau_out;
+    A.out = ColOut<T>{(T*)dtau_dq, layout_of(layout, (long)m->nv * m->nq, B), (T*)dtau_dv, layout_of(layout, (long)m->nv * m->nv, B), m->nq, m->nv};
+    if (g1 <= g0) A.out.a = A.out.b = nullptr;  // (τ alone)
+    HIP_TRY(launch_tangent_rnea<T>(w->tan, A, w->d_tan_scratch, w->tan_threads, w->stream));
+  }
+  if (M_out) {  // ∂τ/∂v̇ = M (mass_matrix! :248-272), the full square
+    const Layout Lq = layout_of(layout, m->nq, B), Lm = layout_of(layout, (long)m->nv * m->nv, B);
+    if (m->big) HIP_TRY(launch_big_crba<T>(w->big, B, q, M_out, w->d_big_scratch, Lq, Lm, w->stream));
+    else HIP_TRY(launch_crba<T>(w->dm, B, q, M_out, Lq, Lm, 1, w->stream));
+    HIP_TRY(launch_symmetrize<T>(m->nv, B, M_out, Lm, w->stream));
+  }
+  return RBD_OK;
+}
+
+template <typename T>
+int tan_dyn_derivs(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, const void* tau, const void* fext, void* vdot_out, void* dvdot_dq, void* dvdot_dv,
+                   void* dvdot_dtau) {
+  const rbd_model* m = w->model;
+  void* vd = vdot_out ? vdot_out : w->d_tan_vd;
+  int st;
+  if ((st = tan_dynamics_value<T>(w, B, layout, q, v, tau, fext, vd))) return st;
+  const int g0 = dvdot_dq ? 0 : m->nq, g1 = dvdot_dv ? m->nq + m->nv : m->nq;
+  if (g1 > g0) {  // −∂ID/∂(q, v) at the computed v̇, column g of the right-hand sides at g; then M⁻¹ of each
+    TanArgs<T> A = tan_args<T>(w, B, layout, g1 - g0, q, v, vd, fext);
+    A.unit = 1; A.g0 = g0;
+    A.out.a = (T*)w->d_tan_rhs; A.out.La = Layout{B, 1};
+    A.sign = T(-1);
+    HIP_TRY(launch_tangent_rnea<T>(w->tan, A, w->d_tan_scratch, w->tan_threads, w->stream));
+    const ColOut<T> out{(T*)dvdot_dq, layout_of(layout, (long)m->nv * m->nq, B), (T*)dvdot_dv, layout_of(layout, (long)m->nv * m->nv, B), m->nq, m->nv};
+    HIP_TRY(launch_tangent_solve<T>(m->nv, B, g0, g1 - g0, w->d_tan_L, Layout{B, 1}, w->d_tan_rhs, 0, out, w->d_tan_x, w->stream));
+  }
+  if (dvdot_dtau) {  // ∂v̇/∂τ = M⁻¹: the solve against the identity, generated in the kernel
+    const ColOut<T> out{(T*)dvdot_dtau, layout_of(layout, (long)m->nv * m->nv, B), nullptr, Layout{0, 0}, INT32_MAX, m->nv};
+    HIP_TRY(launch_tangent_solve<T>(m->nv, B, 0, m->nv, w->d_tan_L, Layout{B, 1}, nullptr, 1, out, w->d_tan_x, w->stream));
+  }
+  return RBD_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rbd_inverse_dynamics_jvp(rbd_ws_t* w, int32_t B, int32_t ntan, const void* q, const void* v, const void* vdot, const void* fext, const void* dq,
+                             const void* dv, const void* dvdot, const void* dfext, void* tau_out, void* dtau_out, const rbd_opts_t* opts) {
+  BigOk big_ok;
+  const Opts o = read_opts(opts);
+  int st = tan_check(w, B, o);
+  if (st != RBD_OK) return st;
+  const rbd_model* m = w->model;
+  if (ntan <= 0 || missing(q, m->nq) || missing(v, m->nv) || missing(vdot, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0 || m->nv == 0) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  if ((st = tan_ensure(w, ntan))) return st;
+  Timed t(w);
+  w->last_kernel = "tangent_rnea_kernel";
+  return w->dtype == RBD_F64 ? tan_id_jvp<double>(w, B, ntan, o.layout, q, v, vdot, fext, dq, dv, dvdot, dfext, tau_out, dtau_out)
+                             : tan_id_jvp<float>(w, B, ntan, o.layout, q, v, vdot, fext, dq, dv, dvdot, dfext, tau_out, dtau_out);
+}
+
+int rbd_dynamics_jvp(rbd_ws_t* w, int32_t B, int32_t ntan, const void* q, const void* v, const void* tau, const void* fext, const void* dq, const void* dv,
+                     const void* dtau, const void* dfext, void* vdot_out, void* dvdot_out, const rbd_opts_t* opts) {
+  BigOk big_ok;
+  const Opts o = read_opts(opts);
+  int st = tan_check(w, B, o);
+  if (st != RBD_OK) return st;
+  const rbd_model* m = w->model;
+  if (ntan <= 0 || missing(q, m->nq) || missing(v, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0 || m->nv == 0) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  if ((st = tan_ensure(w, ntan))) return st;
+  Timed t(w);
+  w->last_kernel = "tangent_rnea_kernel + tangent_solve_kernel";
+  return w->dtype == RBD_F64 ? tan_dyn_jvp<double>(w, B, ntan, o.layout, q, v, tau, fext, dq, dv, dtau, dfext, vdot_out, dvdot_out)
+                             : tan_dyn_jvp<float>(w, B, ntan, o.layout, q, v, tau, fext, dq, dv, dtau, dfext, vdot_out, dvdot_out);
+}
+
+int rbd_inverse_dynamics_derivatives(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* vdot, const void* fext, void* tau_out, void* dtau_dq,
+                                     void* dtau_dv, void* M_out, const rbd_opts_t* opts) {
+  BigOk big_ok;
+  const Opts o = read_opts(opts);
+  int st = tan_check(w, B, o);
+  if (st != RBD_OK) return st;
+  const rbd_model* m = w->model;
+  if (missing(q, m->nq) || missing(v, m->nv) || missing(vdot, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0 || m->nv == 0) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  if ((st = tan_ensure(w, m->nq + m->nv))) return st;
+  Timed t(w);
+  w->last_kernel = "tangent_rnea_kernel";
+  return w->dtype == RBD_F64 ? tan_id_derivs<double>(w, B, o.layout, q, v, vdot, fext, tau_out, dtau_dq, dtau_dv, M_out)
+                             : tan_id_derivs<float>(w, B, o.layout, q, v, vdot, fext, tau_out, dtau_dq, dtau_dv, M_out);
+}
+
+int rbd_dynamics_derivatives(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* tau, const void* fext, void* vdot_out, void* dvdot_dq,
+                             void* dvdot_dv, void* dvdot_dtau, const rbd_opts_t* opts) {
+  BigOk big_ok;
+  const Opts o = read_opts(opts);
+  int st = tan_check(w, B, o);
+  if (st != RBD_OK) return st;
+  const rbd_model* m = w->model;
+  if (missing(q, m->nq) || missing(v, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0 || m->nv == 0) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  if ((st = tan_ensure(w, m->nq + m->nv))) return st;
+  Timed t(w);
+  w->last_kernel = "tangent_rnea_kernel + tangent_solve_kernel";
+  return w->dtype == RBD_F64 ? tan_dyn_derivs<double>(w, B, o.layout, q, v, tau, fext, vdot_out, dvdot_dq, dvdot_dv, dvdot_dtau)
+                             : tan_dyn_derivs<float>(w, B, o.layout, q, v, tau, fext, vdot_out, dvdot_dq, dvdot_dv, dvdot_dtau);
 }
 
 }  // extern "C"

@@ -456,6 +456,109 @@ def mass_matrix_solve_(x: torch.Tensor, state: MechanismState, rhs: torch.Tensor
     return x
 
 
+# ---- forward-mode derivatives (rbd_*_jvp / rbd_*_derivatives, header 700): what ForwardDiff.jacobian / Dual numbers through the reference compute,
+# in the raw coordinates q (a quaternion's unnormalised rotation formula; test/test_mechanism_algorithms.jl:600-652 uses exactly this).  Tangents are
+# (B, ntan·n) — direction d of a state at columns d·n … d·n+n−1 — ((ntan·n, B) with layout="soa"); Jacobians (B, nv·ncols) column-major per state, like
+# mass_matrix_ (jacobian_view turns either into (B, rows, cols)).
+
+def _check_tangent(state: MechanismState, t: Optional[torch.Tensor], n: int, ntan: int, what: str):
+    state._check(t, n * ntan, what)
+
+
+def inverse_dynamics_jvp_(dtau: Optional[torch.Tensor], state: MechanismState, vd: torch.Tensor, ntan: int, dq: Optional[torch.Tensor] = None,
+                          dv: Optional[torch.Tensor] = None, dvd: Optional[torch.Tensor] = None, externalwrenches: Optional[torch.Tensor] = None,
+                          dexternalwrenches: Optional[torch.Tensor] = None, torquesout: Optional[torch.Tensor] = None):
+    """`inverse_dynamics!` with `ntan` tangent directions per state: dτ = ∂τ/∂q dq + ∂τ/∂v dv + M dv̇ − (the dfext term).  Every tangent input is optional
+    (a zero direction); `torquesout` (optional) receives τ itself."""
+    f = state.flat
+    if int(ntan) <= 0:
+        raise ValueError("ntan must be positive")
+    _check_tangent(state, dtau, f.nv, ntan, "dtau")
+    state._check(vd, f.nv, "v̇")
+    _check_tangent(state, dq, f.nq, ntan, "dq")
+    _check_tangent(state, dv, f.nv, ntan, "dv")
+    _check_tangent(state, dvd, f.nv, ntan, "dv̇")
+    state._check(externalwrenches, 6 * f.n_bodies, "externalwrenches")
+    _check_tangent(state, dexternalwrenches, 6 * f.n_bodies, ntan, "dexternalwrenches")
+    state._check(torquesout, f.nv, "torquesout")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_inverse_dynamics_jvp(state.ws.handle, state.batch, int(ntan), _ptr(state.q), _ptr(state.v), _ptr(vd), _ptr(externalwrenches),
+                                              _ptr(dq), _ptr(dv), _ptr(dvd), _ptr(dexternalwrenches), _ptr(torquesout), _ptr(dtau), ctypes.byref(opts))
+    _raise(st, "rbd_inverse_dynamics_jvp")
+    return dtau
+
+
+def dynamics_jvp_(dvd: Optional[torch.Tensor], state: MechanismState, ntan: int, torques: Optional[torch.Tensor] = None, dq: Optional[torch.Tensor] = None,
+                  dv: Optional[torch.Tensor] = None, dtorques: Optional[torch.Tensor] = None, externalwrenches: Optional[torch.Tensor] = None,
+                  dexternalwrenches: Optional[torch.Tensor] = None, vdout: Optional[torch.Tensor] = None):
+    """`dynamics!` with `ntan` tangent directions per state, by the implicit-function identity M dv̇ = dτ − ∂ID·(dq, dv, 0, dfext) at the v̇ this call
+    computes (the CRBA + Cholesky route, `dynamics_solve!` :764, :819).  `vdout` (optional) receives v̇ itself."""
+    f = state.flat
+    if int(ntan) <= 0:
+        raise ValueError("ntan must be positive")
+    _check_tangent(state, dvd, f.nv, ntan, "dv̇")
+    state._check(torques, f.nv, "torques")
+    _check_tangent(state, dq, f.nq, ntan, "dq")
+    _check_tangent(state, dv, f.nv, ntan, "dv")
+    _check_tangent(state, dtorques, f.nv, ntan, "dτ")
+    state._check(externalwrenches, 6 * f.n_bodies, "externalwrenches")
+    _check_tangent(state, dexternalwrenches, 6 * f.n_bodies, ntan, "dexternalwrenches")
+    state._check(vdout, f.nv, "vdout")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_dynamics_jvp(state.ws.handle, state.batch, int(ntan), _ptr(state.q), _ptr(state.v), _ptr(torques), _ptr(externalwrenches),
+                                      _ptr(dq), _ptr(dv), _ptr(dtorques), _ptr(dexternalwrenches), _ptr(vdout), _ptr(dvd), ctypes.byref(opts))
+    _raise(st, "rbd_dynamics_jvp")
+    return dvd
+
+
+def inverse_dynamics_derivatives_(state: MechanismState, vd: torch.Tensor, dtau_dq: Optional[torch.Tensor] = None, dtau_dv: Optional[torch.Tensor] = None,
+                                  M_out: Optional[torch.Tensor] = None, externalwrenches: Optional[torch.Tensor] = None, torquesout: Optional[torch.Tensor] = None):
+    """The Jacobians of `inverse_dynamics!` with the external wrenches held fixed: dtau_dq (B, nv·nq), dtau_dv (B, nv·nv), M_out = ∂τ/∂v̇ = M (B, nv·nv, the
+    full square) — column-major per state; every output optional."""
+    f = state.flat
+    state._check(vd, f.nv, "v̇")
+    state._check(dtau_dq, f.nv * f.nq, "dtau_dq")
+    state._check(dtau_dv, f.nv * f.nv, "dtau_dv")
+    state._check(M_out, f.nv * f.nv, "M_out")
+    state._check(externalwrenches, 6 * f.n_bodies, "externalwrenches")
+    state._check(torquesout, f.nv, "torquesout")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_inverse_dynamics_derivatives(state.ws.handle, state.batch, _ptr(state.q), _ptr(state.v), _ptr(vd), _ptr(externalwrenches),
+                                                      _ptr(torquesout), _ptr(dtau_dq), _ptr(dtau_dv), _ptr(M_out), ctypes.byref(opts))
+    _raise(st, "rbd_inverse_dynamics_derivatives")
+    return dtau_dq, dtau_dv, M_out
+
+
+def dynamics_derivatives_(state: MechanismState, torques: Optional[torch.Tensor] = None, dvd_dq: Optional[torch.Tensor] = None,
+                          dvd_dv: Optional[torch.Tensor] = None, dvd_dtau: Optional[torch.Tensor] = None, externalwrenches: Optional[torch.Tensor] = None,
+                          vdout: Optional[torch.Tensor] = None):
+    """The Jacobians of `dynamics!` with the external wrenches held fixed: dvd_dq (B, nv·nq), dvd_dv (B, nv·nv), dvd_dtau = M⁻¹ (B, nv·nv) — column-major
+    per state; every output optional; `vdout` receives v̇."""
+    f = state.flat
+    state._check(torques, f.nv, "torques")
+    state._check(dvd_dq, f.nv * f.nq, "dvd_dq")
+    state._check(dvd_dv, f.nv * f.nv, "dvd_dv")
+    state._check(dvd_dtau, f.nv * f.nv, "dvd_dtau")
+    state._check(externalwrenches, 6 * f.n_bodies, "externalwrenches")
+    state._check(vdout, f.nv, "vdout")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_dynamics_derivatives(state.ws.handle, state.batch, _ptr(state.q), _ptr(state.v), _ptr(torques), _ptr(externalwrenches),
+                                              _ptr(vdout), _ptr(dvd_dq), _ptr(dvd_dv), _ptr(dvd_dtau), ctypes.byref(opts))
+    _raise(st, "rbd_dynamics_derivatives")
+    return dvd_dq, dvd_dv, dvd_dtau
+
+
+def jacobian_view(t: torch.Tensor, state: MechanismState, rows: int, cols: int) -> torch.Tensor:
+    """A derivative output as (B, rows, cols): a Jacobian (rows × cols, column-major per state: (B, rows·cols), or (rows·cols, B) with layout="soa"), or a
+    tangent output of `cols` directions of `rows` coordinates (direction d = column d).  A view when the layout allows, else a copy."""
+    per = t if state.layout == "aos" else t.t()
+    return per.reshape(per.shape[0], cols, rows).transpose(1, 2)
+
+
 def unpack_lower(packed, nv: int):
     """(B, nv (nv + 1) / 2) packed lower triangles (LAPACK 'L': columns back to back from their diagonals down) -> (B, nv, nv) with the strict upper part zero."""
     import numpy as np
