@@ -3,6 +3,7 @@
 // every hot-path entry point launches HIP kernels or fails with a status code.
 #include <hip/hip_runtime.h>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <unistd.h>
 
@@ -109,6 +110,17 @@ struct rbd_model {
   const StatePlan& spec_plan() const { return state.ok ? state : state_wide; }
 };
 
+// A program compiled for the mechanism at run time (rbd_jit.hip): `tried` once the answer is final (the module loaded, or no module), its source while the
+// compilation is pending (generated once).  The slots of a workspace: the SPEC_* families at spec_slot(family), then the program of a small loop mechanism, the
+// banked program and the 12 walk programs (SPEC_WALK + 4 kind + 2 rerooted + pair, as spec_walk)
+struct SpecSlot { bool tried = false; hipModule_t mod = nullptr; std::string src; };
+enum { SPEC_LOOP = SPEC_SLOTS, SPEC_BANK, SPEC_WALK, SPEC_PROGRAMS = SPEC_WALK + 12 };
+// the kernel of run_aba's last launch, as far as simulate_core routes by it: the lane-per-state program compiled for the mechanism (aba_spec_*), its fp64 form
+// with the spare rows in the HBM stash (aba_spec_gst_f64), the walk program compiled for the mechanism (aba_walk_spec), any other
+enum AbaProgram { ABA_OTHER, ABA_SPEC, ABA_SPEC_STASH, ABA_WALK_SPEC };
+// a compiled kernel that is held against the kernels built with the library on its first use by a workspace, and whether it has been (first_use)
+struct SpecKernel { hipFunction_t f = nullptr; bool checked = false; };
+
 struct rbd_ws {
   const rbd_model* model = nullptr;
   int32_t device = 0, dtype = RBD_F64, max_batch = 0;
@@ -122,23 +134,23 @@ struct rbd_ws {
   ContactModel ctm{}; void* d_cp_body = nullptr; void* d_cp_r = nullptr; void* d_hs_r = nullptr;  // soft contact tables
   void* d_tw = nullptr; void* d_cw = nullptr; void* d_s0 = nullptr; void* d_sacc = nullptr; void* d_sdot = nullptr; void* d_rows = nullptr; size_t d_rows_bytes = 0, d_tw_bytes = 0, d_cw_bytes = 0, d_s0_bytes = 0, d_sacc_bytes = 0, d_sdot_bytes = 0;
   WalkModel wm{}; void* d_walk_wk = nullptr; size_t walk_lds_bytes = 0, walk_lds_bytes_pair = 0; long walk_min_batch = 0, walk_pair_min_batch = 0, sim_walk_min_batch = 1;
-  // run-time specialised kernels (rbd_jit.hip), built on the first use of a route that has them; null: not available
-  bool spec_tried[SPEC_SLOTS] = {false, false, false, false}; hipModule_t spec_mod[SPEC_SLOTS] = {nullptr, nullptr, nullptr, nullptr};  // (by spec_slot(family))
+  // run-time specialised programs (rbd_jit.hip), loaded on the first use of a route that has them (spec_module), and their kernels; null: not available
+  SpecSlot spec_prog[SPEC_PROGRAMS];
   hipFunction_t spec_kin = nullptr, spec_jac = nullptr, spec_mom = nullptr, spec_energy = nullptr, spec_com = nullptr; long spec_kin_min_batch = (long)1 << 62;  // the kinematics by-products compiled for the mechanism (SPEC_KIN, round 6)
-  hipFunction_t spec_crba = nullptr, spec_crba_perm = nullptr, spec_chol = nullptr, spec_chol_nom = nullptr, spec_chol_packed = nullptr, spec_emit = nullptr, spec_aba = nullptr, spec_aba_nofext = nullptr, spec_aba_gst = nullptr, spec_aba_gst_nofext = nullptr, spec_rnea = nullptr, spec_loop = nullptr;
+  hipFunction_t spec_crba = nullptr, spec_crba_perm = nullptr, spec_emit = nullptr, spec_loop = nullptr, spec_bank_fused = nullptr;
+  // (the kernels checked on their first use: first_use)
+  SpecKernel spec_chol, spec_chol_nom, spec_chol_packed;  // (each checked with crba_spec_perm before it: M emitted | M_out = NULL | M as the packed triangle)
+  SpecKernel spec_aba, spec_aba_nofext, spec_aba_gst, spec_aba_gst_nofext, spec_rnea;
+  SpecKernel spec_bank_aba, spec_bank_rnea;  // (the banked programs; spec_bank_aba's check drops spec_bank_fused with it)
+  SpecKernel spec_walk[12];  // [dynamics! | inverse dynamics | dynamics!, four `simulate` stages per launch][re-rooted tree][two fp32 states per lane]
   int spec_f64_max_scratch = 0;  // (RBD_TUNE spec_f64_max_scratch; set from the measurement in workspace_create)
   // fp64 dynamics! of those mechanisms: the program with its spare rows in the HBM stash (two wavefronts per CU, a longer chain) against the one with every row in
   // LDS (one per CU): RBD_TUNE spec_f64_stash = 1 always / 0 never / -1 whichever needs fewer chain-times for the batch; the chains' ratio in percent
   int spec_f64_stash = -1, spec_f64_stash_ratio = 170, spec_f64_stash_ratio_fext = 120, spec_ncu = 256;
-  // first use of a run-time compiled dynamics! program by this workspace: its result on the first states of the call against the interpreting kernel's
-  // (first_use_check; RBD_TUNE first_use_check=0 for timing experiments with programs that are wrong by construction).  [stash program][no wrenches]
-  bool spec_first_use_check = true, spec_first_use_inject = false, spec_aba_checked[4] = {false, false, false, false}, spec_walk_checked[12] = {}, spec_bank_checked = false, spec_rnea_checked = false, spec_bank_rnea_checked = false, spec_mass_checked[3] = {false, false, false};  // (mass: [M emitted | M_out = NULL | packed triangle])
-  double spec_check_err = 0;  // (what the last check measured: max |difference| / max(1, max |reference|))
+  // first use of a run-time compiled program by this workspace: its result on the first states of the call against the kernels built with the library
+  // (first_use; RBD_TUNE first_use_check=0 for timing experiments with programs that are wrong by construction)
+  bool spec_first_use_check = true, spec_first_use_inject = false;
   int spec_aba_scratch = 0, spec_aba_nofext_scratch = 0, spec_rnea_scratch = 0;  // bytes per lane spilled by those kernels: only a kernel without any is picked on its own (it runs 3.4 times slower with: the dispatcher admits fewer wavefronts)
-  bool spec_loop_tried = false; hipModule_t spec_loop_mod = nullptr;
-  bool spec_bank_tried = false; hipModule_t spec_bank_mod = nullptr; hipFunction_t spec_bank_aba = nullptr, spec_bank_fused = nullptr, spec_bank_rnea = nullptr; std::string spec_bank_src;  // the banked kernels compiled for the mechanism
-  std::string spec_src[SPEC_SLOTS], spec_loop_src, spec_walk_src[12];  // the programs' sources while their compilation is pending (generated once)
-  bool spec_walk_tried[12] = {}; hipModule_t spec_walk_mod[12] = {}; hipFunction_t spec_walk[12] = {};  // [dynamics! | inverse dynamics | dynamics!, four `simulate` stages per launch][re-rooted tree][two fp32 states per lane]
   bool no_reroot = false, loop_no_fused = false; int spec_max_scratch = 512;  // RBD_TUNE: walk_no_reroot, loop_no_fused (tests: the original tree / the three-launch loop route), spec_max_scratch (spilled bytes per lane above which a compiled kernel steps aside)
   bool spec_walk_f32 = true;  // fp32 batches through the compiled walk kernels too (RBD_SPEC_WALK_F32=0: not)
   std::vector<double> loop_gains; bool custom_gains = false;  // rbd_workspace_set_loop_gains: this workspace's Baumgarte gains (4 per loop joint), and whether they differ from the model's
@@ -167,6 +179,7 @@ struct rbd_ws {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool ev_pending = false;
   const char* last_kernel = "";  // dominant kernel of the last rbd_dynamics / rbd_simulate / rbd_mass_matrix_solve call
+  int last_aba = ABA_OTHER;  // what the last run_aba launched (AbaProgram): simulate_core routes by it
   // the derivative entry points (rbd_tangent_kernels.hip): the tree in the reference's order for every mechanism (BigModel tables), the tangent scratch
   // (tan_threads (state, chunk) threads per launch) and the dynamics! buffers — M, its factor, c, v̇, tangent right-hand sides for tan_ntan directions,
   // and for more than 64 coordinates the solve's own vectors — allocated by the first derivative call and when ntan grows
@@ -220,6 +233,10 @@ static std::string program_source(const rbd_model* m, int32_t dtype, int32_t fam
                                    : spec_source(m->spec_plan(), m->nb, m->nq, m->nv, m->row_mask.data(), m->gravity, dtype, family);
 }
 static bool family_is_walk(int family) { return (family > SPEC_FAMILIES && family <= SPEC_FAMILIES + 4) || family == SPEC_FAMILIES + 6 || family == SPEC_FAMILIES + 7; }
+// a program's code object (rbd_jit.hip): a walk program's goes through the admission of its registers (jit_walk_code_object_get)
+static int code_object_get(const std::string& src, bool walk, bool wait, std::vector<char>* code, std::string* log) {
+  return walk ? jit_walk_code_object_get(src, wait, code, log) : jit_code_object_get(src, wait, code, log);
+}
 int64_t rbd_jit_source(const rbd_model_t* m, int32_t dtype, int32_t family, char* buf, int64_t cap) {
   const std::string s = program_source(m, dtype, family);
   if (s.empty()) return -1;
@@ -243,7 +260,7 @@ int rbd_jit_status(const rbd_model_t* m, int32_t dtype, int32_t family) {
   if (src.empty() || !jit_available()) return -1;
   std::vector<char> code;
   std::string log;
-  const int js = family_is_walk(family) ? jit_walk_code_object_get(src, false, &code, &log) : jit_code_object_get(src, false, &code, &log);
+  const int js = code_object_get(src, family_is_walk(family), false, &code, &log);
   return js == JIT_READY ? 1 : js == JIT_PENDING ? 0 : -1;
 }
 int rbd_jit_precompile(const rbd_model_t* m, int32_t dtype, char* log, int64_t cap) {
@@ -270,7 +287,7 @@ int rbd_jit_precompile(const rbd_model_t* m, int32_t dtype, char* log, int64_t c
     for (Job& j : jobs) {
       if (j.state != JIT_PENDING) continue;
       std::vector<char> code;
-      j.state = j.walk ? jit_walk_code_object_get(j.src, false, &code, &j.log) : jit_code_object_get(j.src, false, &code, &j.log);
+      j.state = code_object_get(j.src, j.walk, false, &code, &j.log);
       if (j.state == JIT_PENDING) pending = true;
       else j.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
@@ -1097,10 +1114,7 @@ int rbd_workspace_destroy(rbd_ws_t* w) {
     void* mkp[] = {w->mk.q0, w->mk.v0, w->mk.phid[0], w->mk.phid[1], w->mk.phid[2], w->mk.phid[3], w->mk.vd[0], w->mk.vd[1], w->mk.vd[2], w->mk.vd[3], w->d_vdwork};
     for (void* p : mkp) if (p) (void)hipFree(p);
   }
-  for (hipModule_t mod : w->spec_mod) if (mod) (void)hipModuleUnload(mod);
-  if (w->spec_loop_mod) (void)hipModuleUnload(w->spec_loop_mod);
-  if (w->spec_bank_mod) (void)hipModuleUnload(w->spec_bank_mod);
-  for (int k = 0; k < 12; ++k) if (w->spec_walk_mod[k]) (void)hipModuleUnload(w->spec_walk_mod[k]);
+  for (const SpecSlot& p : w->spec_prog) if (p.mod) (void)hipModuleUnload(p.mod);
   if (w->ev0) (void)hipEventDestroy(w->ev0);
   if (w->ev1) (void)hipEventDestroy(w->ev1);
   delete w;
@@ -1320,81 +1334,71 @@ static std::string walk_program_source(const rbd_model* m, int dtype, bool reroo
   return walk_spec_source(W, dtype, kind, pair);
 }
 static bool capturing(rbd_ws* w);
+// The module of a program compiled for the mechanism, loaded into its slot: returned by the call that loads it, null otherwise — loaded or given up before, no
+// hiprtc, a stream capture (a module cannot be loaded inside one: the next call outside tries again), no such program (`source()` empty), its compilation
+// still pending on a background thread (`wait` false: the kernels built with the library meanwhile) or failed (`fallback`: what serves instead).  `walk`: a walk
+// program, whose code object must pass the admission of its registers.
+template <class Source>
+static hipModule_t spec_module(rbd_ws* w, SpecSlot& p, Source source, bool walk, bool wait, const char* fallback) {
+  if (p.tried) return nullptr;
+  if (!jit_available()) { p.tried = true; return nullptr; }
+  if (capturing(w)) return nullptr;
+  if (p.src.empty()) p.src = source();
+  if (p.src.empty()) { p.tried = true; return nullptr; }
+  std::string log;
+  std::vector<char> code;
+  const int js = code_object_get(p.src, walk, wait, &code, &log);
+  if (js == JIT_PENDING) return nullptr;
+  p.tried = true;
+  std::string src;
+  src.swap(p.src);
+  if (js == JIT_FAILED || code.empty()) { g_last_hip_error = std::string("run-time compilation failed (") + fallback + "): " + log; return nullptr; }
+  if (hipModuleLoadData(&p.mod, code.data()) != hipSuccess) { (void)hipGetLastError(); p.mod = nullptr; jit_cache_discard(src); return nullptr; }
+  return p.mod;
+}
+// A kernel of a loaded program, admitted when it is there and spills at most `max_scratch` bytes per lane (kNoScratchCheck: not asked) — a kernel whose
+// registers spilled beyond a few values is slower than the kernels built with the library: it steps aside.  `scratch`: the bytes it spills.
+static const int kNoScratchCheck = INT_MAX;
+static hipFunction_t spec_kernel(hipModule_t mod, const char* name, int max_scratch, int* scratch = nullptr) {
+  hipFunction_t f = nullptr;
+  int bytes = 0;
+  if (hipModuleGetFunction(&f, mod, name) != hipSuccess) { (void)hipGetLastError(); f = nullptr; }
+  else if (max_scratch != kNoScratchCheck && (hipFuncGetAttribute(&bytes, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, f) != hipSuccess || bytes > max_scratch)) { (void)hipGetLastError(); f = nullptr; }
+  if (scratch) *scratch = bytes;
+  return f;
+}
 // aba_walk_kernel compiled for the mechanism (aba_walk_spec of rbd_walk.hpp): nullptr when unavailable (or while it is being compiled)
 static hipFunction_t spec_walk(rbd_ws* w, bool rerooted, int kind = 0, int pair = 0) {
   const int k = 4 * kind + (rerooted ? 2 : 0) + (pair ? 1 : 0);  // kind 0: dynamics!, 1: inverse dynamics, 2: dynamics! with the four stages of a `simulate` step in one launch
-  if (w->spec_walk_tried[k]) return w->spec_walk[k];
-  if (!jit_available()) { w->spec_walk_tried[k] = true; return nullptr; }
-  if (capturing(w)) return nullptr;
-  std::string& src = w->spec_walk_src[k];
-  if (src.empty()) src = walk_program_source(w->model, w->dtype, rerooted, kind, pair);
-  if (src.empty()) { w->spec_walk_tried[k] = true; return nullptr; }
-  std::string log;
-  std::vector<char> code;
-  const int js = jit_walk_code_object_get(src, !jit_async(), &code, &log);
-  if (js == JIT_PENDING) return nullptr;  // being compiled on a background thread: the interpreting walk kernel meanwhile
-  w->spec_walk_tried[k] = true;
-  if (js == JIT_FAILED || code.empty()) { g_last_hip_error = "run-time compilation failed (the interpreting kernel is used): " + log; src.clear(); src.shrink_to_fit(); return nullptr; }
-  if (hipModuleLoadData(&w->spec_walk_mod[k], code.data()) != hipSuccess) { (void)hipGetLastError(); w->spec_walk_mod[k] = nullptr; jit_cache_discard(src); return nullptr; }
-  const std::string fname = std::string(kind == 1 ? "rnea_walk_spec_" : kind == 2 ? "aba_walk_sim_spec_" : "aba_walk_spec_") + walk_spec_suffix(w->dtype, pair);
-  if (hipModuleGetFunction(&w->spec_walk[k], w->spec_walk_mod[k], fname.c_str()) != hipSuccess) { (void)hipGetLastError(); w->spec_walk[k] = nullptr; }
-  int scratch = 0;
-  const int max_scratch = w->spec_max_scratch;  // bytes per lane
-  if (w->spec_walk[k] && (hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, w->spec_walk[k]) != hipSuccess || scratch > max_scratch)) { (void)hipGetLastError(); w->spec_walk[k] = nullptr; }
-  src.clear(); src.shrink_to_fit();
-  return w->spec_walk[k];
+  if (hipModule_t mod = spec_module(w, w->spec_prog[SPEC_WALK + k], [&] { return walk_program_source(w->model, w->dtype, rerooted, kind, pair); }, true, !jit_async(),
+                                    "the interpreting kernel is used")) {
+    const std::string name = std::string(kind == 1 ? "rnea_walk_spec_" : kind == 2 ? "aba_walk_sim_spec_" : "aba_walk_spec_") + walk_spec_suffix(w->dtype, pair);
+    w->spec_walk[k].f = spec_kernel(mod, name.c_str(), w->spec_max_scratch);
+  }
+  return w->spec_walk[k].f;
 }
 // scratch of the any-size kernels (rbd_big_kernels.hip)
 static int big_scratch(rbd_ws* w, int32_t B) { return ensure(&w->d_big_scratch, &w->d_big_scratch_bytes, esize(w) * big_scratch_elems(w->big, B)); }
 // small loop mechanisms compiled for the mechanism (rbd_loop_small.hpp against constant tables): nullptr when unavailable
 static hipFunction_t spec_loop(rbd_ws* w) {
-  if (w->spec_loop_tried) return w->spec_loop;
-  if (!jit_available()) { w->spec_loop_tried = true; return nullptr; }
-  if (capturing(w)) return nullptr;
-  std::vector<int32_t> xi;
-  std::string& src = w->spec_loop_src;
-  if (src.empty()) src = loop_program_source(w->model, w->dtype, &xi);
-  if (src.empty()) { w->spec_loop_tried = true; return nullptr; }
-  std::string log;
-  std::vector<char> code;
-  const int js = jit_code_object_get(src, !jit_async(), &code, &log);
-  if (js == JIT_PENDING) return nullptr;  // the generic loop kernels meanwhile
-  w->spec_loop_tried = true;
-  if (js == JIT_FAILED || code.empty()) { g_last_hip_error = "run-time compilation failed (the generic loop kernels are used): " + log; return nullptr; }
-  if (hipModuleLoadData(&w->spec_loop_mod, code.data()) != hipSuccess) { (void)hipGetLastError(); w->spec_loop_mod = nullptr; jit_cache_discard(src); return nullptr; }
-  if (hipModuleGetFunction(&w->spec_loop, w->spec_loop_mod, w->dtype == RBD_F64 ? "loop_spec_f64" : "loop_spec_f32") != hipSuccess) { (void)hipGetLastError(); w->spec_loop = nullptr; }
-  int scratch = 0;
-  if (w->spec_loop && (hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, w->spec_loop) != hipSuccess || scratch > 0)) { (void)hipGetLastError(); w->spec_loop = nullptr; }
-  src.clear(); src.shrink_to_fit();
+  auto source = [&] { std::vector<int32_t> xi; return loop_program_source(w->model, w->dtype, &xi); };
+  if (hipModule_t mod = spec_module(w, w->spec_prog[SPEC_LOOP], source, false, !jit_async(), "the generic loop kernels are used"))
+    w->spec_loop = spec_kernel(mod, w->dtype == RBD_F64 ? "loop_spec_f64" : "loop_spec_f32", 0);
   return w->spec_loop;
 }
 
 // the two-bodies-per-lane kernels compiled for the mechanism (rbd_bank.hpp with the level structure as constants); false while unavailable
 static bool spec_bank(rbd_ws* w) {
-  if (w->spec_bank_tried) return w->spec_bank_aba != nullptr;
-  if (!jit_available() || w->model->bank_lps <= 0) { w->spec_bank_tried = true; return false; }
-  if (capturing(w)) return false;
-  std::string& src = w->spec_bank_src;
-  if (src.empty()) src = bank_program_source(w->model, w->dtype, w->bm.simple);
-  if (src.empty()) { w->spec_bank_tried = true; return false; }
-  std::string log;
-  std::vector<char> code;
-  const int js = jit_code_object_get(src, !jit_async(), &code, &log);
-  if (js == JIT_PENDING) return false;  // the kernels built with the library meanwhile
-  w->spec_bank_tried = true;
-  if (js == JIT_FAILED || code.empty()) { g_last_hip_error = "run-time compilation failed (the banked kernels built with the library are used): " + log; return false; }
-  if (hipModuleLoadData(&w->spec_bank_mod, code.data()) != hipSuccess) { (void)hipGetLastError(); w->spec_bank_mod = nullptr; jit_cache_discard(src); return false; }
-  const char* sfx = w->dtype == RBD_F64 ? "f64" : "f32";
-  auto get = [&](hipFunction_t* f, const std::string& name) {
-    int scratch = 0;
-    if (hipModuleGetFunction(f, w->spec_bank_mod, name.c_str()) != hipSuccess) { (void)hipGetLastError(); *f = nullptr; }
-    else if (hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, *f) != hipSuccess || scratch > w->spec_max_scratch) { (void)hipGetLastError(); *f = nullptr; }
-  };
-  get(&w->spec_bank_aba, std::string("aba_bank_spec_") + sfx);
-  get(&w->spec_bank_fused, std::string("aba_bank_fused_spec_") + sfx);
-  get(&w->spec_bank_rnea, std::string("rnea_bank_spec_") + sfx);
-  src.clear(); src.shrink_to_fit();
-  return w->spec_bank_aba != nullptr;
+  SpecSlot& p = w->spec_prog[SPEC_BANK];
+  if (w->model->bank_lps <= 0) p.tried = true;
+  if (hipModule_t mod = spec_module(w, p, [&] { return bank_program_source(w->model, w->dtype, w->bm.simple); }, false, !jit_async(),
+                                    "the banked kernels built with the library are used")) {
+    const std::string sfx = w->dtype == RBD_F64 ? "f64" : "f32";
+    w->spec_bank_aba.f = spec_kernel(mod, ("aba_bank_spec_" + sfx).c_str(), w->spec_max_scratch);
+    w->spec_bank_fused = spec_kernel(mod, ("aba_bank_fused_spec_" + sfx).c_str(), w->spec_max_scratch);
+    w->spec_bank_rnea.f = spec_kernel(mod, ("rnea_bank_spec_" + sfx).c_str(), w->spec_max_scratch);
+  }
+  return w->spec_bank_aba.f != nullptr;
 }
 
 namespace {
@@ -1462,48 +1466,68 @@ int dynamics_loops(rbd_ws* w, int32_t B, const Opts& o, const void* dq, const vo
 }  // namespace
 
 
-// inverse_dynamics! / dynamics_bias! (vdot == nullptr) through the lane mapping that fits the batch: same rule as run_aba
 static void spec_load(rbd_ws* w, int family, bool force = false);  // the kernels compiled for the mechanism (below)
 
-// The first result of a run-time compiled dynamics! program against the interpreting one-body-per-lane kernel (aba_kernel) on the first states of the same call
-// (up to 256): max |difference| <= tol max(1, max |reference|), tol 1e-7 in fp64, 5e-3 in fp32 (two fp32 evaluations in different operation orders).  One
-// allocation, two small launches and a synchronisation — once per program and workspace, on a call that has just waited for the module to load.
+// The first result a workspace gets from a program compiled for the mechanism is held against kernels built with the library on the first states of the same
+// call (up to 256): a program that hiprtc miscompiled (round 6 met one in an experiment: profiles/r06_experiments.txt §8) is dropped, loudly, and the call
+// recomputed.  first_use: whether this launch is that check — not when the checks are off (RBD_TUNE first_use_check=0), the kernel was checked, the stream is
+// capturing, or `wanted` is false (the outputs the check needs are missing, or the launch is a `simulate` stage or has one fused in); marks the kernel checked.
 static bool capturing(rbd_ws* w);
-static int first_use_check(rbd_ws* w, long B, const void* dq, const void* dv, const void* dtau, const void* df, const void* dvd, Layout Lq, Layout Lv, Layout Lf,
-                           const double* gravity, bool* same, bool inverse = false) {  // inverse: inverse_dynamics! — `dtau` is v̇ (input), `dvd` the torques (output), against rnea_kernel
-  const rbd_model* m = w->model;
+static bool first_use(rbd_ws* w, SpecKernel& k, bool wanted) {
+  if (!wanted || !w->spec_first_use_check || k.checked || capturing(w)) return false;
+  k.checked = true;
+  return true;
+}
+// What a check compares: the name its HIP errors carry, the reference kernels, the quantity, what the caller drops, and the tolerance — the two agree when
+// max |difference| <= tol max(floor, max |reference|)
+struct FirstUseCheck { const char* name; const char* against; const char* quantity; const char* dropped; double floor, tol; };
+// The check itself: `reference(n, ref, tmp)` computes the program's output `out` (layout Lo) for the first n states into `ref` (the same layout), with `tmp`
+// tmp_bytes of scratch.  One allocation, two small launches and a synchronisation — once per program and workspace, on a call that has just waited for the
+// module to load.  *same false: the difference is reported (stderr and g_last_hip_error); RBD_TUNE first_use_inject finds one in every check.
+template <class Reference>
+static int first_use_check(rbd_ws* w, const FirstUseCheck& c, long B, const void* out, Layout Lo, size_t tmp_bytes, Reference reference, bool* same) {
   const long n = std::min<long>(B, 256);
-  const size_t es = w->dtype == RBD_F64 ? 8 : 4;
-  const size_t elems = (size_t)(layout_base(Lv, n - 1) + (long)(m->nv - 1) * Lv.sk + 1);  // v̇'s layout, its first n states
-  void* ref = nullptr;
-  double* out = nullptr;
-  HIP_TRY(hipMalloc(&ref, elems * es));
-  if (hipMalloc((void**)&out, 2 * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(ref); return RBD_ERR_OUT_OF_MEMORY; }
-  DevModel dm = w->dm;
-  if (gravity) memcpy(dm.gravity, gravity, sizeof dm.gravity);
+  const size_t elems = (size_t)(layout_base(Lo, n - 1) + (long)(w->model->nv - 1) * Lo.sk + 1);  // the output's layout, its first n states
+  void *ref = nullptr, *tmp = nullptr;
+  double* diff = nullptr;
+  HIP_TRY(hipMalloc(&ref, elems * esize(w)));
+  if ((tmp_bytes && hipMalloc(&tmp, tmp_bytes) != hipSuccess) || hipMalloc((void**)&diff, 2 * sizeof(double)) != hipSuccess) {
+    (void)hipGetLastError(); (void)hipFree(ref); (void)hipFree(tmp); return RBD_ERR_OUT_OF_MEMORY;
+  }
   double h[2] = {0, 0};
-  hipError_t e = inverse ? (w->dtype == RBD_F64 ? launch_rnea<double>(dm, n, dq, dv, dtau, df, ref, nullptr, nullptr, Lq, Lv, Lf, w->stream)
-                                                : launch_rnea<float>(dm, n, dq, dv, dtau, df, ref, nullptr, nullptr, Lq, Lv, Lf, w->stream))
-                 : w->dtype == RBD_F64 ? launch_aba<double>(dm, n, dq, dv, dtau, df, ref, nullptr, Lq, Lv, Lf, w->stream)
-                                       : launch_aba<float>(dm, n, dq, dv, dtau, df, ref, nullptr, Lq, Lv, Lf, w->stream);
-  if (e == hipSuccess) e = w->dtype == RBD_F64 ? launch_max_diff<double>(n, m->nv, dvd, ref, Lv, out, w->stream) : launch_max_diff<float>(n, m->nv, dvd, ref, Lv, out, w->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(h, out, sizeof h, hipMemcpyDeviceToHost, w->stream);
+  hipError_t e = reference(n, ref, tmp);
+  if (e == hipSuccess) e = w->dtype == RBD_F64 ? launch_max_diff<double>(n, w->model->nv, out, ref, Lo, diff, w->stream) : launch_max_diff<float>(n, w->model->nv, out, ref, Lo, diff, w->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h, diff, sizeof h, hipMemcpyDeviceToHost, w->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(w->stream);
-  (void)hipFree(ref);
-  (void)hipFree(out);
-  if (e != hipSuccess) { g_last_hip_error = std::string("first_use_check: ") + hipGetErrorString(e); (void)hipGetLastError(); return RBD_ERR_HIP; }
-  w->spec_check_err = h[0] / std::max(1.0, h[1]);
-  *same = w->spec_check_err <= (w->dtype == RBD_F64 ? 1e-7 : 5e-3) && !w->spec_first_use_inject;
+  (void)hipFree(ref); (void)hipFree(tmp); (void)hipFree(diff);
+  if (e != hipSuccess) { g_last_hip_error = std::string(c.name) + ": " + hipGetErrorString(e); (void)hipGetLastError(); return RBD_ERR_HIP; }
+  const double err = h[0] / std::max(c.floor, h[1]);
+  *same = err <= c.tol && !w->spec_first_use_inject;
   if (!*same) {
     char msg[320];
-    snprintf(msg, sizeof msg, "%s differs from the interpreting kernel on this call's first states by %.3g of the largest %s%s: the program is dropped, the kernels built with the library serve",
-             w->last_kernel, w->spec_check_err, inverse ? "torque" : "acceleration", w->spec_first_use_inject ? " (RBD_TUNE first_use_inject)" : "");
+    snprintf(msg, sizeof msg, "%s differs from %s on this call's first states by %.3g of the largest %s%s: the %s dropped, the kernels built with the library serve",
+             w->last_kernel, c.against, err, c.quantity, w->spec_first_use_inject ? " (RBD_TUNE first_use_inject)" : "", c.dropped);
     g_last_hip_error = msg;
     fprintf(stderr, "[rbd] %s\n", msg);
   }
   return RBD_OK;
 }
+// dynamics! (v̇ in `dvd`) against the interpreting one-body-per-lane kernel aba_kernel; `inverse`: inverse_dynamics! — `dtau` is v̇ (input), `dvd` the torques
+// (output), against rnea_kernel.  1e-7 in fp64, 5e-3 in fp32 (two fp32 evaluations in different operation orders) of max(1, max |reference|).
+static int check_dynamics(rbd_ws* w, long B, const void* dq, const void* dv, const void* dtau, const void* df, const void* dvd, Layout Lq, Layout Lv, Layout Lf,
+                          const double* gravity, bool* same, bool inverse = false) {
+  DevModel dm = w->dm;
+  if (gravity) memcpy(dm.gravity, gravity, sizeof dm.gravity);
+  const bool f64 = w->dtype == RBD_F64;
+  const FirstUseCheck c{"first_use_check", "the interpreting kernel", inverse ? "torque" : "acceleration", "program is", 1.0, f64 ? 1e-7 : 5e-3};
+  return first_use_check(w, c, B, dvd, Lv, 0, [&](long n, void* ref, void*) {
+    if (inverse) return f64 ? launch_rnea<double>(dm, n, dq, dv, dtau, df, ref, nullptr, nullptr, Lq, Lv, Lf, w->stream)
+                            : launch_rnea<float>(dm, n, dq, dv, dtau, df, ref, nullptr, nullptr, Lq, Lv, Lf, w->stream);
+    return f64 ? launch_aba<double>(dm, n, dq, dv, dtau, df, ref, nullptr, Lq, Lv, Lf, w->stream) : launch_aba<float>(dm, n, dq, dv, dtau, df, ref, nullptr, Lq, Lv, Lf, w->stream);
+  }, same);
+}
 
+// inverse_dynamics! / dynamics_bias! (vdot == nullptr) through the lane mapping that fits the batch: same rule as run_aba
 static int run_rnea(rbd_ws* w, int32_t B, int mapping, const void* dq, const void* dv, const void* dvd, const void* df, void* dtau, void* dqd,
                     Layout Lq, Layout Lv, Layout Lf, void* dacc = nullptr, void* djw = nullptr) {
   const rbd_model* m = w->model;
@@ -1526,7 +1550,7 @@ static int run_rnea(rbd_ws* w, int32_t B, int mapping, const void* dq, const voi
   const bool bodies = dacc || djw, rows_out = Lf.sb == 1;
   if (!dqd && (mapping == RBD_ALGO_ABA_COMPILED || (mapping == RBD_ALGO_ABA && !(bodies && w->dtype == RBD_F64 && !rows_out)))) {
     if (mapping == RBD_ALGO_ABA_COMPILED || B >= w->spec_rnea_min_batch) spec_load(w, SPEC_RNEA, mapping == RBD_ALGO_ABA_COMPILED);
-    if (w->spec_rnea && (mapping == RBD_ALGO_ABA_COMPILED || (B >= w->spec_rnea_min_batch && w->spec_rnea_scratch == 0))) {
+    if (w->spec_rnea.f && (mapping == RBD_ALGO_ABA_COMPILED || (B >= w->spec_rnea_min_batch && w->spec_rnea_scratch == 0))) {
       long Bl = B;
       const long ld = (long)B + 64;  // scratch rows 256 bytes past a power of two apart
       const size_t es = w->dtype == RBD_F64 ? 8 : 4, each = es * 6 * (size_t)m->nb * (size_t)ld;
@@ -1540,7 +1564,7 @@ static int run_rnea(rbd_ws* w, int32_t B, int mapping, const void* dq, const voi
         if (djw) ojw = (char*)w->d_rows + each;
       }
       void* args[] = {&Bl, &dq, &dv, &dvd, &df, &dtau, &Lq, &Lv, &Lf, &oacc, &ojw, &Lo};
-      HIP_TRY(hipModuleLaunchKernel(w->spec_rnea, (unsigned)((B + 63) / 64), 1, 1, 64, 1, 1, 0, w->stream, args, nullptr));
+      HIP_TRY(hipModuleLaunchKernel(w->spec_rnea.f, (unsigned)((B + 63) / 64), 1, 1, 64, 1, 1, 0, w->stream, args, nullptr));
       if (staged) {
         if (dacc && djw) HIP_TRY(launch_rows_to_state_major<float>(6 * m->nb, B, ld, oacc, dacc, ojw, djw, w->stream));
         else HIP_TRY(launch_rows_to_state_major<float>(6 * m->nb, B, ld, dacc ? oacc : ojw, dacc ? dacc : djw, nullptr, nullptr, w->stream));
@@ -1548,16 +1572,12 @@ static int run_rnea(rbd_ws* w, int32_t B, int mapping, const void* dq, const voi
       w->last_kernel = w->dtype == RBD_F64 ? "rnea_spec_f64 (compiled for the mechanism at run time)"
                        : staged            ? "rnea_spec_f32 (compiled for the mechanism at run time) + rows_to_state_major_kernel"
                                            : "rnea_spec_f32 (compiled for the mechanism at run time)";
-      if (dvd && dtau && w->spec_first_use_check && !w->spec_rnea_checked && !capturing(w)) {  // (first use of this program by this workspace: first_use_check)
-        w->spec_rnea_checked = true;
-        bool same = true;
-        if (int st = first_use_check(w, B, dq, dv, dvd, df, dtau, Lq, Lv, Lf, nullptr, &same, true)) return st;
-        if (!same) {
-          w->spec_rnea = nullptr;
-          return mapping == RBD_ALGO_ABA_COMPILED ? RBD_ERR_UNSUPPORTED : run_rnea(w, B, mapping, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, dacc, djw);
-        }
-      }
-      return RBD_OK;
+      bool same = true;
+      if (first_use(w, w->spec_rnea, dvd && dtau))
+        if (int st = check_dynamics(w, B, dq, dv, dvd, df, dtau, Lq, Lv, Lf, nullptr, &same, true)) return st;
+      if (same) return RBD_OK;
+      w->spec_rnea.f = nullptr;
+      return mapping == RBD_ALGO_ABA_COMPILED ? RBD_ERR_UNSUPPORTED : run_rnea(w, B, mapping, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, dacc, djw);
     }
   }
   if (mapping == RBD_ALGO_ABA_COMPILED) return RBD_ERR_UNSUPPORTED;
@@ -1572,14 +1592,13 @@ static int run_rnea(rbd_ws* w, int32_t B, int mapping, const void* dq, const voi
       const long per = pair ? 128 : 64;
       HIP_TRY(hipModuleLaunchKernel(f, (unsigned)((B + per - 1) / per), 1, 1, 64u * (unsigned)w->wm.G, 1, 1, 0, w->stream, args, nullptr));
       w->last_kernel = pair ? "rnea_walk_spec (compiled for the mechanism, two fp32 states per lane)" : "rnea_walk_spec (compiled for the mechanism)";
-      const int k = 4 + (pair ? 1 : 0);
-      if (dvd && dtau && w->spec_first_use_check && !w->spec_walk_checked[k] && !capturing(w)) {
-        w->spec_walk_checked[k] = true;
-        bool same = true;
-        if (int st = first_use_check(w, B, dq, dv, dvd, df, dtau, Lq, Lv, Lf, nullptr, &same, true)) return st;
-        if (!same) { w->spec_walk[k] = nullptr; return run_rnea(w, B, mapping, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, dacc, djw); }
-      }
-      return RBD_OK;
+      SpecKernel& k = w->spec_walk[4 + (pair ? 1 : 0)];
+      bool same = true;
+      if (first_use(w, k, dvd && dtau))
+        if (int st = check_dynamics(w, B, dq, dv, dvd, df, dtau, Lq, Lv, Lf, nullptr, &same, true)) return st;
+      if (same) return RBD_OK;
+      k.f = nullptr;
+      return run_rnea(w, B, mapping, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, dacc, djw);
     }
     w->last_kernel = pair ? "rnea_walk_kernel (two fp32 states per lane)" : "rnea_walk_kernel";
     if (w->dtype == RBD_F64) HIP_TRY(launch_rnea_walk<double>(w->wm, m->track.has_floating, m->track.general, 0, B, w->walk_lds_bytes, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, w->stream, dacc, djw));
@@ -1591,20 +1610,18 @@ static int run_rnea(rbd_ws* w, int32_t B, int mapping, const void* dq, const voi
   } else if (banks) {
     const int ncol = m->has3dof ? 3 : 1;
     w->last_kernel = "rnea_bank_kernel";
-    if (spec_bank(w) && w->spec_bank_rnea) {  // the same kernel compiled against this mechanism's level structure (rbd_jit.hip spec_bank_source)
+    if (spec_bank(w) && w->spec_bank_rnea.f) {  // the same kernel compiled against this mechanism's level structure (rbd_jit.hip spec_bank_source)
       BankModel bm = w->bm;
       long Bl = B;
       int nc = ncol;
       const long spw = 64 / bm.lps, waves = (B + spw - 1) / spw;
       void* args[] = {&bm, &Bl, &nc, (void*)&dq, (void*)&dv, (void*)&dvd, (void*)&df, (void*)&dtau, (void*)&dqd, &Lq, &Lv, &Lf, (void*)&dacc, (void*)&djw};
-      HIP_TRY(hipModuleLaunchKernel(w->spec_bank_rnea, (unsigned)((waves + 3) / 4), 1, 1, 256, 1, 1, 0, w->stream, args, nullptr));
+      HIP_TRY(hipModuleLaunchKernel(w->spec_bank_rnea.f, (unsigned)((waves + 3) / 4), 1, 1, 256, 1, 1, 0, w->stream, args, nullptr));
       w->last_kernel = "rnea_bank_kernel (compiled for the mechanism at run time)";
-      if (dvd && dtau && w->spec_first_use_check && !w->spec_bank_rnea_checked && !capturing(w)) {
-        w->spec_bank_rnea_checked = true;
-        bool same = true;
-        if (int st = first_use_check(w, B, dq, dv, dvd, df, dtau, Lq, Lv, Lf, nullptr, &same, true)) return st;
-        if (!same) { w->spec_bank_rnea = nullptr; return run_rnea(w, B, mapping, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, dacc, djw); }
-      }
+      bool same = true;
+      if (first_use(w, w->spec_bank_rnea, dvd && dtau))
+        if (int st = check_dynamics(w, B, dq, dv, dvd, df, dtau, Lq, Lv, Lf, nullptr, &same, true)) return st;
+      if (!same) { w->spec_bank_rnea.f = nullptr; return run_rnea(w, B, mapping, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, dacc, djw); }
     } else
     if (w->dtype == RBD_F64) HIP_TRY(launch_rnea_bank<double>(w->bm, B, ncol, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, w->stream, dacc, djw));
     else HIP_TRY(launch_rnea_bank<float>(w->bm, B, ncol, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, w->stream, dacc, djw));
@@ -1646,22 +1663,22 @@ static int run_aba(rbd_ws* w, int32_t B, int algorithm, const void* dq, const vo
     if (algorithm == RBD_ALGO_ABA_COMPILED || B >= spec_from) spec_load(w, SPEC_ABA, algorithm == RBD_ALGO_ABA_COMPILED);
     // without external wrenches: the instantiation that holds no registers for them.  Left to itself (RBD_ALGO_ABA) the library takes a compiled kernel only
     // when it spilled nothing
-    const bool nofext = df == nullptr && w->spec_aba_nofext != nullptr;
-    hipFunction_t faba = nofext ? w->spec_aba_nofext : w->spec_aba;
+    const bool nofext = df == nullptr && w->spec_aba_nofext.f != nullptr;
+    SpecKernel* faba = nofext ? &w->spec_aba_nofext : &w->spec_aba;
     const int faba_scratch = nofext ? w->spec_aba_nofext_scratch : w->spec_aba_scratch;
     // fp64: the program with the spare rows in the HBM stash runs two wavefronts per CU where the one with every row in LDS runs one, on a chain 1.7 times as
     // long (1.2 with wrenches: randmech(), 16 384 states 84 against 50 us, 65 536 states 176 against 200; with wrenches 218 against 393) — the one that needs
     // less time for this batch's rounds
     bool stash_program = false;
-    if (spec_f64 && faba) {
-      hipFunction_t const fg = nofext ? w->spec_aba_gst_nofext : w->spec_aba_gst;
+    if (spec_f64 && faba->f) {
+      SpecKernel* const fg = nofext ? &w->spec_aba_gst_nofext : &w->spec_aba_gst;
       const long waves = (B + 63) / 64, r_lds = (waves + w->spec_ncu - 1) / w->spec_ncu, r_gst = (waves + 2 * w->spec_ncu - 1) / (2 * w->spec_ncu);
       const long ratio = nofext ? w->spec_f64_stash_ratio : w->spec_f64_stash_ratio_fext;
-      if (fg && (w->spec_f64_stash > 0 || (w->spec_f64_stash < 0 && r_lds * 100 > r_gst * ratio))) { faba = fg; stash_program = true; }
+      if (fg->f && (w->spec_f64_stash > 0 || (w->spec_f64_stash < 0 && r_lds * 100 > r_gst * ratio))) { faba = fg; stash_program = true; }
     }
     // (fp64: the program spills by construction — its per-body leave-behind does not fit 512 registers in doubles; it is taken up to spec_f64_max_scratch bytes
     //  per lane because what it replaces is the one-body-per-lane kernel, not a walk kernel)
-    if (faba && (algorithm == RBD_ALGO_ABA_COMPILED || (B >= spec_from && (faba_scratch == 0 || (spec_f64 && faba_scratch <= w->spec_f64_max_scratch))))) {
+    if (faba->f && (algorithm == RBD_ALGO_ABA_COMPILED || (B >= spec_from && (faba_scratch == 0 || (spec_f64 && faba_scratch <= w->spec_f64_max_scratch))))) {
       Timed t(w);
       long Bl = B;
       const double* gv = gravity ? gravity : m->gravity;
@@ -1677,18 +1694,15 @@ static int run_aba(rbd_ws* w, int32_t B, int algorithm, const void* dq, const vo
         }
       }
       void* args64[] = {&Bl, &dq, &dv, &dtau, &df, &dvd, &dqd, &Lq, &Lv, &Lf, &gxd, &gyd, &gzd, &F, &stash};
-      HIP_TRY(hipModuleLaunchKernel(faba, (unsigned)((B + 63) / 64), 1, 1, 64, 1, 1, 0, w->stream, w->dtype == RBD_F64 ? args64 : args, nullptr));
+      HIP_TRY(hipModuleLaunchKernel(faba->f, (unsigned)((B + 63) / 64), 1, 1, 64, 1, 1, 0, w->stream, w->dtype == RBD_F64 ? args64 : args, nullptr));
       w->last_kernel = stash_program ? "aba_spec_gst_f64 (compiled for the mechanism at run time; spare rows in the HBM stash)"
                        : w->dtype == RBD_F64 ? "aba_spec_f64 (compiled for the mechanism at run time)" : "aba_spec_f32 (compiled for the mechanism at run time)";
-      // The first result a workspace gets from one of these programs is held against the interpreting one-body-per-lane kernel on the call's first states: a
-      // program that hiprtc miscompiled (round 6 met one in an experiment: profiles/r06_experiments.txt §8) is dropped, loudly, and the call recomputed
-      bool& checked = w->spec_aba_checked[(stash_program ? 2 : 0) + (nofext ? 1 : 0)];
-      if (mk || !dv || !dvd || !w->spec_first_use_check || checked || capturing(w)) return RBD_OK;
-      checked = true;
+      w->last_aba = stash_program ? ABA_SPEC_STASH : ABA_SPEC;
       bool same = true;
-      if (int st = first_use_check(w, B, dq, dv, dtau, df, dvd, Lq, Lv, Lf, gravity, &same)) return st;
+      if (first_use(w, *faba, !mk && dv && dvd))
+        if (int st = check_dynamics(w, B, dq, dv, dtau, df, dvd, Lq, Lv, Lf, gravity, &same)) return st;
       if (same) return RBD_OK;
-      (stash_program ? (nofext ? w->spec_aba_gst_nofext : w->spec_aba_gst) : (nofext ? w->spec_aba_nofext : w->spec_aba)) = nullptr;
+      faba->f = nullptr;
       if (algorithm == RBD_ALGO_ABA_COMPILED) return RBD_ERR_UNSUPPORTED;
       // (falls through: the call is recomputed below)
     }
@@ -1704,6 +1718,7 @@ static int run_aba(rbd_ws* w, int32_t B, int algorithm, const void* dq, const vo
   if (mk && pick != RBD_ALGO_ABA_WALK) return RBD_ERR_UNSUPPORTED;
   Timed t(w);
   w->last_kernel = pick == RBD_ALGO_ABA_BANKS ? "aba_bank_kernel" : "aba_kernel";
+  w->last_aba = ABA_OTHER;
   if (pick == RBD_ALGO_ABA_WALK) {
     // the tree re-rooted at its centre (rbd_reroot.hpp) when there is one: fewer steps per track, better balanced tracks (RBD_WALK_NO_REROOT=1: the original tree)
     const bool no_rr = w->no_reroot;
@@ -1717,6 +1732,7 @@ static int run_aba(rbd_ws* w, int32_t B, int algorithm, const void* dq, const vo
     const int wkind = (mk && mk->stage == 4) ? 2 : 0;  // (all four stages of a `simulate` step in one launch: the instantiation with the passes inside a loop)
     if (hipFunction_t f = ((w->dtype == RBD_F64 || w->spec_walk_f32) && (B >= w->spec_walk_min_batch || wkind == 2)) ? spec_walk(w, rr, wkind, pair) : nullptr) {  // the same kernel compiled for this mechanism
       w->last_kernel = pair ? "aba_walk_spec (compiled for the mechanism, two fp32 states per lane)" : "aba_walk_spec (compiled for the mechanism)";
+      w->last_aba = ABA_WALK_SPEC;
       long Bl = B;
       Layout lq = Lq, lv = Lv, lf = Lf;
       double gx = wm.gravity[0], gy = wm.gravity[1], gz = wm.gravity[2];
@@ -1724,14 +1740,11 @@ static int run_aba(rbd_ws* w, int32_t B, int algorithm, const void* dq, const vo
       void* args[] = {&Bl, (void*)&dq, (void*)&dv, (void*)&dtau, (void*)&df, (void*)&dvd, (void*)&dqd, &lq, &lv, &lf, &gx, &gy, &gz, &F};
       const long per = pair ? 128 : 64;
       HIP_TRY(hipModuleLaunchKernel(f, (unsigned)((B + per - 1) / per), 1, 1, 64u * (unsigned)wm.G, 1, 1, 0, w->stream, args, nullptr));
-      // (first use of this program by this workspace: see first_use_check; a program that differs is dropped and the call recomputed on the kernel built with the library)
-      const int k = 4 * wkind + (rr ? 2 : 0) + (pair ? 1 : 0);
-      if (!mk && dv && dvd && w->spec_first_use_check && !w->spec_walk_checked[k] && !capturing(w)) {
-        w->spec_walk_checked[k] = true;
-        bool same = true;
-        if (int st = first_use_check(w, B, dq, dv, dtau, df, dvd, Lq, Lv, Lf, gravity, &same)) return st;
-        if (!same) { w->spec_walk[k] = nullptr; return run_aba(w, B, algorithm, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, gravity, fuse, mk); }
-      }
+      SpecKernel& k = w->spec_walk[4 * wkind + (rr ? 2 : 0) + (pair ? 1 : 0)];
+      bool same = true;
+      if (first_use(w, k, !mk && dv && dvd))
+        if (int st = check_dynamics(w, B, dq, dv, dtau, df, dvd, Lq, Lv, Lf, gravity, &same)) return st;
+      if (!same) { k.f = nullptr; return run_aba(w, B, algorithm, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, gravity, fuse, mk); }
     } else if (mk) return RBD_ERR_UNSUPPORTED;
     else
     if (w->dtype == RBD_F64) HIP_TRY(launch_aba_walk<double>(wm, TP.has_floating, TP.general, 0, B, lds, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, w->stream));
@@ -1739,7 +1752,7 @@ static int run_aba(rbd_ws* w, int32_t B, int algorithm, const void* dq, const vo
   } else if (pick == RBD_ALGO_ABA_BANKS) {
     BankModel bm = w->bm;
     if (gravity) memcpy(bm.gravity, gravity, sizeof bm.gravity);
-    hipFunction_t f = spec_bank(w) ? (fuse ? w->spec_bank_fused : w->spec_bank_aba) : nullptr;
+    hipFunction_t f = spec_bank(w) ? (fuse ? w->spec_bank_fused : w->spec_bank_aba.f) : nullptr;
     if (f) {  // the same kernel compiled against this mechanism's level structure: the level loops unrolled (rbd_jit.hip spec_bank_source)
       MkFuse F{};
       F.stage = -1;
@@ -1749,12 +1762,10 @@ static int run_aba(rbd_ws* w, int32_t B, int algorithm, const void* dq, const vo
       void* args[] = {&bm, &Bl, (void*)&dq, (void*)&dv, (void*)&dtau, (void*)&df, (void*)&dvd, (void*)&dqd, &Lq, &Lv, &Lf, &F};
       HIP_TRY(hipModuleLaunchKernel(f, (unsigned)((waves + 3) / 4), 1, 1, 256, 1, 1, 0, w->stream, args, nullptr));
       w->last_kernel = "aba_bank_kernel (compiled for the mechanism at run time)";
-      if (!fuse && dv && dvd && w->spec_first_use_check && !w->spec_bank_checked && !capturing(w)) {  // (first use: see first_use_check)
-        w->spec_bank_checked = true;
-        bool same = true;
-        if (int st = first_use_check(w, B, dq, dv, dtau, df, dvd, Lq, Lv, Lf, gravity, &same)) return st;
-        if (!same) { w->spec_bank_aba = w->spec_bank_fused = nullptr; return run_aba(w, B, algorithm, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, gravity, fuse, mk); }
-      }
+      bool same = true;
+      if (first_use(w, w->spec_bank_aba, !fuse && dv && dvd))
+        if (int st = check_dynamics(w, B, dq, dv, dtau, df, dvd, Lq, Lv, Lf, gravity, &same)) return st;
+      if (!same) { w->spec_bank_aba.f = w->spec_bank_fused = nullptr; return run_aba(w, B, algorithm, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, gravity, fuse, mk); }
     } else
     if (w->dtype == RBD_F64) HIP_TRY(launch_aba_bank<double>(bm, B, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, w->stream, fuse));
     else HIP_TRY(launch_aba_bank<float>(bm, B, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, w->stream, fuse));
@@ -1779,65 +1790,44 @@ static bool capturing(rbd_ws* w) {
   return cs != hipStreamCaptureStatusNone;
 }
 static void spec_load(rbd_ws* w, int family, bool force) {
-  const int slot = spec_slot(family);
-  if (w->spec_tried[slot]) return;
   const rbd_model* m = w->model;
-  if (!m->spec_plan().ok || !jit_available() || !spec_has(family, w->dtype, m->nb, m->nq, m->nv, m->spec_plan().n3)) { w->spec_tried[slot] = true; return; }
-  if (capturing(w)) return;  // a module cannot be loaded inside a stream capture: the interpreting kernels serve it, the next call outside tries again
-  std::string log;
-  std::string& src = w->spec_src[slot];
-  if (src.empty()) src = spec_source(m->spec_plan(), m->nb, m->nq, m->nv, m->row_mask.data(), m->gravity, w->dtype, family);
-  if (src.empty()) { w->spec_tried[slot] = true; return; }  // (no such program for this mechanism: fp64 dynamics! of a tree the walk kernels take)
-  std::vector<char> code;
-  const int js = jit_code_object_get(src, force || !jit_async(), &code, &log);
-  if (js == JIT_PENDING) return;
-  w->spec_tried[slot] = true;
-  if (js == JIT_FAILED || code.empty()) { g_last_hip_error = "run-time compilation failed (the interpreting kernels are used): " + log; src.clear(); src.shrink_to_fit(); return; }
-  hipModule_t& mod = w->spec_mod[slot];
-  if (hipModuleLoadData(&mod, code.data()) != hipSuccess) { (void)hipGetLastError(); mod = nullptr; jit_cache_discard(src); return; }
-  auto get = [&](hipFunction_t* f, const char* name) { if (hipModuleGetFunction(f, mod, name) != hipSuccess) { (void)hipGetLastError(); *f = nullptr; } };
-  // a kernel whose registers spilled beyond a few values is slower than the kernels that interpret the mechanism: it steps aside
-  auto fits = [&](hipFunction_t* f, int* bytes = nullptr) {
-    int scratch = 0;
-    // bytes per lane (the fp64 dynamics! program of round 6 spills by construction and is taken with it: what it replaces is the one-body-per-lane kernel)
-    const int max_scratch = (family == SPEC_ABA && w->dtype == RBD_F64) ? std::max(w->spec_max_scratch, w->spec_f64_max_scratch) : w->spec_max_scratch;
-    if (*f && (hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, *f) != hipSuccess || scratch > max_scratch)) { (void)hipGetLastError(); *f = nullptr; }
-    if (bytes) *bytes = scratch;
-  };
-  int ncu = 256;
-  (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, w->device);
-  if (family == SPEC_MASS) {
-    get(&w->spec_crba, w->dtype == RBD_F64 ? "crba_spec_f64" : "crba_spec_f32");
+  SpecSlot& p = w->spec_prog[spec_slot(family)];
+  if (!p.tried && (!m->spec_plan().ok || !spec_has(family, w->dtype, m->nb, m->nq, m->nv, m->spec_plan().n3))) p.tried = true;
+  // (an empty source: no such program for this mechanism — fp64 dynamics! of a tree the walk kernels take)
+  const hipModule_t mod = spec_module(w, p, [&] { return program_source(m, w->dtype, family); }, false, force || !jit_async(), "the interpreting kernels are used");
+  if (!mod) return;
+  const bool f64 = w->dtype == RBD_F64;
+  const int cap = w->spec_max_scratch;  // bytes per lane
+  if (family == SPEC_MASS) {  // (no scratch check)
+    w->spec_crba = spec_kernel(mod, f64 ? "crba_spec_f64" : "crba_spec_f32", kNoScratchCheck);
     if (spec_has_chol(w->dtype, m->nv)) {
-      get(&w->spec_crba_perm, "crba_spec_perm_f32");
-      get(&w->spec_chol, "chol_spec_f32");
-      get(&w->spec_chol_packed, "chol_spec_packed_f32");  // M as the packed lower triangle (rbd_mass_matrix_solve_packed); optional
-      get(&w->spec_chol_nom, "chol_spec_nom_f32");        // no M wanted: a kernel of its own (rbd_spec.hpp: EMIT)
-      if (!w->spec_chol_nom) w->spec_chol = nullptr;
-      get(&w->spec_emit, "emit_spec_f32");
-      if (!w->spec_crba_perm || !w->spec_chol || !w->spec_emit) w->spec_crba_perm = w->spec_chol = w->spec_emit = nullptr;
-    } else if (w->dtype == RBD_F64 && spec_has_chol(RBD_F32, m->nv)) {
-      get(&w->spec_emit, "emit_spec_f64");  // fp64: the emitter alone (the staging buffer in the original order; the dense kernel is rbd_kernels.hip's)
+      w->spec_crba_perm = spec_kernel(mod, "crba_spec_perm_f32", kNoScratchCheck);
+      w->spec_chol.f = spec_kernel(mod, "chol_spec_f32", kNoScratchCheck);
+      w->spec_chol_packed.f = spec_kernel(mod, "chol_spec_packed_f32", kNoScratchCheck);  // M as the packed lower triangle (rbd_mass_matrix_solve_packed); optional
+      w->spec_chol_nom.f = spec_kernel(mod, "chol_spec_nom_f32", kNoScratchCheck);        // no M wanted: a kernel of its own (rbd_spec.hpp: EMIT)
+      if (!w->spec_chol_nom.f) w->spec_chol.f = nullptr;
+      w->spec_emit = spec_kernel(mod, "emit_spec_f32", kNoScratchCheck);
+      if (!w->spec_crba_perm || !w->spec_chol.f || !w->spec_emit) w->spec_crba_perm = w->spec_chol.f = w->spec_emit = nullptr;
+    } else if (f64 && spec_has_chol(RBD_F32, m->nv)) {
+      w->spec_emit = spec_kernel(mod, "emit_spec_f64", kNoScratchCheck);  // fp64: the emitter alone (the staging buffer in the original order; the dense kernel is rbd_kernels.hip's)
     }
   } else if (family == SPEC_ABA) {
-    get(&w->spec_aba, w->dtype == RBD_F64 ? "aba_spec_f64" : "aba_spec_f32");
-    fits(&w->spec_aba, &w->spec_aba_scratch);
-    get(&w->spec_aba_nofext, w->dtype == RBD_F64 ? "aba_spec_nofext_f64" : "aba_spec_nofext_f32");  // the instantiation for calls without external wrenches (rbd_spec.hpp: FEXT)
-    fits(&w->spec_aba_nofext, &w->spec_aba_nofext_scratch);
-    if (w->dtype == RBD_F64) {  // (the stash programs step in only where the LDS ones are taken: no threshold of their own)
-      get(&w->spec_aba_gst, "aba_spec_gst_f64"); fits(&w->spec_aba_gst);
-      get(&w->spec_aba_gst_nofext, "aba_spec_gst_nofext_f64"); fits(&w->spec_aba_gst_nofext);
+    // (the fp64 dynamics! program of round 6 spills by construction and is taken with it: what it replaces is the one-body-per-lane kernel)
+    const int aba_cap = f64 ? std::max(cap, w->spec_f64_max_scratch) : cap;
+    w->spec_aba.f = spec_kernel(mod, f64 ? "aba_spec_f64" : "aba_spec_f32", aba_cap, &w->spec_aba_scratch);
+    w->spec_aba_nofext.f = spec_kernel(mod, f64 ? "aba_spec_nofext_f64" : "aba_spec_nofext_f32", aba_cap, &w->spec_aba_nofext_scratch);  // the instantiation for calls without external wrenches (rbd_spec.hpp: FEXT)
+    if (f64) {  // (the stash programs step in only where the LDS ones are taken: no threshold of their own)
+      w->spec_aba_gst.f = spec_kernel(mod, "aba_spec_gst_f64", aba_cap);
+      w->spec_aba_gst_nofext.f = spec_kernel(mod, "aba_spec_gst_nofext_f64", aba_cap);
     }
   } else if (family == SPEC_RNEA) {
-    get(&w->spec_rnea, w->dtype == RBD_F64 ? "rnea_spec_f64" : "rnea_spec_f32");
-    fits(&w->spec_rnea, &w->spec_rnea_scratch);
+    w->spec_rnea.f = spec_kernel(mod, f64 ? "rnea_spec_f64" : "rnea_spec_f32", cap, &w->spec_rnea_scratch);
   } else if (family == SPEC_KIN) {  // (a kernel that spilled steps aside: the lane-per-body kin_kernel serves)
-    int sc = 0;
-    get(&w->spec_kin, w->dtype == RBD_F64 ? "kin_spec_f64" : "kin_spec_f32"); fits(&w->spec_kin, &sc); if (sc) w->spec_kin = nullptr;
-    get(&w->spec_jac, w->dtype == RBD_F64 ? "jac_spec_f64" : "jac_spec_f32"); fits(&w->spec_jac, &sc); if (sc) w->spec_jac = nullptr;
-    get(&w->spec_mom, w->dtype == RBD_F64 ? "mom_spec_f64" : "mom_spec_f32"); fits(&w->spec_mom, &sc); if (sc) w->spec_mom = nullptr;
-    get(&w->spec_energy, w->dtype == RBD_F64 ? "energy_spec_f64" : "energy_spec_f32"); fits(&w->spec_energy, &sc); if (sc) w->spec_energy = nullptr;
-    get(&w->spec_com, w->dtype == RBD_F64 ? "com_spec_f64" : "com_spec_f32"); fits(&w->spec_com, &sc); if (sc) w->spec_com = nullptr;
+    w->spec_kin = spec_kernel(mod, f64 ? "kin_spec_f64" : "kin_spec_f32", 0);
+    w->spec_jac = spec_kernel(mod, f64 ? "jac_spec_f64" : "jac_spec_f32", 0);
+    w->spec_mom = spec_kernel(mod, f64 ? "mom_spec_f64" : "mom_spec_f32", 0);
+    w->spec_energy = spec_kernel(mod, f64 ? "energy_spec_f64" : "energy_spec_f32", 0);
+    w->spec_com = spec_kernel(mod, f64 ? "com_spec_f64" : "com_spec_f32", 0);
   }
 }
 // one launch of a by-product kernel compiled for the mechanism (rbd_spec.hpp kin_spec<T, WHAT>): a wavefront of 64 states per workgroup
@@ -1861,7 +1851,7 @@ static hipError_t launch_crba_spec(rbd_ws* w, hipFunction_t f, long B, const voi
 static hipError_t launch_chol_spec(rbd_ws* w, long B, const void* Mg, const void* tau, const void* c, void* x, Layout Lv, void* Mcopy, Layout Lc, bool packed = false) {
   int* notpd = w->d_notpd;
   void* args[] = {&B, &Mg, &tau, &c, &x, &Lv, &notpd, &Mcopy, &Lc};
-  return hipModuleLaunchKernel(!Mcopy ? w->spec_chol_nom : packed ? w->spec_chol_packed : w->spec_chol, (unsigned)((B + 15) / 16), 1, 1, 64, 1, 1, 0, w->stream, args, nullptr);
+  return hipModuleLaunchKernel(!Mcopy ? w->spec_chol_nom.f : packed ? w->spec_chol_packed.f : w->spec_chol.f, (unsigned)((B + 15) / 16), 1, 1, 64, 1, 1, 0, w->stream, args, nullptr);
 }
 
 // The staging buffer of M for the one-lane-per-state CRBA when the caller's layout is AOS: grouped by 16 states (Layout{16, -nv nv}).  Its
@@ -1920,43 +1910,21 @@ static int run_crba(rbd_ws* w, int32_t B, int layout, const void* dq, void* dM, 
   return RBD_OK;
 }
 
+// The first-use check of the fp32 mass_matrix! + Cholesky solve on the two kernels compiled for the mechanism (crba_spec_perm + chol_spec[_nom | _packed]) — taken
+// from 256 states since round 6 —: x on the first states of the call against crba_kernel + the dense Cholesky kernel, 2e-2 of the largest |x| (two fp32
+// factorisations in different elimination orders of a matrix of condition 1e4).  Column-per-state callers only (the compiled pair's scope).
+static int check_solve(rbd_ws* w, long B, const void* dq, const void* dtau, const void* dc, const void* dx, Layout Lq, Layout Lm, Layout Lv, bool* same) {
+  const int nv = w->model->nv;
+  const FirstUseCheck c{"first_use_check_solve", "crba_kernel + the dense Cholesky kernel", "solution component", "programs are", 1e-30, 2e-2};
+  return first_use_check(w, c, B, dx, Lv, esize(w) * (size_t)nv * nv * std::min<long>(B, 256), [&](long n, void* xt, void* Mt) {
+    const hipError_t e = launch_crba<float>(w->dm, n, dq, Mt, Lq, Lm, 1, w->stream);
+    return e != hipSuccess ? e : launch_chol_solve<float>(nv, n, Mt, dtau, dc, xt, nullptr, Lm, Lv, w->d_notpd, w->stream);
+  }, same);
+}
+
 // mass_matrix! into dM (caller's layout) followed by the Cholesky solve of M x = tau - c (either may be null).  Large batches
 // build M with one lane per state; for an AOS caller that kernel writes a batch-innermost staging copy which the tile Cholesky
 // reads (coalesced) and re-emits as the caller's M.
-// ... and of the fp32 mass_matrix! + Cholesky solve on the two kernels compiled for the mechanism (crba_spec_perm + chol_spec[_nom | _packed]) — taken from 256 states
-// since round 6 —: x on the first states of the call against crba_kernel + the dense Cholesky kernel, 2e-2 of the largest |x| (two fp32 factorisations in different
-// elimination orders of a matrix of condition 1e4).  Column-per-state callers only (the compiled pair's scope).
-static int first_use_check_solve(rbd_ws* w, long B, const void* dq, const void* dtau, const void* dc, const void* dx, Layout Lq, Layout Lm, Layout Lv, bool* same) {
-  const rbd_model* m = w->model;
-  const long n = std::min<long>(B, 256);
-  const size_t es = esize(w);
-  void *Mt = nullptr, *xt = nullptr;
-  double* out = nullptr;
-  HIP_TRY(hipMalloc(&Mt, es * (size_t)m->nv * m->nv * n));
-  if (hipMalloc(&xt, es * (size_t)m->nv * n) != hipSuccess || hipMalloc((void**)&out, 2 * sizeof(double)) != hipSuccess) {
-    (void)hipGetLastError(); (void)hipFree(Mt); (void)hipFree(xt); return RBD_ERR_OUT_OF_MEMORY;
-  }
-  double h[2] = {0, 0};
-  hipError_t e = launch_crba<float>(w->dm, n, dq, Mt, Lq, Lm, 1, w->stream);
-  if (e == hipSuccess) e = launch_chol_solve<float>(m->nv, n, Mt, dtau, dc, xt, nullptr, Lm, Lv, w->d_notpd, w->stream);
-  if (e == hipSuccess) e = launch_max_diff<float>(n, m->nv, dx, xt, Lv, out, w->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(h, out, sizeof h, hipMemcpyDeviceToHost, w->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(w->stream);
-  (void)hipFree(Mt); (void)hipFree(xt); (void)hipFree(out);
-  if (e != hipSuccess) { g_last_hip_error = std::string("first_use_check_solve: ") + hipGetErrorString(e); (void)hipGetLastError(); return RBD_ERR_HIP; }
-  w->spec_check_err = h[0] / std::max(1e-30, h[1]);
-  *same = w->spec_check_err <= 2e-2 && !w->spec_first_use_inject;
-  if (!*same) {
-    char msg[320];
-    snprintf(msg, sizeof msg, "%s differs from crba_kernel + the dense Cholesky kernel on this call's first states by %.3g of the largest solution component%s: the programs are dropped, the kernels built with the library serve",
-             w->last_kernel, w->spec_check_err, w->spec_first_use_inject ? " (RBD_TUNE first_use_inject)" : "");
-    g_last_hip_error = msg;
-    fprintf(stderr, "[rbd] %s\n", msg);
-    w->spec_chol = w->spec_chol_nom = w->spec_chol_packed = nullptr;  // (the pair's second kernel in its three forms: every route that needs one falls back)
-  }
-  return RBD_OK;
-}
-
 static int run_crba_chol(rbd_ws* w, int32_t B, int layout, const void* dq, void* dM, const void* dtau, const void* dc, void* dx, Layout Lq,
                          Layout Lm, Layout Lv) {
   const rbd_model* m = w->model;
@@ -1973,7 +1941,7 @@ static int run_crba_chol(rbd_ws* w, int32_t B, int layout, const void* dq, void*
   if (state && layout == RBD_LAYOUT_AOS && chol_copies_m((int)es, m->nv)) {
     spec_load(w, SPEC_MASS);
     const bool mcopy_ok = !dM || (Lm.sk == 1 && (Lm.sb & 3) == 0 && (reinterpret_cast<uintptr_t>(dM) & 15) == 0);
-    const bool spec_route = w->spec_chol && spec_crba_fits(w) && es * (size_t)m->nv * m->nv * (((size_t)B + 15) & ~(size_t)15) < ((size_t)1 << 32) && mcopy_ok;
+    const bool spec_route = w->spec_chol.f && spec_crba_fits(w) && es * (size_t)m->nv * m->nv * (((size_t)B + 15) & ~(size_t)15) < ((size_t)1 << 32) && mcopy_ok;
     // the compiled mass-matrix kernel for THIS call's staging size, asked for once (the buffer itself keeps the high-water mark of earlier, larger batches: asking
     // again with its size could answer differently — 4 GB and more — and leave a mechanism the interpreting kernel does not take without any kernel)
     hipFunction_t const spec = spec_route ? nullptr : spec_crba(w, es * (size_t)m->nv * m->nv * (((size_t)B + 15) & ~(size_t)15));
@@ -1989,14 +1957,11 @@ static int run_crba_chol(rbd_ws* w, int32_t B, int layout, const void* dq, void*
       //  against 120 for the pair in one launch; what pays is the staggered order inside chol_spec, rbd_spec.hpp)
       HIP_TRY(launch_chol_spec(w, B, w->d_Msoa, dtau, dc, dx, Lv, dM, Lm));
       w->last_kernel = "crba_spec_perm_f32 + chol_spec_f32 (compiled for the mechanism at run time)";
-      bool& checked = w->spec_mass_checked[dM ? 0 : 1];
-      if (w->spec_first_use_check && !checked && dx && !capturing(w)) {  // (first use of the pair by this workspace: first_use_check_solve)
-        checked = true;
-        bool same = true;
-        if ((st = first_use_check_solve(w, B, dq, dtau, dc, dx, Lq, Lm, Lv, &same))) return st;
-        if (!same) goto lanes;
-      }
-      return RBD_OK;
+      bool same = true;
+      if (first_use(w, dM ? w->spec_chol : w->spec_chol_nom, dx) && (st = check_solve(w, B, dq, dtau, dc, dx, Lq, Lm, Lv, &same))) return st;
+      if (same) return RBD_OK;
+      w->spec_chol.f = w->spec_chol_nom.f = w->spec_chol_packed.f = nullptr;  // (the pair's second kernel in its three forms: every route that needs one falls back)
+      goto lanes;
     }
     if (spec) HIP_TRY(launch_crba_spec(w, spec, B, dq, w->d_Msoa, Lq, Ls, 0));
     else HIP_TRY(launch_crba_state<float>(w->sm, B, dq, w->d_Msoa, Lq, Ls, 0, w->stream));
@@ -2232,7 +2197,7 @@ int rbd_mass_matrix_solve_packed(rbd_ws_t* w, int32_t B, const void* q, const vo
   }
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B), Lm = layout_of(o.layout, (long)m->nv * m->nv, B), Lp = layout_of(o.layout, np, B);
   const bool fast = !m->big && m->nv > 0 && B >= w->mass_solve_min_batch && o.layout == RBD_LAYOUT_AOS && chol_copies_m((int)es, m->nv) &&
-                    (spec_load(w, SPEC_MASS), w->spec_chol_packed != nullptr && w->spec_crba_perm != nullptr) && spec_crba_fits(w) &&
+                    (spec_load(w, SPEC_MASS), w->spec_chol_packed.f != nullptr && w->spec_crba_perm != nullptr) && spec_crba_fits(w) &&
                     es * (size_t)m->nv * m->nv * (((size_t)B + 15) & ~(size_t)15) < ((size_t)1 << 32) &&
                     (reinterpret_cast<uintptr_t>(dP) & 15) == 0;  // (the triangle leaves in 16-byte pieces)
   {
@@ -2244,11 +2209,11 @@ int rbd_mass_matrix_solve_packed(rbd_ws_t* w, int32_t B, const void* q, const vo
       HIP_TRY(launch_crba_spec(w, w->spec_crba_perm, B, dq, w->d_Msoa, Lq, Ls, 0));
       HIP_TRY(launch_chol_spec(w, B, w->d_Msoa, dr, nullptr, dx, Lv, dP, Lp, true));
       w->last_kernel = "crba_spec_perm_f32 + chol_spec_packed_f32 (compiled for the mechanism at run time)";
-      if (w->spec_first_use_check && !w->spec_mass_checked[2] && dx && !capturing(w)) {
-        w->spec_mass_checked[2] = true;
-        bool same = true;
-        if ((st = first_use_check_solve(w, B, dq, dr, nullptr, dx, Lq, Lm, Lv, &same))) return st;
-        if (!same) fast_failed = true;
+      bool same = true;
+      if (first_use(w, w->spec_chol_packed, dx) && (st = check_solve(w, B, dq, dr, nullptr, dx, Lq, Lm, Lv, &same))) return st;
+      if (!same) {
+        w->spec_chol.f = w->spec_chol_nom.f = w->spec_chol_packed.f = nullptr;  // (as run_crba_chol's check)
+        fast_failed = true;
       }
     }
     if (!fast || fast_failed) {
@@ -2416,7 +2381,7 @@ static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_con
       if (st == RBD_ERR_UNSUPPORTED && step == 0 && stage == 0) break;
       if (st) return st;
       if (!spec_sim) {
-        sim_lane_per_state = strstr(w->last_kernel, "aba_spec_") != nullptr;  // (aba_spec_f32 / aba_spec_f64 / aba_spec_gst_f64)
+        sim_lane_per_state = w->last_aba == ABA_SPEC || w->last_aba == ABA_SPEC_STASH;
         sim_algo = sim_lane_per_state ? RBD_ALGO_ABA_COMPILED : RBD_ALGO_ABA_WALK;
       }
       spec_sim = true;
@@ -2424,7 +2389,7 @@ static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_con
     if (!spec_sim) break;
   }
   if (spec_sim) {
-    const bool sim_stash = strstr(w->last_kernel, "aba_spec_gst_") != nullptr;
+    const bool sim_stash = w->last_aba == ABA_SPEC_STASH;
     w->last_kernel = sim_lane_per_state ? (sim_stash ? "aba_spec_gst_f64 with the Munthe-Kaas stage folded in (compiled for the mechanism at run time; spare rows in the HBM stash)"
                                            : w->dtype == RBD_F64 ? "aba_spec_f64 with the Munthe-Kaas stage folded in (compiled for the mechanism at run time)"
                                                                : "aba_spec_f32 with the Munthe-Kaas stage folded in (compiled for the mechanism at run time)")

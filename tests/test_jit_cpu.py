@@ -224,7 +224,7 @@ def test_precompile_without_a_device(rbd, tmp_path, monkeypatch):
 
 def test_compilation_in_the_background(rbd, tmp_path, monkeypatch):
     """A program that is not in the cache is compiled on a background thread: rbd_jit_status — the query the hot-path calls make before they pick a kernel
-    (spec_load / spec_walk / spec_loop in csrc/rbd_capi.hip) — returns at once with 0 while hiprtc runs, and 1 once the code object is there; the object
+    (spec_module in csrc/rbd_capi.hip, for spec_load / spec_walk / spec_loop / spec_bank) — returns at once with 0 while hiprtc runs, and 1 once the code object is there; the object
     is in the cache afterwards, so a second process finds it ready.  No device needed."""
     import time
     monkeypatch.setenv("RBD_JIT_CACHE", str(tmp_path / "cache"))  # (a missing directory is created, 0700)

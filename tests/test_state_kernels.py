@@ -128,7 +128,7 @@ def test_mass_matrix_solve_f32_takes_the_compiled_kernels_from_small_batches(rbd
 @pytest.mark.parametrize("form", ["dense", "no_M", "packed"])
 def test_first_use_check_of_the_compiled_mass_matrix_solve(rbd, oracle, models, form, monkeypatch, capfd):
     """The first x a workspace gets from the fp32 pair compiled for the mechanism (crba_spec_perm + chol_spec, its M_out = NULL and packed-triangle forms) is
-    compared with crba_kernel + the dense Cholesky kernel on the call's first states (csrc/rbd_capi.hip first_use_check_solve); here every check is made to find
+    compared with crba_kernel + the dense Cholesky kernel on the call's first states (csrc/rbd_capi.hip check_solve); here every check is made to find
     a difference (RBD_TUNE first_use_inject=1): the pair is dropped, the call recomputed, x and M are right, a message says so."""
     model = models["atlas_floating"]
     nv = model.nv
@@ -387,7 +387,7 @@ def test_compiled_aba_f64_program_by_batch(rbd, oracle, models):
 @pytest.mark.parametrize("dtype,name", [("f32", "double_pendulum"), ("f64", "inner_floating")])
 def test_first_use_check_drops_a_wrong_program(rbd, oracle, models, dtype, name, monkeypatch, capfd):
     """The first result a workspace gets from a run-time compiled dynamics! program is compared with the interpreting one-body-per-lane kernel on the call's first
-    states (csrc/rbd_capi.hip first_use_check): a program that computes something else — here one that is wrong by construction, RBD_TUNE spec_variant=16: the
+    states (csrc/rbd_capi.hip check_dynamics): a program that computes something else — here one that is wrong by construction, RBD_TUNE spec_variant=16: the
     passes on made-up rows instead of q, v, tau — is dropped with a message; asked for by name the call fails, left to the library it is recomputed on the
     interpreting kernels and the caller gets the right v̇.  (Round 6 met a miscompiled variant of the fp64 program in an experiment: profiles/r06_experiments.txt §8.)"""
     model = models[name]
