@@ -188,9 +188,10 @@ typedef struct rbd_opts {
 /* ---- model / workspace lifetime ------------------------------------------ */
 /* Sizes: mechanisms of up to 64 moving bodies with at most 8 children per body run on the wavefront-shaped kernels (any nv).  Mechanisms of MORE than 64 bodies, or
  * with a body of more than 8 children (since header 600; refused before), are accepted too and run on one-thread-per-state kernels with an HBM scratch (no speed
- * claim) — every entry point: rbd_dynamics with its loop branch, rbd_inverse_dynamics[_bodies], rbd_dynamics_bias[_bodies], rbd_mass_matrix[_solve], rbd_dynamics_result,
- * the contact entry points, rbd_simulate / rbd_simulate_controlled (the PD law included) / rbd_mk_stage (since 500), and since 600 the kinematics by-products
- * rbd_kinematics, rbd_geometric_jacobian, rbd_momentum.  The reference has no size limit (src/mechanism_algorithms.jl:28-50, :80-99, :313-327). */
+ * claim) — rbd_dynamics with its loop branch, rbd_inverse_dynamics[_bodies], rbd_dynamics_bias[_bodies], rbd_mass_matrix[_solve], rbd_mass_matrix_solve_packed,
+ * rbd_dynamics_result, rbd_contact_dynamics, rbd_dynamics_contact, rbd_simulate / rbd_simulate_controlled (the PD law included) / rbd_mk_stage (since 500), since 600
+ * the kinematics by-products rbd_kinematics, rbd_geometric_jacobian, rbd_momentum, and since 700 the derivative entry points.  rbd_simulate_contact and
+ * rbd_cholesky_solve return RBD_ERR_UNSUPPORTED for such a model.  The reference has no size limit (src/mechanism_algorithms.jl:28-50, :80-99, :313-327). */
 int rbd_model_create(const rbd_flat_model_t* desc, rbd_model_t** out); /* deep-copies desc */
 int rbd_model_destroy(rbd_model_t* model);
 /* Introspection of the chain schedule under the track / walk plans: tracks per state, steps per pass, (lds_fields: 0, kept for ABI

@@ -40,6 +40,10 @@ static thread_local std::string g_last_hip_error;
     }                                                                                              \
   } while (0)
 
+// f(T()) with T the scalar type of `dtype`: one argument list for the fp64 and the fp32 instantiation of a launch
+template <class F>
+static auto by_dtype(int dtype, F&& f) { return dtype == RBD_F64 ? f(double()) : f(float()); }
+
 static int joint_nq_host(int t) {
   switch (t) {
     case RBD_JOINT_FIXED: return 0;
@@ -160,7 +164,7 @@ struct rbd_ws {
   void* d_Msoa = nullptr; size_t d_Msoa_bytes = 0; long Msoa_B = -1; int Msoa_perm = -1;  // batch-innermost staging of M for the one-lane-per-state CRBA when the caller's layout is AOS
   long bank_min_batch = 0, rnea_bank_min_batch = 0, bank_resident_states = 0;
   void* d_ib = nullptr; void* d_rb = nullptr; void* d_nslots = nullptr; void* d_dof_body = nullptr; void* d_anc = nullptr; void* d_row_mask = nullptr;
-  // staging for RBD_MEM_HOST (lazy)
+  // staging for RBD_MEM_HOST (lazy; HostIO)
   void* stage[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   size_t stage_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // internal device scratch (mass matrix / bias for the CRBA route), lazy
@@ -773,6 +777,13 @@ static int upload(void** dst, const void* src, size_t bytes) {
   return RBD_OK;
 }
 
+// a table of real numbers, in the scalar type of `dtype`
+static int upload_real(void** dst, const std::vector<double>& src, int dtype) {
+  if (dtype == RBD_F64) return upload(dst, src.data(), src.size() * sizeof(double));
+  const std::vector<float> f(src.begin(), src.end());
+  return upload(dst, f.data(), f.size() * sizeof(float));
+}
+
 // the loop joints' tables on the device (workspace copies: rbd_workspace_set_loop_gains rewrites the gains in place)
 static int upload_loop_tables(rbd_ws* w, const rbd_model* m, int dtype) {
   int st = RBD_OK;
@@ -786,18 +797,9 @@ static int upload_loop_tables(rbd_ws* w, const rbd_model* m, int dtype) {
       for (int i = 0; i < m->nb; ++i) { xi[3 * i] = m->parent_ref[i]; xi[3 * i + 1] = m->qoff_ref[i]; xi[3 * i + 2] = m->slot_of[i]; }
       st = upload(&w->d_fused_i, xi.data(), xi.size() * sizeof(int32_t));
     }
-    if (st == RBD_OK) {
-      if (dtype == RBD_F64) {
-        st = upload(&w->d_loop_r, m->loop_r.data(), m->loop_r.size() * sizeof(double));
-        if (st == RBD_OK) st = upload(&w->d_axis_ref, m->axis_ref.data(), m->axis_ref.size() * sizeof(double));
-        if (st == RBD_OK) st = upload(&w->d_axis2_ref, m->axis2_ref.data(), m->axis2_ref.size() * sizeof(double));
-      } else {
-        std::vector<float> a(m->loop_r.begin(), m->loop_r.end()), b2(m->axis_ref.begin(), m->axis_ref.end()), b3(m->axis2_ref.begin(), m->axis2_ref.end());
-        st = upload(&w->d_loop_r, a.data(), a.size() * sizeof(float));
-        if (st == RBD_OK) st = upload(&w->d_axis_ref, b2.data(), b2.size() * sizeof(float));
-        if (st == RBD_OK) st = upload(&w->d_axis2_ref, b3.data(), b3.size() * sizeof(float));
-      }
-    }
+    if (st == RBD_OK) st = upload_real(&w->d_loop_r, m->loop_r, dtype);
+    if (st == RBD_OK) st = upload_real(&w->d_axis_ref, m->axis_ref, dtype);
+    if (st == RBD_OK) st = upload_real(&w->d_axis2_ref, m->axis2_ref, dtype);
   }
   return st;
 }
@@ -806,13 +808,8 @@ static int upload_loop_tables(rbd_ws* w, const rbd_model* m, int dtype) {
 static int upload_contact_tables(rbd_ws* w, const rbd_model* m, int dtype) {
   if (m->ncp <= 0) return RBD_OK;
   int st = upload(&w->d_cp_body, m->cp_body.data(), m->cp_body.size() * sizeof(int32_t));
-  auto up = [&](void** dst, const std::vector<double>& src) {
-    if (dtype == RBD_F64) return upload(dst, src.data(), src.size() * sizeof(double));
-    std::vector<float> f(src.begin(), src.end());
-    return upload(dst, f.data(), f.size() * sizeof(float));
-  };
-  if (st == RBD_OK) st = up(&w->d_cp_r, m->cp_r);
-  if (st == RBD_OK) st = up(&w->d_hs_r, m->hs_r);
+  if (st == RBD_OK) st = upload_real(&w->d_cp_r, m->cp_r, dtype);
+  if (st == RBD_OK) st = upload_real(&w->d_hs_r, m->hs_r, dtype);
   if (st != RBD_OK) return st;
   w->ctm.nb = m->nb; w->ctm.np = m->ncp; w->ctm.nh = m->nhs;
   w->ctm.cbody = (const int32_t*)w->d_cp_body; w->ctm.cp = w->d_cp_r; w->ctm.hs = w->d_hs_r;
@@ -834,10 +831,7 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
   w->model = m; w->device = device; w->dtype = dtype; w->max_batch = max_batch; w->stream = (hipStream_t)stream;
   if (m->big) {  // the any-size fallback needs its two tables only
     int st = upload(&w->d_big_tbl, m->big_tbl.data(), m->big_tbl.size() * sizeof(int32_t));
-    if (st == RBD_OK) {
-      if (dtype == RBD_F64) st = upload(&w->d_big_rb, m->big_rb.data(), m->big_rb.size() * sizeof(double));
-      else { std::vector<float> f(m->big_rb.begin(), m->big_rb.end()); st = upload(&w->d_big_rb, f.data(), f.size() * sizeof(float)); }
-    }
+    if (st == RBD_OK) st = upload_real(&w->d_big_rb, m->big_rb, dtype);
     if (st == RBD_OK) { int zero = 0; st = upload((void**)&w->d_notpd, &zero, sizeof(int)); }
     if (st == RBD_OK) st = upload_loop_tables(w, m, dtype);
     if (st == RBD_OK) st = upload_contact_tables(w, m, dtype);
@@ -849,14 +843,7 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
     return RBD_OK;
   }
   int st = upload(&w->d_ib, m->ib.data(), m->ib.size() * sizeof(int32_t));
-  if (st == RBD_OK) {
-    if (dtype == RBD_F64) {
-      st = upload(&w->d_rb, m->rb.data(), m->rb.size() * sizeof(double));
-    } else {
-      std::vector<float> rbf(m->rb.begin(), m->rb.end());
-      st = upload(&w->d_rb, rbf.data(), rbf.size() * sizeof(float));
-    }
-  }
+  if (st == RBD_OK) st = upload_real(&w->d_rb, m->rb, dtype);
   if (st == RBD_OK) st = upload(&w->d_dof_body, m->dof_body.data(), m->dof_body.size() * sizeof(int32_t));
   if (st == RBD_OK) st = upload(&w->d_anc, m->anc.data(), m->anc.size() * sizeof(int32_t));
   if (st == RBD_OK) st = upload(&w->d_row_mask, m->row_mask.data(), m->row_mask.size() * sizeof(uint64_t));
@@ -884,8 +871,7 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
     for (int k = 0; k < 2 && st == RBD_OK; ++k) {
       st = upload(&w->d_bank_ib[k], m->bank_ib[k].data(), m->bank_ib[k].size() * sizeof(int32_t));
       if (st != RBD_OK) break;
-      if (dtype == RBD_F64) st = upload(&w->d_bank_rb[k], m->bank_rb[k].data(), m->bank_rb[k].size() * sizeof(double));
-      else { std::vector<float> f(m->bank_rb[k].begin(), m->bank_rb[k].end()); st = upload(&w->d_bank_rb[k], f.data(), f.size() * sizeof(float)); }
+      st = upload_real(&w->d_bank_rb[k], m->bank_rb[k], dtype);
       bm.ib[k] = (const int32_t*)w->d_bank_ib[k]; bm.rb[k] = w->d_bank_rb[k]; bm.nbk[k] = m->bank_nb[k];
     }
     if (st != RBD_OK) { rbd_workspace_destroy(w); return st; }
@@ -920,13 +906,8 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
   if (m->rrs.ok) {
     const Reroot& R = m->rr;
     const rbd_model::RrSlots& S = m->rrs;
-    auto up_real = [&](void** dst, const std::vector<double>& src) {
-      if (dtype == RBD_F64) return upload(dst, src.data(), src.size() * sizeof(double));
-      std::vector<float> f(src.begin(), src.end());
-      return upload(dst, f.data(), f.size() * sizeof(float));
-    };
     st = upload(&w->d_rr_chain_i, R.chain_i.data(), R.chain_i.size() * sizeof(int32_t));
-    if (st == RBD_OK) st = up_real(&w->d_rr_chain_r, R.chain_r);
+    if (st == RBD_OK) st = upload_real(&w->d_rr_chain_r, R.chain_r, dtype);
     RerootView V{};
     V.nchain = (int32_t)(R.chain_i.size() / RC_I_STRIDE); V.fq = R.fq; V.fv = R.fv;
     V.chain_i = (const int32_t*)w->d_rr_chain_i; V.chain_r = w->d_rr_chain_r;
@@ -934,7 +915,7 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
     if (st == RBD_OK && S.track.ok && S.walk.ok) {
       const TrackPlan& P = S.track;
       st = upload(&w->d_rrtrack_ri, P.ri.data(), P.ri.size() * sizeof(int32_t));
-      if (st == RBD_OK) st = up_real(&w->d_rrtrack_rr, P.rr);
+      if (st == RBD_OK) st = upload_real(&w->d_rrtrack_rr, P.rr, dtype);
       if (st == RBD_OK) st = upload(&w->d_rrwalk_wk, S.walk.wk.data(), S.walk.wk.size() * sizeof(int32_t));
       WalkModel& wm = w->wm_rr;
       wm.ns = P.ns; wm.G = P.G; wm.nA = P.nA; wm.nB = P.nB; wm.nS = S.walk.nS; wm.nq = m->nq; wm.nv = m->nv; wm.reroot = V;
@@ -953,10 +934,7 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
   if (m->track.ok) {
     const TrackPlan& P = m->track;
     st = upload(&w->d_track_ri, P.ri.data(), P.ri.size() * sizeof(int32_t));
-    if (st == RBD_OK) {
-      if (dtype == RBD_F64) st = upload(&w->d_track_rr, P.rr.data(), P.rr.size() * sizeof(double));
-      else { std::vector<float> f(P.rr.begin(), P.rr.end()); st = upload(&w->d_track_rr, f.data(), f.size() * sizeof(float)); }
-    }
+    if (st == RBD_OK) st = upload_real(&w->d_track_rr, P.rr, dtype);
     if (st != RBD_OK) { rbd_workspace_destroy(w); return st; }
     TrackModel& tm = w->tm;
     tm.ns = P.ns; tm.G = P.G; tm.nA = P.nA; tm.nB = P.nB; tm.ri = (const int32_t*)w->d_track_ri; tm.rr = w->d_track_rr;
@@ -986,8 +964,7 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
     if (w->walk_lds_bytes_pair > 160 * 1024) w->walk_lds_bytes_pair = 0;
     {
       const size_t l1 = std::max(w->walk_lds_bytes, w->walk_rr ? w->walk_rr_lds_bytes : (size_t)0), l2 = std::max(w->walk_lds_bytes_pair, w->walk_rr ? w->walk_rr_lds_bytes_pair : (size_t)0);
-      const hipError_t e = dtype == RBD_F64 ? configure_walk_kernel<double>(P.has_floating, P.general, l1, 0)
-                                            : configure_walk_kernel<float>(P.has_floating, P.general, l1, l2);
+      const hipError_t e = by_dtype(dtype, [&](auto t) { return configure_walk_kernel<decltype(t)>(P.has_floating, P.general, l1, l2); });  // (l2 = 0 in fp64)
       if (e != hipSuccess) { g_last_hip_error = std::string("configure_walk_kernel: ") + hipGetErrorString(e); rbd_workspace_destroy(w); return RBD_ERR_HIP; }
     }
     // the packed form from the batch size at which the 64-state workgroups no longer fit the chip in one round (RBD_WALK_PAIR_MIN_BATCH overrides)
@@ -1020,10 +997,7 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
     const StatePlan& P = m->state;
     st = upload(&w->d_state_ops, P.ops.data(), P.ops.size() * sizeof(int32_t));
     if (st == RBD_OK) st = upload(&w->d_state_cols, P.cols.data(), P.cols.size() * sizeof(int32_t));
-    if (st == RBD_OK) {
-      if (dtype == RBD_F64) st = upload(&w->d_state_sr, P.sr.data(), P.sr.size() * sizeof(double));
-      else { std::vector<float> f(P.sr.begin(), P.sr.end()); st = upload(&w->d_state_sr, f.data(), f.size() * sizeof(float)); }
-    }
+    if (st == RBD_OK) st = upload_real(&w->d_state_sr, P.sr, dtype);
     if (st != RBD_OK) { rbd_workspace_destroy(w); return st; }
     StateModel& sm = w->sm;
     sm.nb = m->nb; sm.nq = m->nq; sm.nv = m->nv; sm.nops = P.nops; sm.nlevels = P.nlevels;
@@ -1094,7 +1068,7 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
   w->spec_first_use_check = tune("first_use_check", 1) != 0;
   w->spec_first_use_inject = tune("first_use_inject", 0) != 0;  // (tests: every check finds a difference — the drop-and-recompute path of each route without a wrong program)
   {
-    const hipError_t e = dtype == RBD_F64 ? configure_bank_kernels<double>() : configure_bank_kernels<float>();
+    const hipError_t e = by_dtype(dtype, [](auto t) { return configure_bank_kernels<decltype(t)>(); });
     if (e != hipSuccess) { g_last_hip_error = std::string("configure_bank_kernels: ") + hipGetErrorString(e); rbd_workspace_destroy(w); return RBD_ERR_HIP; }
   }
   dm.debug_stop = 0;
@@ -1223,51 +1197,18 @@ Layout layout_of(int layout, long n, long B) {
 inline bool missing(const void* p, long n) { return p == nullptr && n > 0; }
 
 struct Opts { int layout, memory, algorithm, stabilization; };
-Opts read_opts(const rbd_opts_t* o) {
-  Opts r{RBD_LAYOUT_SOA, RBD_MEM_DEVICE, RBD_ALGO_ABA, 1};
-  if (o) { r.layout = o->layout; r.memory = o->memory; r.algorithm = o->algorithm; r.stabilization = o->stabilization; }
-  return r;
-}
 
-// a model of more than 64 bodies is taken by the entry points that declare a BigOk (the four hot-path functions and the solve); all others refuse it
-thread_local int g_big_ok = 0;
-struct BigOk { BigOk() { ++g_big_ok; } ~BigOk() { --g_big_ok; } };
-int check_common(rbd_ws* w, int32_t B, const Opts& o) {
+// What every entry point that takes a batch checks first, in this order: the workspace, the model's size, the batch, the layout and the memory kind.  *o: the
+// options (the defaults when opts is NULL).  `any_size`: the entry point runs models of more than 64 bodies (on the any-size kernels of rbd_big_kernels.hip);
+// the others refuse them
+const bool kAnySize = true, kUpTo64Bodies = false;
+int begin_call(rbd_ws* w, int32_t B, const rbd_opts_t* opts, bool any_size, Opts* o) {
+  *o = opts ? Opts{opts->layout, opts->memory, opts->algorithm, opts->stabilization} : Opts{RBD_LAYOUT_SOA, RBD_MEM_DEVICE, RBD_ALGO_ABA, 1};
   if (!w) return RBD_ERR_INVALID_ARGUMENT;
-  if (w->model->big && g_big_ok == 0) return RBD_ERR_UNSUPPORTED;
+  if (w->model->big && !any_size) return RBD_ERR_UNSUPPORTED;
   if (B < 0 || B > w->max_batch) return RBD_ERR_DIMENSION_MISMATCH;
-  if (o.layout != RBD_LAYOUT_SOA && o.layout != RBD_LAYOUT_AOS) return RBD_ERR_INVALID_ARGUMENT;
-  if (o.memory != RBD_MEM_DEVICE && o.memory != RBD_MEM_HOST) return RBD_ERR_INVALID_ARGUMENT;
-  return RBD_OK;
-}
-
-// host-memory mode: copy `src` (host) into staging slot `slot`; returns device pointer via *dev
-int stage_in(rbd_ws* w, int slot, const void* src, size_t bytes, const void** dev) {
-  if (!src) { *dev = nullptr; return RBD_OK; }
-  if (w->stage_bytes[slot] < bytes) {
-    if (w->stage[slot]) HIP_TRY(hipFree(w->stage[slot]));
-    w->stage[slot] = nullptr; w->stage_bytes[slot] = 0;
-    HIP_TRY(hipMalloc(&w->stage[slot], bytes));
-    w->stage_bytes[slot] = bytes;
-  }
-  HIP_TRY(hipMemcpyAsync(w->stage[slot], src, bytes, hipMemcpyHostToDevice, w->stream));
-  *dev = w->stage[slot];
-  return RBD_OK;
-}
-int stage_out_alloc(rbd_ws* w, int slot, void* dst, size_t bytes, void** dev) {
-  if (!dst) { *dev = nullptr; return RBD_OK; }
-  if (w->stage_bytes[slot] < bytes) {
-    if (w->stage[slot]) HIP_TRY(hipFree(w->stage[slot]));
-    w->stage[slot] = nullptr; w->stage_bytes[slot] = 0;
-    HIP_TRY(hipMalloc(&w->stage[slot], bytes));
-    w->stage_bytes[slot] = bytes;
-  }
-  *dev = w->stage[slot];
-  return RBD_OK;
-}
-int stage_out_copy(rbd_ws* w, void* dst, const void* dev, size_t bytes) {
-  if (!dst) return RBD_OK;
-  HIP_TRY(hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, w->stream));
+  if (o->layout != RBD_LAYOUT_SOA && o->layout != RBD_LAYOUT_AOS) return RBD_ERR_INVALID_ARGUMENT;
+  if (o->memory != RBD_MEM_DEVICE && o->memory != RBD_MEM_HOST) return RBD_ERR_INVALID_ARGUMENT;
   return RBD_OK;
 }
 
@@ -1285,6 +1226,45 @@ int ensure(void** p, size_t* have, size_t need) {
   *have = need;
   return RBD_OK;
 }
+
+// The buffers of one call.  RBD_MEM_HOST: each buffer the caller passes is staged in a device buffer of the workspace (w->stage, taken in the order the
+// buffers are registered) — in() and inout() copy it there at once, finish() copies every out() and inout() buffer back; asynchronously on the workspace's
+// stream (the caller synchronises, rbd_sync).  RBD_MEM_DEVICE: every pointer is the device buffer itself.  A NULL buffer stays NULL.
+class HostIO {
+ public:
+  HostIO(rbd_ws* w, int memory) : w_(w), host_(memory == RBD_MEM_HOST) {}
+  int in(const void* src, size_t bytes, const void** dev) {
+    void* d;
+    const int st = stage(const_cast<void*>(src), bytes, true, false, &d);
+    *dev = d;
+    return st;
+  }
+  int out(void* dst, size_t bytes, void** dev) { return stage(dst, bytes, false, true, dev); }
+  int inout(void* buf, size_t bytes, void** dev) { return stage(buf, bytes, true, true, dev); }
+  int finish() {
+    for (int k = 0; k < nout_; ++k) HIP_TRY(hipMemcpyAsync(out_[k].host, out_[k].dev, out_[k].bytes, hipMemcpyDeviceToHost, w_->stream));
+    return RBD_OK;
+  }
+
+ private:
+  enum { kSlots = sizeof(rbd_ws::stage) / sizeof(void*) };
+  struct Out { void* host; const void* dev; size_t bytes; };
+  int stage(void* buf, size_t bytes, bool copy_in, bool copy_out, void** dev) {
+    *dev = buf;
+    if (!host_ || !buf) return RBD_OK;
+    const int k = nslot_++;
+    if (k >= kSlots) return RBD_ERR_INVALID_ARGUMENT;  // (more buffers than slots: a call site that outgrew w->stage)
+    if (int st = ensure(&w_->stage[k], &w_->stage_bytes[k], bytes)) return st;
+    *dev = w_->stage[k];
+    if (copy_in && bytes) HIP_TRY(hipMemcpyAsync(*dev, buf, bytes, hipMemcpyHostToDevice, w_->stream));
+    if (copy_out) out_[nout_++] = Out{buf, *dev, bytes};
+    return RBD_OK;
+  }
+  rbd_ws* w_;
+  bool host_;
+  int nslot_ = 0, nout_ = 0;
+  Out out_[kSlots];
+};
 
 }  // namespace
 
@@ -1460,8 +1440,7 @@ int dynamics_loops_t(rbd_ws* w, int32_t B, const Opts& o, const void* dq, const 
   return RBD_OK;
 }
 int dynamics_loops(rbd_ws* w, int32_t B, const Opts& o, const void* dq, const void* dv, const void* dtau, const void* df, void* dvd, void* dqd, void* dlam) {
-  return w->dtype == RBD_F64 ? dynamics_loops_t<double>(w, B, o, dq, dv, dtau, df, dvd, dqd, dlam)
-                             : dynamics_loops_t<float>(w, B, o, dq, dv, dtau, df, dvd, dqd, dlam);
+  return by_dtype(w->dtype, [&](auto t) { return dynamics_loops_t<decltype(t)>(w, B, o, dq, dv, dtau, df, dvd, dqd, dlam); });
 }
 }  // namespace
 
@@ -1496,7 +1475,7 @@ static int first_use_check(rbd_ws* w, const FirstUseCheck& c, long B, const void
   }
   double h[2] = {0, 0};
   hipError_t e = reference(n, ref, tmp);
-  if (e == hipSuccess) e = w->dtype == RBD_F64 ? launch_max_diff<double>(n, w->model->nv, out, ref, Lo, diff, w->stream) : launch_max_diff<float>(n, w->model->nv, out, ref, Lo, diff, w->stream);
+  if (e == hipSuccess) e = by_dtype(w->dtype, [&](auto t) { return launch_max_diff<decltype(t)>(n, w->model->nv, out, ref, Lo, diff, w->stream); });
   if (e == hipSuccess) e = hipMemcpyAsync(h, diff, sizeof h, hipMemcpyDeviceToHost, w->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(w->stream);
   (void)hipFree(ref); (void)hipFree(tmp); (void)hipFree(diff);
@@ -1521,9 +1500,11 @@ static int check_dynamics(rbd_ws* w, long B, const void* dq, const void* dv, con
   const bool f64 = w->dtype == RBD_F64;
   const FirstUseCheck c{"first_use_check", "the interpreting kernel", inverse ? "torque" : "acceleration", "program is", 1.0, f64 ? 1e-7 : 5e-3};
   return first_use_check(w, c, B, dvd, Lv, 0, [&](long n, void* ref, void*) {
-    if (inverse) return f64 ? launch_rnea<double>(dm, n, dq, dv, dtau, df, ref, nullptr, nullptr, Lq, Lv, Lf, w->stream)
-                            : launch_rnea<float>(dm, n, dq, dv, dtau, df, ref, nullptr, nullptr, Lq, Lv, Lf, w->stream);
-    return f64 ? launch_aba<double>(dm, n, dq, dv, dtau, df, ref, nullptr, Lq, Lv, Lf, w->stream) : launch_aba<float>(dm, n, dq, dv, dtau, df, ref, nullptr, Lq, Lv, Lf, w->stream);
+    return by_dtype(w->dtype, [&](auto t) {
+      using T = decltype(t);
+      if (inverse) return launch_rnea<T>(dm, n, dq, dv, dtau, df, ref, nullptr, nullptr, Lq, Lv, Lf, w->stream);
+      return launch_aba<T>(dm, n, dq, dv, dtau, df, ref, nullptr, Lq, Lv, Lf, w->stream);
+    });
   }, same);
 }
 
@@ -1534,8 +1515,7 @@ static int run_rnea(rbd_ws* w, int32_t B, int mapping, const void* dq, const voi
   if (m->big) {
     int st = big_scratch(w, B);
     if (st) return st;
-    if (w->dtype == RBD_F64) HIP_TRY(launch_big_rnea<double>(w->big, B, dq, dv, dvd, df, dtau, dqd, w->d_big_scratch, dacc, djw, Lq, Lv, Lf, w->stream));
-    else HIP_TRY(launch_big_rnea<float>(w->big, B, dq, dv, dvd, df, dtau, dqd, w->d_big_scratch, dacc, djw, Lq, Lv, Lf, w->stream));
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_big_rnea<decltype(t)>(w->big, B, dq, dv, dvd, df, dtau, dqd, w->d_big_scratch, dacc, djw, Lq, Lv, Lf, w->stream); }));
     return RBD_OK;
   }
   if (mapping == RBD_ALGO_ABA_BANKS && m->bank_lps == 0) return RBD_ERR_UNSUPPORTED;
@@ -1601,12 +1581,13 @@ static int run_rnea(rbd_ws* w, int32_t B, int mapping, const void* dq, const voi
       return run_rnea(w, B, mapping, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, dacc, djw);
     }
     w->last_kernel = pair ? "rnea_walk_kernel (two fp32 states per lane)" : "rnea_walk_kernel";
-    if (w->dtype == RBD_F64) HIP_TRY(launch_rnea_walk<double>(w->wm, m->track.has_floating, m->track.general, 0, B, w->walk_lds_bytes, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, w->stream, dacc, djw));
-    else HIP_TRY(launch_rnea_walk<float>(w->wm, m->track.has_floating, m->track.general, pair, B, pair ? w->walk_lds_bytes_pair : w->walk_lds_bytes, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, w->stream, dacc, djw));
+    const size_t lds = pair ? w->walk_lds_bytes_pair : w->walk_lds_bytes;  // (pair = 0 in fp64)
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) {
+      return launch_rnea_walk<decltype(t)>(w->wm, m->track.has_floating, m->track.general, pair, B, lds, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, w->stream, dacc, djw);
+    }));
   } else if (w->state_aot && !dacc && !djw && mapping != RBD_ALGO_ABA_BANKS && mapping != RBD_ALGO_ABA_LANES && B >= w->state_min_batch) {  // one lane per state
     w->last_kernel = "rnea_state_kernel";
-    if (w->dtype == RBD_F64) HIP_TRY(launch_rnea_state<double>(w->sm, B, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, w->stream));
-    else HIP_TRY(launch_rnea_state<float>(w->sm, B, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, w->stream));
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_rnea_state<decltype(t)>(w->sm, B, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, w->stream); }));
   } else if (banks) {
     const int ncol = m->has3dof ? 3 : 1;
     w->last_kernel = "rnea_bank_kernel";
@@ -1622,13 +1603,12 @@ static int run_rnea(rbd_ws* w, int32_t B, int mapping, const void* dq, const voi
       if (first_use(w, w->spec_bank_rnea, dvd && dtau))
         if (int st = check_dynamics(w, B, dq, dv, dvd, df, dtau, Lq, Lv, Lf, nullptr, &same, true)) return st;
       if (!same) { w->spec_bank_rnea.f = nullptr; return run_rnea(w, B, mapping, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, dacc, djw); }
-    } else
-    if (w->dtype == RBD_F64) HIP_TRY(launch_rnea_bank<double>(w->bm, B, ncol, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, w->stream, dacc, djw));
-    else HIP_TRY(launch_rnea_bank<float>(w->bm, B, ncol, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, w->stream, dacc, djw));
+    } else {
+      HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_rnea_bank<decltype(t)>(w->bm, B, ncol, dq, dv, dvd, df, dtau, dqd, Lq, Lv, Lf, w->stream, dacc, djw); }));
+    }
   } else {
     w->last_kernel = "rnea_kernel";
-    if (w->dtype == RBD_F64) HIP_TRY(launch_rnea<double>(w->dm, B, dq, dv, dvd, df, dtau, dqd, nullptr, Lq, Lv, Lf, w->stream, dacc, djw));
-    else HIP_TRY(launch_rnea<float>(w->dm, B, dq, dv, dvd, df, dtau, dqd, nullptr, Lq, Lv, Lf, w->stream, dacc, djw));
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_rnea<decltype(t)>(w->dm, B, dq, dv, dvd, df, dtau, dqd, nullptr, Lq, Lv, Lf, w->stream, dacc, djw); }));
   }
   return RBD_OK;
 }
@@ -1745,10 +1725,11 @@ static int run_aba(rbd_ws* w, int32_t B, int algorithm, const void* dq, const vo
       if (first_use(w, k, !mk && dv && dvd))
         if (int st = check_dynamics(w, B, dq, dv, dtau, df, dvd, Lq, Lv, Lf, gravity, &same)) return st;
       if (!same) { k.f = nullptr; return run_aba(w, B, algorithm, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, gravity, fuse, mk); }
-    } else if (mk) return RBD_ERR_UNSUPPORTED;
-    else
-    if (w->dtype == RBD_F64) HIP_TRY(launch_aba_walk<double>(wm, TP.has_floating, TP.general, 0, B, lds, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, w->stream));
-    else HIP_TRY(launch_aba_walk<float>(wm, TP.has_floating, TP.general, pair, B, lds, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, w->stream));
+    } else if (mk) {
+      return RBD_ERR_UNSUPPORTED;
+    } else {  // (pair = 0 in fp64)
+      HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_aba_walk<decltype(t)>(wm, TP.has_floating, TP.general, pair, B, lds, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, w->stream); }));
+    }
   } else if (pick == RBD_ALGO_ABA_BANKS) {
     BankModel bm = w->bm;
     if (gravity) memcpy(bm.gravity, gravity, sizeof bm.gravity);
@@ -1766,14 +1747,13 @@ static int run_aba(rbd_ws* w, int32_t B, int algorithm, const void* dq, const vo
       if (first_use(w, w->spec_bank_aba, !fuse && dv && dvd))
         if (int st = check_dynamics(w, B, dq, dv, dtau, df, dvd, Lq, Lv, Lf, gravity, &same)) return st;
       if (!same) { w->spec_bank_aba.f = w->spec_bank_fused = nullptr; return run_aba(w, B, algorithm, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, gravity, fuse, mk); }
-    } else
-    if (w->dtype == RBD_F64) HIP_TRY(launch_aba_bank<double>(bm, B, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, w->stream, fuse));
-    else HIP_TRY(launch_aba_bank<float>(bm, B, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, w->stream, fuse));
+    } else {
+      HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_aba_bank<decltype(t)>(bm, B, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, w->stream, fuse); }));
+    }
   } else {
     DevModel dm = w->dm;
     if (gravity) memcpy(dm.gravity, gravity, sizeof dm.gravity);
-    if (w->dtype == RBD_F64) HIP_TRY(launch_aba<double>(dm, B, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, w->stream, fuse));
-    else HIP_TRY(launch_aba<float>(dm, B, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, w->stream, fuse));
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_aba<decltype(t)>(dm, B, dq, dv, dtau, df, dvd, dqd, Lq, Lv, Lf, w->stream, fuse); }));
   }
   return RBD_OK;
 }
@@ -1876,8 +1856,7 @@ static int run_crba(rbd_ws* w, int32_t B, int layout, const void* dq, void* dM, 
   if (w->model->big) {
     int st = big_scratch(w, B);
     if (st) return st;
-    if (w->dtype == RBD_F64) HIP_TRY(launch_big_crba<double>(w->big, B, dq, dM, w->d_big_scratch, Lq, Lm, w->stream));
-    else HIP_TRY(launch_big_crba<float>(w->big, B, dq, dM, w->d_big_scratch, Lq, Lm, w->stream));
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_big_crba<decltype(t)>(w->big, B, dq, dM, w->d_big_scratch, Lq, Lm, w->stream); }));
     return RBD_OK;
   }
   if (B >= w->mass_min_batch && layout == RBD_LAYOUT_AOS && Lm.sk == 1 && ((Lm.sb * (long)esize(w)) & 15) == 0 && (reinterpret_cast<uintptr_t>(dM) & 15) == 0 &&
@@ -1900,12 +1879,10 @@ static int run_crba(rbd_ws* w, int32_t B, int layout, const void* dq, void* dM, 
   if (B >= w->state_min_batch && layout == RBD_LAYOUT_SOA && (fsoa || w->state_aot)) {  // one lane per state: its stores are coalesced when the batch is innermost
     w->last_kernel = fsoa ? (w->dtype == RBD_F64 ? "crba_spec_f64 (compiled for the mechanism at run time)" : "crba_spec_f32 (compiled for the mechanism at run time)") : "crba_state_kernel";
     if (hipFunction_t f = fsoa) HIP_TRY(launch_crba_spec(w, f, B, dq, dM, Lq, Lm, 1));
-    else if (w->dtype == RBD_F64) HIP_TRY(launch_crba_state<double>(w->sm, B, dq, dM, Lq, Lm, 1, w->stream));
-    else HIP_TRY(launch_crba_state<float>(w->sm, B, dq, dM, Lq, Lm, 1, w->stream));
+    else HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_crba_state<decltype(t)>(w->sm, B, dq, dM, Lq, Lm, 1, w->stream); }));
   } else {
     w->last_kernel = "crba_kernel";
-    if (w->dtype == RBD_F64) HIP_TRY(launch_crba<double>(w->dm, B, dq, dM, Lq, Lm, 1, w->stream));
-    else HIP_TRY(launch_crba<float>(w->dm, B, dq, dM, Lq, Lm, 1, w->stream));
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_crba<decltype(t)>(w->dm, B, dq, dM, Lq, Lm, 1, w->stream); }));
   }
   return RBD_OK;
 }
@@ -1933,8 +1910,7 @@ static int run_crba_chol(rbd_ws* w, int32_t B, int layout, const void* dq, void*
   if (m->big) {  // any-size fallback: M into dM (never null here), then one thread per state factors a COPY (the reference's result.L, :763-764) and solves
     if ((st = run_crba(w, B, layout, dq, dM, Lq, Lm))) return st;
     if ((st = ensure(&w->d_big_L, &w->d_big_L_bytes, es * (size_t)m->nv * m->nv * B))) return st;
-    if (w->dtype == RBD_F64) HIP_TRY(launch_big_chol_solve<double>(m->nv, B, dM, w->d_big_L, dtau, dc, dx, Lm, Lv, w->d_notpd, w->stream));
-    else HIP_TRY(launch_big_chol_solve<float>(m->nv, B, dM, w->d_big_L, dtau, dc, dx, Lm, Lv, w->d_notpd, w->stream));
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_big_chol_solve<decltype(t)>(m->nv, B, dM, w->d_big_L, dtau, dc, dx, Lm, Lv, w->d_notpd, w->stream); }));
     return RBD_OK;
   }
   const bool state = B >= w->mass_solve_min_batch;  // (below state_min_batch: only with both kernels compiled for the mechanism — spec_route)
@@ -1975,8 +1951,7 @@ lanes:
     dM = w->d_M;
   }
   if ((st = run_crba(w, B, layout, dq, dM, Lq, Lm))) return st;
-  if (w->dtype == RBD_F64) HIP_TRY(launch_chol_solve<double>(m->nv, B, dM, dtau, dc, dx, nullptr, Lm, Lv, w->d_notpd, w->stream));
-  else HIP_TRY(launch_chol_solve<float>(m->nv, B, dM, dtau, dc, dx, nullptr, Lm, Lv, w->d_notpd, w->stream));
+  HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_chol_solve<decltype(t)>(m->nv, B, dM, dtau, dc, dx, nullptr, Lm, Lv, w->d_notpd, w->stream); }));
   w->last_kernel = strstr(w->last_kernel, "crba_spec") ? "crba_spec (compiled for the mechanism at run time) + chol kernel"
                    : strstr(w->last_kernel, "crba_state") ? "crba_state_kernel + chol kernel" : "crba_kernel + chol kernel";
   return RBD_OK;
@@ -2018,9 +1993,8 @@ extern "C" {
 
 int rbd_dynamics(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* tau, const void* fext, void* vdot, void* qdot,
                  void* lambda, const rbd_opts_t* opts) {
-  BigOk big_ok;
-  const Opts o = read_opts(opts);
-  int st = check_common(w, B, o);
+  Opts o;
+  int st = begin_call(w, B, opts, kAnySize, &o);
   if (st != RBD_OK) return st;
   const rbd_model* m = w->model;
   if (missing(q, m->nq) || missing(v, m->nv) || missing(vdot, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
@@ -2029,55 +2003,39 @@ int rbd_dynamics(rbd_ws_t* w, int32_t B, const void* q, const void* v, const voi
   if (m->ncp > 0 && m->nhs > 0) return RBD_ERR_UNSUPPORTED;
   if (B == 0) return RBD_OK;
   HIP_TRY(hipSetDevice(w->device));
-  const size_t es = esize(w);
-  const void *dq = q, *dv = v, *dtau = tau, *df = fext;
-  void *dvd = vdot, *dqd = qdot, *dlam = lambda;
-  if (o.memory == RBD_MEM_HOST) {
-    if ((st = stage_out_alloc(w, 7, lambda, es * (m->nc > 0 ? m->nc : 1) * B, &dlam))) return st;
-    if ((st = stage_in(w, 0, q, es * m->nq * B, &dq)) || (st = stage_in(w, 1, v, es * m->nv * B, &dv)) ||
-        (st = stage_in(w, 2, tau, es * m->nv * B, &dtau)) || (st = stage_in(w, 3, fext, es * 6 * m->nb * B, &df)) ||
-        (st = stage_out_alloc(w, 4, vdot, es * m->nv * B, &dvd)) || (st = stage_out_alloc(w, 5, qdot, es * m->nq * B, &dqd)))
-      return st;
-  }
+  const size_t row = esize(w) * B;  // (bytes of one value per state)
+  HostIO io(w, o.memory);
+  const void *dq, *dv, *dtau, *df;
+  void *dvd, *dqd, *dlam;
+  if ((st = io.in(q, row * m->nq, &dq)) || (st = io.in(v, row * m->nv, &dv)) || (st = io.in(tau, row * m->nv, &dtau)) || (st = io.in(fext, row * 6 * m->nb, &df)) ||
+      (st = io.out(vdot, row * m->nv, &dvd)) || (st = io.out(qdot, row * m->nq, &dqd)) || (st = io.out(lambda, row * m->nc, &dlam)))
+    return st;
   if ((st = run_dynamics(w, B, o, dq, dv, dtau, df, dvd, dqd, dlam))) return st;
-  if (o.memory == RBD_MEM_HOST) {
-    if ((st = stage_out_copy(w, vdot, dvd, es * m->nv * B)) || (st = stage_out_copy(w, qdot, dqd, es * m->nq * B)) ||
-        (st = stage_out_copy(w, lambda, dlam, es * m->nc * B)))
-      return st;
-  }
-  return RBD_OK;
+  return io.finish();
 }
 
 static int rnea_common(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* vdot, const void* fext, void* tau_out,
                        const rbd_opts_t* opts, void* jw_out = nullptr, void* acc_out = nullptr) {
-  BigOk big_ok;
-  const Opts o = read_opts(opts);
-  int st = check_common(w, B, o);
+  Opts o;
+  int st = begin_call(w, B, opts, kAnySize, &o);
   if (st != RBD_OK) return st;
   const rbd_model* m = w->model;
   if (missing(q, m->nq) || missing(v, m->nv) || missing(tau_out, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
   if (B == 0) return RBD_OK;
   HIP_TRY(hipSetDevice(w->device));
-  const size_t es = esize(w);
-  const void *dq = q, *dv = v, *dvd = vdot, *df = fext;
-  void *dt = tau_out, *djw = jw_out, *dacc = acc_out;
-  const size_t bbytes = es * 6 * (size_t)m->nb * B;
-  if (o.memory == RBD_MEM_HOST) {
-    if ((st = stage_in(w, 0, q, es * m->nq * B, &dq)) || (st = stage_in(w, 1, v, es * m->nv * B, &dv)) ||
-        (st = stage_in(w, 2, vdot, es * m->nv * B, &dvd)) || (st = stage_in(w, 3, fext, es * 6 * m->nb * B, &df)) ||
-        (st = stage_out_alloc(w, 4, tau_out, es * m->nv * B, &dt)) || (st = stage_out_alloc(w, 5, jw_out, bbytes, &djw)) ||
-        (st = stage_out_alloc(w, 6, acc_out, bbytes, &dacc)))
-      return st;
-  }
+  const size_t row = esize(w) * B;
+  HostIO io(w, o.memory);
+  const void *dq, *dv, *dvd, *df;
+  void *dt, *djw, *dacc;
+  if ((st = io.in(q, row * m->nq, &dq)) || (st = io.in(v, row * m->nv, &dv)) || (st = io.in(vdot, row * m->nv, &dvd)) || (st = io.in(fext, row * 6 * m->nb, &df)) ||
+      (st = io.out(tau_out, row * m->nv, &dt)) || (st = io.out(jw_out, row * 6 * m->nb, &djw)) || (st = io.out(acc_out, row * 6 * m->nb, &dacc)))
+    return st;
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B), Lf = layout_of(o.layout, 6L * m->nb, B);
   {
     Timed t(w);
     if ((st = run_rnea(w, B, o.algorithm, dq, dv, dvd, df, dt, nullptr, Lq, Lv, Lf, dacc, djw))) return st;
   }
-  if (o.memory == RBD_MEM_HOST) {
-    if ((st = stage_out_copy(w, tau_out, dt, es * m->nv * B)) || (st = stage_out_copy(w, jw_out, djw, bbytes)) || (st = stage_out_copy(w, acc_out, dacc, bbytes))) return st;
-  }
-  return RBD_OK;
+  return io.finish();
 }
 
 int rbd_inverse_dynamics(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* vdot, const void* fext, void* tau_out,
@@ -2104,34 +2062,29 @@ int rbd_dynamics_bias_bodies(rbd_ws_t* w, int32_t B, const void* q, const void* 
 }
 
 int rbd_mass_matrix(rbd_ws_t* w, int32_t B, const void* q, void* M_out, const rbd_opts_t* opts) {
-  BigOk big_ok;
-  const Opts o = read_opts(opts);
-  int st = check_common(w, B, o);
+  Opts o;
+  int st = begin_call(w, B, opts, kAnySize, &o);
   if (st != RBD_OK) return st;
   const rbd_model* m = w->model;
   if (missing(q, m->nq) || missing(M_out, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
   if (B == 0) return RBD_OK;
   HIP_TRY(hipSetDevice(w->device));
-  const size_t es = esize(w);
-  const void* dq = q;
-  void* dM = M_out;
-  const size_t mbytes = es * (size_t)m->nv * m->nv * B;
-  if (o.memory == RBD_MEM_HOST) {
-    if ((st = stage_in(w, 0, q, es * m->nq * B, &dq)) || (st = stage_out_alloc(w, 6, M_out, mbytes, &dM))) return st;
-  }
+  const size_t row = esize(w) * B;
+  HostIO io(w, o.memory);
+  const void* dq;
+  void* dM;
+  if ((st = io.in(q, row * m->nq, &dq)) || (st = io.out(M_out, row * m->nv * m->nv, &dM))) return st;
   const Layout Lq = layout_of(o.layout, m->nq, B), Lm = layout_of(o.layout, (long)m->nv * m->nv, B);
   {
     Timed t(w);
     if ((st = run_crba(w, B, o.layout, dq, dM, Lq, Lm))) return st;
   }
-  if (o.memory == RBD_MEM_HOST) return stage_out_copy(w, M_out, dM, mbytes);
-  return RBD_OK;
+  return io.finish();
 }
 
 int rbd_mass_matrix_solve(rbd_ws_t* w, int32_t B, const void* q, const void* rhs, void* x, void* M_out, const rbd_opts_t* opts) {
-  BigOk big_ok;
-  const Opts o = read_opts(opts);
-  int st = check_common(w, B, o);
+  Opts o;
+  int st = begin_call(w, B, opts, kAnySize, &o);
   if (st != RBD_OK) return st;
   const rbd_model* m = w->model;
   if (missing(q, m->nq) || missing(rhs, m->nv) || missing(x, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
@@ -2139,13 +2092,11 @@ int rbd_mass_matrix_solve(rbd_ws_t* w, int32_t B, const void* q, const void* rhs
   HIP_TRY(hipSetDevice(w->device));
   const size_t es = esize(w);
   const size_t mbytes = es * (size_t)m->nv * m->nv * B;
-  const void *dq = q, *dr = rhs;
-  void *dx = x, *dM = M_out;
-  if (o.memory == RBD_MEM_HOST) {
-    if ((st = stage_in(w, 0, q, es * m->nq * B, &dq)) || (st = stage_in(w, 2, rhs, es * m->nv * B, &dr)) ||
-        (st = stage_out_alloc(w, 4, x, es * m->nv * B, &dx)) || (st = stage_out_alloc(w, 6, M_out, mbytes, &dM)))
-      return st;
-  }
+  HostIO io(w, o.memory);
+  const void *dq, *dr;
+  void *dx, *dM;
+  if ((st = io.in(q, es * m->nq * B, &dq)) || (st = io.in(rhs, es * m->nv * B, &dr)) || (st = io.out(x, es * m->nv * B, &dx)) || (st = io.out(M_out, mbytes, &dM)))
+    return st;
   // M_out == NULL: the caller wants x only.  The lane-per-state route (large batches) then skips the emission of M altogether — its factorization
   // reads the staged triangle, and the whole-square store is 340 MB of the route's ~560 MB at 65 536 Atlas states; the other routes factor M in
   // place and need a buffer of their own
@@ -2167,19 +2118,15 @@ int rbd_mass_matrix_solve(rbd_ws_t* w, int32_t B, const void* q, const void* rhs
     if ((st = run_aba(w, B, RBD_ALGO_ABA, dq, nullptr, dr, nullptr, dx, nullptr, Lq, Lv, Lf, g0, nullptr))) return st;
     if (dM && (st = run_crba(w, B, o.layout, dq, dM, Lq, Lm))) return st;
   }
-  if (o.memory == RBD_MEM_HOST) {
-    if ((st = stage_out_copy(w, x, dx, es * m->nv * B)) || (st = stage_out_copy(w, M_out, dM, mbytes))) return st;
-  }
-  return RBD_OK;
+  return io.finish();
 }
 
 // x = M(q)^-1 rhs with M as LAPACK's packed lower triangle — the part of M the reference defines (Symmetric, uplo 'L': src/dynamics_result.jl:42), half the bytes
 // of the square, and bytes are what the emission of M costs.  Large fp32 batches of a mechanism with compiled kernels: the tile Cholesky sends the triangle
 // on its way from its own tiles (chol_spec<PACKED>, rbd_spec.hpp); everything else forms the square in the workspace and packs it.
 int rbd_mass_matrix_solve_packed(rbd_ws_t* w, int32_t B, const void* q, const void* rhs, void* x, void* M_packed_out, const rbd_opts_t* opts) {
-  BigOk big_ok;
-  const Opts o = read_opts(opts);
-  int st = check_common(w, B, o);
+  Opts o;
+  int st = begin_call(w, B, opts, kAnySize, &o);
   if (st != RBD_OK) return st;
   const rbd_model* m = w->model;
   if (missing(q, m->nq) || missing(rhs, m->nv) || missing(x, m->nv) || !M_packed_out) return RBD_ERR_INVALID_ARGUMENT;
@@ -2187,14 +2134,12 @@ int rbd_mass_matrix_solve_packed(rbd_ws_t* w, int32_t B, const void* q, const vo
   HIP_TRY(hipSetDevice(w->device));
   const size_t es = esize(w);
   const long np = (long)m->nv * (m->nv + 1) / 2;
-  const size_t pbytes = es * (size_t)np * B;
-  const void *dq = q, *dr = rhs;
-  void *dx = x, *dP = M_packed_out;
-  if (o.memory == RBD_MEM_HOST) {
-    if ((st = stage_in(w, 0, q, es * m->nq * B, &dq)) || (st = stage_in(w, 2, rhs, es * m->nv * B, &dr)) ||
-        (st = stage_out_alloc(w, 4, x, es * m->nv * B, &dx)) || (st = stage_out_alloc(w, 6, M_packed_out, pbytes, &dP)))
-      return st;
-  }
+  HostIO io(w, o.memory);
+  const void *dq, *dr;
+  void *dx, *dP;
+  if ((st = io.in(q, es * m->nq * B, &dq)) || (st = io.in(rhs, es * m->nv * B, &dr)) || (st = io.out(x, es * m->nv * B, &dx)) ||
+      (st = io.out(M_packed_out, es * (size_t)np * B, &dP)))
+    return st;
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B), Lm = layout_of(o.layout, (long)m->nv * m->nv, B), Lp = layout_of(o.layout, np, B);
   const bool fast = !m->big && m->nv > 0 && B >= w->mass_solve_min_batch && o.layout == RBD_LAYOUT_AOS && chol_copies_m((int)es, m->nv) &&
                     (spec_load(w, SPEC_MASS), w->spec_chol_packed.f != nullptr && w->spec_crba_perm != nullptr) && spec_crba_fits(w) &&
@@ -2219,21 +2164,15 @@ int rbd_mass_matrix_solve_packed(rbd_ws_t* w, int32_t B, const void* q, const vo
     if (!fast || fast_failed) {
       if ((st = ensure(&w->d_M, &w->d_M_bytes, es * (size_t)m->nv * m->nv * B))) return st;
       if ((st = run_crba_chol(w, B, o.layout, dq, w->d_M, dr, nullptr, dx, Lq, Lm, Lv))) return st;
-      if (w->dtype == RBD_F64) HIP_TRY(launch_pack_lower<double>(m->nv, B, w->d_M, dP, Lm, Lp, w->stream));
-      else HIP_TRY(launch_pack_lower<float>(m->nv, B, w->d_M, dP, Lm, Lp, w->stream));
+      HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_pack_lower<decltype(t)>(m->nv, B, w->d_M, dP, Lm, Lp, w->stream); }));
     }
   }
-  if (o.memory == RBD_MEM_HOST) {
-    if ((st = stage_out_copy(w, x, dx, es * m->nv * B)) || (st = stage_out_copy(w, M_packed_out, dP, pbytes))) return st;
-  }
-  return RBD_OK;
+  return io.finish();
 }
 
 int rbd_dynamics_result(rbd_ws_t* w, int32_t B, void* M, void* c, void* K, void* k, const rbd_opts_t* opts) {
-  BigOk big_ok;
-  const Opts o = read_opts(opts);
-  int st = check_common(w, B, o);
-  if (st != RBD_OK) return st;
+  Opts o;
+  if (int st = begin_call(w, B, opts, kAnySize, &o)) return st;
   const rbd_model* m = w->model;
   if (B != w->result_B || o.layout != w->result_layout) return RBD_ERR_DIMENSION_MISMATCH;  // must match the producing rbd_dynamics call
   HIP_TRY(hipSetDevice(w->device));
@@ -2268,17 +2207,16 @@ static int mk_ensure(rbd_ws* w, int32_t B) {
 
 // one stage of the integrator in a launch of its own: lane-per-body tables, or the any-size ones (more than 64 bodies)
 static hipError_t stage_launch(rbd_ws* w, long B, int stage, double dt, void* q, void* v, const void* vdot_prev, Layout Lq, Layout Lv, int close_prev = 0) {
-  if (w->model->big)
-    return w->dtype == RBD_F64 ? launch_big_mk_stage<double>(w->big, B, stage, dt, q, v, vdot_prev, w->mk, Lq, Lv, w->stream, close_prev)
-                               : launch_big_mk_stage<float>(w->big, B, stage, dt, q, v, vdot_prev, w->mk, Lq, Lv, w->stream, close_prev);
-  return w->dtype == RBD_F64 ? launch_mk_stage<double>(w->dm, B, stage, dt, q, v, vdot_prev, w->mk, Lq, Lv, w->stream, close_prev)
-                             : launch_mk_stage<float>(w->dm, B, stage, dt, q, v, vdot_prev, w->mk, Lq, Lv, w->stream, close_prev);
+  return by_dtype(w->dtype, [&](auto t) {
+    using T = decltype(t);
+    if (w->model->big) return launch_big_mk_stage<T>(w->big, B, stage, dt, q, v, vdot_prev, w->mk, Lq, Lv, w->stream, close_prev);
+    return launch_mk_stage<T>(w->dm, B, stage, dt, q, v, vdot_prev, w->mk, Lq, Lv, w->stream, close_prev);
+  });
 }
 
 int rbd_mk_stage(rbd_ws_t* w, int32_t B, int32_t stage, double dt, void* q, void* v, const void* vdot_prev, const rbd_opts_t* opts) {
-  BigOk big_ok;
-  const Opts o = read_opts(opts);
-  int st = check_common(w, B, o);
+  Opts o;
+  int st = begin_call(w, B, opts, kAnySize, &o);
   if (st != RBD_OK) return st;
   if (!q || !v || stage < 0 || stage > 4 || (stage > 0 && !vdot_prev) || o.memory != RBD_MEM_DEVICE) return RBD_ERR_INVALID_ARGUMENT;
   if (w->model->ncp > 0 && w->model->nhs > 0) return RBD_ERR_UNSUPPORTED;  // the additional contact state is not part of this stage form
@@ -2293,8 +2231,8 @@ int rbd_mk_stage(rbd_ws_t* w, int32_t B, int32_t stage, double dt, void* q, void
 
 // simulate with a controller descriptor (rbd_simulate: constant τ)
 static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_control_t& ctl, const void* fext, double dt, int32_t nsteps, const rbd_opts_t* opts) {
-  const Opts o = read_opts(opts);
-  int st = check_common(w, B, o);
+  Opts o;
+  int st = begin_call(w, B, opts, kAnySize, &o);
   if (st != RBD_OK) return st;
   if (!q || !v || nsteps < 0 || !(dt > 0)) return RBD_ERR_INVALID_ARGUMENT;
   if (w->model->ncp > 0 && w->model->nhs > 0) return RBD_ERR_UNSUPPORTED;  // contact points: rbd_simulate_contact (carries the additional state)
@@ -2306,15 +2244,12 @@ static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_con
   HIP_TRY(hipSetDevice(w->device));
   const rbd_model* m = w->model;
   const size_t es = esize(w);
-  void *dq = q, *dv = v;
-  const void *dtau = ctl.tau, *df = fext;
-  if (o.memory == RBD_MEM_HOST) {
-    const void *cq, *cv;
-    if ((st = stage_in(w, 0, q, es * m->nq * B, &cq)) || (st = stage_in(w, 1, v, es * m->nv * B, &cv)) ||
-        (st = stage_in(w, 2, ctl.tau, es * m->nv * B, &dtau)) || (st = stage_in(w, 3, fext, es * 6 * m->nb * B, &df)))
-      return st;
-    dq = const_cast<void*>(cq); dv = const_cast<void*>(cv);
-  }
+  HostIO io(w, o.memory);
+  void *dq, *dv;
+  const void *dtau, *df;
+  if ((st = io.inout(q, es * m->nq * B, &dq)) || (st = io.inout(v, es * m->nv * B, &dv)) || (st = io.in(ctl.tau, es * m->nv * B, &dtau)) ||
+      (st = io.in(fext, es * 6 * m->nb * B, &df)))
+    return st;
   if ((st = mk_ensure(w, B))) return st;
   Opts od = o; od.memory = RBD_MEM_DEVICE;
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B);
@@ -2368,10 +2303,7 @@ static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_con
     }
     if (ok) {
       w->last_kernel = "aba_walk_spec with the Munthe-Kaas stage folded in (compiled for the mechanism; four stages per launch)";
-      if (o.memory == RBD_MEM_HOST) {
-        if ((st = stage_out_copy(w, q, dq, es * m->nq * B)) || (st = stage_out_copy(w, v, dv, es * m->nv * B))) return st;
-      }
-      return RBD_OK;
+      return io.finish();
     }
   }
   for (int step = 0; try_spec_sim && step < nsteps; ++step) {
@@ -2394,10 +2326,7 @@ static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_con
                                            : w->dtype == RBD_F64 ? "aba_spec_f64 with the Munthe-Kaas stage folded in (compiled for the mechanism at run time)"
                                                                : "aba_spec_f32 with the Munthe-Kaas stage folded in (compiled for the mechanism at run time)")
                                         : "aba_walk_spec with the Munthe-Kaas stage folded in (compiled for the mechanism)";
-    if (o.memory == RBD_MEM_HOST) {
-      if ((st = stage_out_copy(w, q, dq, es * m->nq * B)) || (st = stage_out_copy(w, v, dv, es * m->nv * B))) return st;
-    }
-    return RBD_OK;
+    return io.finish();
   }
   const bool fused = (m->nloops == 0) && (o.algorithm == RBD_ALGO_ABA) && !walk_sim && !m->big;  // (more than 64 bodies: the stage in launches of its own around rbd_dynamics' any-size route)
   for (int step = 0; fused && step < nsteps; ++step) {
@@ -2409,10 +2338,7 @@ static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_con
       if (pd) { F.pd_kp = ctl.kp; F.pd_kd = ctl.kd; F.pd_qdes = ctl.q_des; }
       if ((st = run_aba(w, B, RBD_ALGO_ABA, dq, dv, tau_at(step, stage), df, nullptr, nullptr, Lq, Lv, Lf, nullptr, &F))) return st;
     }
-    if (step == nsteps - 1) {
-      if (w->dtype == RBD_F64) HIP_TRY(launch_mk_stage<double>(w->dm, B, 4, dt, dq, dv, nullptr, w->mk, Lq, Lv, w->stream));
-      else HIP_TRY(launch_mk_stage<float>(w->dm, B, 4, dt, dq, dv, nullptr, w->mk, Lq, Lv, w->stream));
-    }
+    if (step == nsteps - 1) HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_mk_stage<decltype(t)>(w->dm, B, 4, dt, dq, dv, nullptr, w->mk, Lq, Lv, w->stream); }));
   }
   if (!fused && pd && (st = ensure(&w->d_tauwork, &w->d_tauwork_bytes, entry))) return st;
   for (int step = 0; !fused && step < nsteps; ++step) {
@@ -2422,25 +2348,20 @@ static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_con
       HIP_TRY(stage_launch(w, B, stage, dt, dq, dv, w->d_vdwork, Lq, Lv, close_prev));
       const void* ts = tau_at(step, stage);
       if (pd) {  // the PD law on the stage state the launch above left in (q, v): one element-wise launch, no host round trip
-        if (m->big) {  // (trees of more than 64 bodies: the same law over the any-size tables, round 6)
-          if (w->dtype == RBD_F64) HIP_TRY(launch_big_pd_control<double>(w->big, B, dq, dv, ts, ctl.q_des, ctl.kp, ctl.kd, w->d_tauwork, Lq, Lv, w->stream));
-          else HIP_TRY(launch_big_pd_control<float>(w->big, B, dq, dv, ts, ctl.q_des, ctl.kp, ctl.kd, w->d_tauwork, Lq, Lv, w->stream));
-        } else
-        if (w->dtype == RBD_F64) HIP_TRY(launch_pd_control<double>(w->dm, B, dq, dv, ts, ctl.q_des, ctl.kp, ctl.kd, w->d_tauwork, Lq, Lv, w->stream));
-        else HIP_TRY(launch_pd_control<float>(w->dm, B, dq, dv, ts, ctl.q_des, ctl.kp, ctl.kd, w->d_tauwork, Lq, Lv, w->stream));
+        HIP_TRY(by_dtype(w->dtype, [&](auto t) {
+          using T = decltype(t);
+          if (m->big) return launch_big_pd_control<T>(w->big, B, dq, dv, ts, ctl.q_des, ctl.kp, ctl.kd, w->d_tauwork, Lq, Lv, w->stream);  // (trees of more than 64 bodies: the same law over the any-size tables, round 6)
+          return launch_pd_control<T>(w->dm, B, dq, dv, ts, ctl.q_des, ctl.kp, ctl.kd, w->d_tauwork, Lq, Lv, w->stream);
+        }));
         ts = w->d_tauwork;
       }
       if ((st = run_dynamics(w, B, od, dq, dv, ts, df, w->d_vdwork, nullptr, nullptr))) return st;
     }
     if (step == nsteps - 1) HIP_TRY(stage_launch(w, B, 4, dt, dq, dv, w->d_vdwork, Lq, Lv));
   }
-  if (o.memory == RBD_MEM_HOST) {
-    if ((st = stage_out_copy(w, q, dq, es * m->nq * B)) || (st = stage_out_copy(w, v, dv, es * m->nv * B))) return st;
-  }
-  return RBD_OK;
+  return io.finish();
 }
 int rbd_simulate(rbd_ws_t* w, int32_t B, void* q, void* v, const void* tau, const void* fext, double dt, int32_t nsteps, const rbd_opts_t* opts) {
-  BigOk big_ok;
   rbd_control_t ctl{};
   ctl.kind = RBD_CONTROL_CONSTANT;
   ctl.tau = tau;
@@ -2448,7 +2369,6 @@ int rbd_simulate(rbd_ws_t* w, int32_t B, void* q, void* v, const void* tau, cons
 }
 int rbd_simulate_controlled(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_control_t* control, const void* fext, double dt, int32_t nsteps,
                             const rbd_opts_t* opts) {
-  BigOk big_ok;
   if (!control) return RBD_ERR_INVALID_ARGUMENT;
   return simulate_core(w, B, q, v, *control, fext, dt, nsteps, opts);
 }
@@ -2472,27 +2392,18 @@ static int run_contact(rbd_ws* w, int32_t B, const Opts& o, const void* dq, cons
   if ((st = ensure(&w->d_body, &w->d_body_bytes, es * (size_t)m->nb * 24 * B)) || (st = ensure(&w->d_c, &w->d_c_bytes, es * (size_t)m->nv * B))) return st;
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B), Lf = layout_of(o.layout, 6L * m->nb, B);
   const Layout Ls = layout_of(o.layout, 3L * m->ncp * m->nhs, B);
-  if (m->big) {  // more than 64 bodies: the per-body kinematics from the any-size kernels
-    if ((st = big_scratch(w, B))) return st;
-    if (w->dtype == RBD_F64) {
-      HIP_TRY(launch_big_rnea<double>(w->big, B, dq, dv, nullptr, nullptr, w->d_c, nullptr, w->d_big_scratch, nullptr, nullptr, Lq, Lv, Lf, w->stream));
-      HIP_TRY(launch_big_export_body<double>(w->big, B, w->d_big_scratch, w->d_body, w->stream));
-      HIP_TRY(launch_contact<double>(w->ctm, B, w->d_body, ds, dsd, df, dcw, dtw, Ls, Lf, w->stream));
+  if (m->big && (st = big_scratch(w, B))) return st;
+  return by_dtype(w->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    if (m->big) {  // more than 64 bodies: the per-body kinematics from the any-size kernels
+      HIP_TRY(launch_big_rnea<T>(w->big, B, dq, dv, nullptr, nullptr, w->d_c, nullptr, w->d_big_scratch, nullptr, nullptr, Lq, Lv, Lf, w->stream));
+      HIP_TRY(launch_big_export_body<T>(w->big, B, w->d_big_scratch, w->d_body, w->stream));
     } else {
-      HIP_TRY(launch_big_rnea<float>(w->big, B, dq, dv, nullptr, nullptr, w->d_c, nullptr, w->d_big_scratch, nullptr, nullptr, Lq, Lv, Lf, w->stream));
-      HIP_TRY(launch_big_export_body<float>(w->big, B, w->d_big_scratch, w->d_body, w->stream));
-      HIP_TRY(launch_contact<float>(w->ctm, B, w->d_body, ds, dsd, df, dcw, dtw, Ls, Lf, w->stream));
+      HIP_TRY(launch_rnea<T>(w->dm, B, dq, dv, nullptr, nullptr, w->d_c, nullptr, w->d_body, Lq, Lv, Lf, w->stream));
     }
+    HIP_TRY(launch_contact<T>(w->ctm, B, w->d_body, ds, dsd, df, dcw, dtw, Ls, Lf, w->stream));
     return RBD_OK;
-  }
-  if (w->dtype == RBD_F64) {
-    HIP_TRY(launch_rnea<double>(w->dm, B, dq, dv, nullptr, nullptr, w->d_c, nullptr, w->d_body, Lq, Lv, Lf, w->stream));
-    HIP_TRY(launch_contact<double>(w->ctm, B, w->d_body, ds, dsd, df, dcw, dtw, Ls, Lf, w->stream));
-  } else {
-    HIP_TRY(launch_rnea<float>(w->dm, B, dq, dv, nullptr, nullptr, w->d_c, nullptr, w->d_body, Lq, Lv, Lf, w->stream));
-    HIP_TRY(launch_contact<float>(w->ctm, B, w->d_body, ds, dsd, df, dcw, dtw, Ls, Lf, w->stream));
-  }
-  return RBD_OK;
+  });
 }
 
 static int contact_scope(const rbd_ws* w, const Opts& o) {
@@ -2503,9 +2414,8 @@ static int contact_scope(const rbd_ws* w, const Opts& o) {
 }
 
 int rbd_contact_dynamics(rbd_ws_t* w, int32_t B, const void* q, const void* v, void* s, void* contactwrenches, void* sdot, const rbd_opts_t* opts) {
-  BigOk big_ok;
-  const Opts o = read_opts(opts);
-  int st = check_common(w, B, o);
+  Opts o;
+  int st = begin_call(w, B, opts, kAnySize, &o);
   if (st != RBD_OK) return st;
   if ((st = contact_scope(w, o))) return st;
   if (!q || !v || !s) return RBD_ERR_INVALID_ARGUMENT;
@@ -2516,9 +2426,8 @@ int rbd_contact_dynamics(rbd_ws_t* w, int32_t B, const void* q, const void* v, v
 
 int rbd_dynamics_contact(rbd_ws_t* w, int32_t B, const void* q, const void* v, void* s, const void* tau, const void* fext, void* vdot, void* qdot,
                          void* sdot, void* contactwrenches, void* totalwrenches, const rbd_opts_t* opts) {
-  BigOk big_ok;
-  const Opts o = read_opts(opts);
-  int st = check_common(w, B, o);
+  Opts o;
+  int st = begin_call(w, B, opts, kAnySize, &o);
   if (st != RBD_OK) return st;
   if ((st = contact_scope(w, o))) return st;
   if (!q || !v || !s || !vdot) return RBD_ERR_INVALID_ARGUMENT;
@@ -2536,8 +2445,8 @@ int rbd_dynamics_contact(rbd_ws_t* w, int32_t B, const void* q, const void* v, v
 
 int rbd_simulate_contact(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, const void* tau, const void* fext, double dt, int32_t nsteps,
                          const rbd_opts_t* opts) {
-  const Opts o = read_opts(opts);
-  int st = check_common(w, B, o);
+  Opts o;
+  int st = begin_call(w, B, opts, kUpTo64Bodies, &o);  // (its stage launches are the lane-per-body mk_stage kernel's)
   if (st != RBD_OK) return st;
   if ((st = contact_scope(w, o))) return st;
   if (!q || !v || !s || nsteps < 0 || !(dt > 0)) return RBD_ERR_INVALID_ARGUMENT;
@@ -2553,13 +2462,13 @@ int rbd_simulate_contact(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, cons
   for (int step = 0; step < nsteps; ++step) {
     // MuntheKaasIntegrator.step (src/ode_integrators.jl:233-299): (q, v) through mk_stage_kernel, s beside them with the same tableau
     for (int stage = 0; stage <= 4; ++stage) {
-      if (w->dtype == RBD_F64) {
-        HIP_TRY(launch_mk_stage<double>(w->dm, B, stage, dt, q, v, w->d_vdwork, w->mk, Lq, Lv, w->stream));
-        HIP_TRY(launch_contact_stage<double>(ns, stage, dt, s, w->d_sdot, w->d_s0, w->d_sacc, w->stream));
-      } else {
-        HIP_TRY(launch_mk_stage<float>(w->dm, B, stage, dt, q, v, w->d_vdwork, w->mk, Lq, Lv, w->stream));
-        HIP_TRY(launch_contact_stage<float>(ns, stage, dt, s, w->d_sdot, w->d_s0, w->d_sacc, w->stream));
-      }
+      if ((st = by_dtype(w->dtype, [&](auto t) -> int {
+             using T = decltype(t);
+             HIP_TRY(launch_mk_stage<T>(w->dm, B, stage, dt, q, v, w->d_vdwork, w->mk, Lq, Lv, w->stream));
+             HIP_TRY(launch_contact_stage<T>(ns, stage, dt, s, w->d_sdot, w->d_s0, w->d_sacc, w->stream));
+             return RBD_OK;
+           })))
+        return st;
       if (stage < 4) {
         if ((st = run_contact(w, B, o, q, v, s, w->d_sdot, fext, nullptr, w->d_tw))) return st;
         if ((st = run_dynamics(w, B, o, q, v, tau, w->d_tw, w->d_vdwork, nullptr, nullptr))) return st;
@@ -2570,39 +2479,34 @@ int rbd_simulate_contact(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, cons
 }
 
 int rbd_cholesky_solve(rbd_ws_t* w, int32_t B, const void* M, const void* rhs, void* x, void* L_out, const rbd_opts_t* opts) {
-  const Opts o = read_opts(opts);
-  int st = check_common(w, B, o);
-  if (st != RBD_OK) return st;
+  Opts o;
+  if (int st = begin_call(w, B, opts, kUpTo64Bodies, &o)) return st;
   if (!M || !rhs || !x || o.memory != RBD_MEM_DEVICE) return RBD_ERR_INVALID_ARGUMENT;
   if (B == 0) return RBD_OK;
   HIP_TRY(hipSetDevice(w->device));
   const rbd_model* m = w->model;
   const Layout Lv = layout_of(o.layout, m->nv, B), Lm = layout_of(o.layout, (long)m->nv * m->nv, B);
   Timed t(w);
-  if (w->dtype == RBD_F64) HIP_TRY(launch_chol_solve<double>(m->nv, B, M, rhs, nullptr, x, L_out, Lm, Lv, w->d_notpd, w->stream));
-  else HIP_TRY(launch_chol_solve<float>(m->nv, B, M, rhs, nullptr, x, L_out, Lm, Lv, w->d_notpd, w->stream));
+  HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_chol_solve<decltype(t)>(m->nv, B, M, rhs, nullptr, x, L_out, Lm, Lv, w->d_notpd, w->stream); }));
   return RBD_OK;
 }
 
 
 int rbd_kinematics(rbd_ws_t* w, int32_t B, const void* q, const void* v, void* momentum_matrix, void* com, void* energy, const rbd_opts_t* opts) {
-  BigOk big_ok;  // (round 6: trees of more than 64 bodies through big_kin_kernel)
-  const Opts o = read_opts(opts);
-  int st = check_common(w, B, o);
+  Opts o;
+  int st = begin_call(w, B, opts, kAnySize, &o);  // (round 6: trees of more than 64 bodies through big_kin_kernel)
   if (st != RBD_OK) return st;
   const rbd_model* m = w->model;
   if (missing(q, m->nq) || (energy && missing(v, m->nv))) return RBD_ERR_INVALID_ARGUMENT;
   if (B == 0) return RBD_OK;
   HIP_TRY(hipSetDevice(w->device));
-  const size_t es = esize(w);
-  const void *dq = q, *dv = v;
-  void *dA = momentum_matrix, *dcom = com, *den = energy;
-  if (o.memory == RBD_MEM_HOST) {
-    if ((st = stage_in(w, 0, q, es * m->nq * B, &dq)) || (st = stage_in(w, 1, v, es * m->nv * B, &dv)) ||
-        (st = stage_out_alloc(w, 4, momentum_matrix, es * 6 * m->nv * B, &dA)) || (st = stage_out_alloc(w, 5, com, es * 3 * B, &dcom)) ||
-        (st = stage_out_alloc(w, 6, energy, es * 2 * B, &den)))
-      return st;
-  }
+  const size_t row = esize(w) * B;
+  HostIO io(w, o.memory);
+  const void *dq, *dv;
+  void *dA, *dcom, *den;
+  if ((st = io.in(q, row * m->nq, &dq)) || (st = io.in(v, row * m->nv, &dv)) || (st = io.out(momentum_matrix, row * 6 * m->nv, &dA)) ||
+      (st = io.out(com, row * 3, &dcom)) || (st = io.out(energy, row * 2, &den)))
+    return st;
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B), La = layout_of(o.layout, 6L * m->nv, B);
   const Layout L3 = layout_of(o.layout, 3, B), L2 = layout_of(o.layout, 2, B);
   w->last_kernel = "kin_kernel";
@@ -2621,26 +2525,20 @@ int rbd_kinematics(rbd_ws_t* w, int32_t B, const void* q, const void* v, void* m
     if ((st = big_scratch(w, B))) return st;
     Timed t(w);
     w->last_kernel = "big_kin_kernel";
-    if (w->dtype == RBD_F64) HIP_TRY(launch_big_kin<double>(w->big, B, dq, dv, dA, dcom, den, nullptr, -1, -1, nullptr, w->d_big_scratch, Lq, Lv, La, L3, L2, L2, w->stream));
-    else HIP_TRY(launch_big_kin<float>(w->big, B, dq, dv, dA, dcom, den, nullptr, -1, -1, nullptr, w->d_big_scratch, Lq, Lv, La, L3, L2, L2, w->stream));
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) {
+      return launch_big_kin<decltype(t)>(w->big, B, dq, dv, dA, dcom, den, nullptr, -1, -1, nullptr, w->d_big_scratch, Lq, Lv, La, L3, L2, L2, w->stream);
+    }));
   } else {
     Timed t(w);
-    if (w->dtype == RBD_F64) HIP_TRY(launch_kin<double>(w->dm, B, dq, dv, dA, dcom, den, nullptr, 0, 0, Lq, Lv, La, L3, L2, w->stream));
-    else HIP_TRY(launch_kin<float>(w->dm, B, dq, dv, dA, dcom, den, nullptr, 0, 0, Lq, Lv, La, L3, L2, w->stream));
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_kin<decltype(t)>(w->dm, B, dq, dv, dA, dcom, den, nullptr, 0, 0, Lq, Lv, La, L3, L2, w->stream); }));
   }
-  if (o.memory == RBD_MEM_HOST) {
-    if ((st = stage_out_copy(w, momentum_matrix, dA, es * 6 * m->nv * B)) || (st = stage_out_copy(w, com, dcom, es * 3 * B)) ||
-        (st = stage_out_copy(w, energy, den, es * 2 * B)))
-      return st;
-  }
-  return RBD_OK;
+  return io.finish();
 }
 
 
 int rbd_geometric_jacobian(rbd_ws_t* w, int32_t B, const void* q, int32_t base_body, int32_t target_body, void* jac, const rbd_opts_t* opts) {
-  BigOk big_ok;
-  const Opts o = read_opts(opts);
-  int st = check_common(w, B, o);
+  Opts o;
+  int st = begin_call(w, B, opts, kAnySize, &o);
   if (st != RBD_OK) return st;
   const rbd_model* m = w->model;
   if (missing(q, m->nq) || missing(jac, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
@@ -2657,12 +2555,11 @@ int rbd_geometric_jacobian(rbd_ws_t* w, int32_t B, const void* q, int32_t base_b
   }
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B), La = layout_of(o.layout, 6L * m->nv, B);
   const Layout L3 = layout_of(o.layout, 3, B), L2 = layout_of(o.layout, 2, B);
-  const size_t es = esize(w);
-  const void* dq = q;
-  void* dJ = jac;
-  if (o.memory == RBD_MEM_HOST) {
-    if ((st = stage_in(w, 0, q, es * m->nq * B, &dq)) || (st = stage_out_alloc(w, 4, jac, es * 6 * m->nv * B, &dJ))) return st;
-  }
+  const size_t row = esize(w) * B;
+  HostIO io(w, o.memory);
+  const void* dq;
+  void* dJ;
+  if ((st = io.in(q, row * m->nq, &dq)) || (st = io.out(jac, row * 6 * m->nv, &dJ))) return st;
   w->last_kernel = "kin_kernel";
   if (!m->big && B >= w->spec_kin_min_batch) spec_load(w, SPEC_KIN, false);
   if (!m->big && B >= w->spec_kin_min_batch && w->spec_jac) {
@@ -2674,35 +2571,30 @@ int rbd_geometric_jacobian(rbd_ws_t* w, int32_t B, const void* q, int32_t base_b
     if ((st = big_scratch(w, B))) return st;
     Timed t(w);
     w->last_kernel = "big_kin_kernel";
-    if (w->dtype == RBD_F64) HIP_TRY(launch_big_kin<double>(w->big, B, dq, nullptr, nullptr, nullptr, nullptr, dJ, base_body, target_body, nullptr, w->d_big_scratch, Lq, Lv, La, L3, L2, L2, w->stream));
-    else HIP_TRY(launch_big_kin<float>(w->big, B, dq, nullptr, nullptr, nullptr, nullptr, dJ, base_body, target_body, nullptr, w->d_big_scratch, Lq, Lv, La, L3, L2, L2, w->stream));
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) {
+      return launch_big_kin<decltype(t)>(w->big, B, dq, nullptr, nullptr, nullptr, nullptr, dJ, base_body, target_body, nullptr, w->d_big_scratch, Lq, Lv, La, L3, L2, L2, w->stream);
+    }));
   } else {
     Timed t(w);
-    if (w->dtype == RBD_F64) HIP_TRY(launch_kin<double>(w->dm, B, dq, nullptr, nullptr, nullptr, nullptr, dJ, plus, minus, Lq, Lv, La, L3, L2, w->stream));
-    else HIP_TRY(launch_kin<float>(w->dm, B, dq, nullptr, nullptr, nullptr, nullptr, dJ, plus, minus, Lq, Lv, La, L3, L2, w->stream));
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_kin<decltype(t)>(w->dm, B, dq, nullptr, nullptr, nullptr, nullptr, dJ, plus, minus, Lq, Lv, La, L3, L2, w->stream); }));
   }
-  if (o.memory == RBD_MEM_HOST) return stage_out_copy(w, jac, dJ, es * 6 * m->nv * B);
-  return RBD_OK;
+  return io.finish();
 }
 
 
 int rbd_momentum(rbd_ws_t* w, int32_t B, const void* q, const void* v, void* out12, const rbd_opts_t* opts) {
-  BigOk big_ok;
-  const Opts o = read_opts(opts);
-  int st = check_common(w, B, o);
+  Opts o;
+  int st = begin_call(w, B, opts, kAnySize, &o);
   if (st != RBD_OK) return st;
   const rbd_model* m = w->model;
   if (missing(q, m->nq) || missing(v, m->nv) || !out12) return RBD_ERR_INVALID_ARGUMENT;
   if (B == 0) return RBD_OK;
   HIP_TRY(hipSetDevice(w->device));
-  const size_t es = esize(w);
-  const void *dq = q, *dv = v;
-  void* dout = out12;
-  if (o.memory == RBD_MEM_HOST) {
-    if ((st = stage_in(w, 0, q, es * m->nq * B, &dq)) || (st = stage_in(w, 1, v, es * m->nv * B, &dv)) ||
-        (st = stage_out_alloc(w, 4, out12, es * 12 * B, &dout)))
-      return st;
-  }
+  const size_t row = esize(w) * B;
+  HostIO io(w, o.memory);
+  const void *dq, *dv;
+  void* dout;
+  if ((st = io.in(q, row * m->nq, &dq)) || (st = io.in(v, row * m->nv, &dv)) || (st = io.out(out12, row * 12, &dout))) return st;
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B), L12 = layout_of(o.layout, 12, B);
   w->last_kernel = "momentum_kernel";
   if (!m->big && B >= w->spec_kin_min_batch) spec_load(w, SPEC_KIN, false);
@@ -2715,15 +2607,14 @@ int rbd_momentum(rbd_ws_t* w, int32_t B, const void* q, const void* v, void* out
     if ((st = big_scratch(w, B))) return st;
     Timed t(w);
     w->last_kernel = "big_kin_kernel";
-    if (w->dtype == RBD_F64) HIP_TRY(launch_big_kin<double>(w->big, B, dq, dv, nullptr, nullptr, nullptr, nullptr, -1, -1, dout, w->d_big_scratch, Lq, Lv, Lq, Lq, Lq, L12, w->stream));
-    else HIP_TRY(launch_big_kin<float>(w->big, B, dq, dv, nullptr, nullptr, nullptr, nullptr, -1, -1, dout, w->d_big_scratch, Lq, Lv, Lq, Lq, Lq, L12, w->stream));
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) {
+      return launch_big_kin<decltype(t)>(w->big, B, dq, dv, nullptr, nullptr, nullptr, nullptr, -1, -1, dout, w->d_big_scratch, Lq, Lv, Lq, Lq, Lq, L12, w->stream);
+    }));
   } else {
     Timed t(w);
-    if (w->dtype == RBD_F64) HIP_TRY(launch_momentum<double>(w->dm, B, dq, dv, dout, Lq, Lv, L12, w->stream));
-    else HIP_TRY(launch_momentum<float>(w->dm, B, dq, dv, dout, Lq, Lv, L12, w->stream));
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_momentum<decltype(t)>(w->dm, B, dq, dv, dout, Lq, Lv, L12, w->stream); }));
   }
-  if (o.memory == RBD_MEM_HOST) return stage_out_copy(w, out12, dout, es * 12 * B);
-  return RBD_OK;
+  return io.finish();
 }
 
 }  // extern "C"
@@ -2762,9 +2653,7 @@ int tan_ensure(rbd_ws* w, int ntan) {
         tbl[4 * i + 1] = ib[IB_JTYPE]; tbl[4 * i + 2] = ib[IB_QOFF]; tbl[4 * i + 3] = ib[IB_VOFF];
         memcpy(&rb[(size_t)i * RB_STRIDE], &m->rb[(size_t)s * RB_STRIDE], sizeof(double) * RB_STRIDE);
       }
-      if (w->dtype == RBD_F64) st = upload(&w->d_tan_rb, rb.data(), rb.size() * sizeof(double));
-      else { std::vector<float> f(rb.begin(), rb.end()); st = upload(&w->d_tan_rb, f.data(), f.size() * sizeof(float)); }
-      if (st) return st;
+      if ((st = upload_real(&w->d_tan_rb, rb, w->dtype))) return st;
       w->tan.nb = nb; w->tan.nq = m->nq; w->tan.nv = m->nv; w->tan.rb = w->d_tan_rb;
       memcpy(w->tan.gravity, m->gravity, sizeof w->tan.gravity);
       if ((st = upload(&w->d_tan_tbl, tbl.data(), tbl.size() * sizeof(int32_t)))) return st;
@@ -2792,13 +2681,12 @@ int tan_ensure(rbd_ws* w, int ntan) {
   return RBD_OK;
 }
 
-// the checks every derivative call shares
-int tan_check(rbd_ws* w, int32_t B, const Opts& o) {
-  int st = check_common(w, B, o);
-  if (st != RBD_OK) return st;
+// the checks every derivative call shares (every model size: the tangent kernels walk the tree in the reference's order, rbd_tangent_kernels.hip)
+int tan_check(rbd_ws* w, int32_t B, const rbd_opts_t* opts, Opts* o) {
+  if (int st = begin_call(w, B, opts, kAnySize, o)) return st;
   if (w->model->nloops > 0) return RBD_ERR_HAS_LOOPS;  // (inverse_dynamics!: src/mechanism_algorithms.jl:549)
   if (w->model->ncp > 0 && w->model->nhs > 0) return RBD_ERR_UNSUPPORTED;  // (as rbd_dynamics: the contact wrenches need the additional state)
-  if (o.memory != RBD_MEM_DEVICE) return RBD_ERR_UNSUPPORTED;
+  if (o->memory != RBD_MEM_DEVICE) return RBD_ERR_UNSUPPORTED;
   return RBD_OK;
 }
 
@@ -2913,9 +2801,8 @@ extern "C" {
 
 int rbd_inverse_dynamics_jvp(rbd_ws_t* w, int32_t B, int32_t ntan, const void* q, const void* v, const void* vdot, const void* fext, const void* dq,
                              const void* dv, const void* dvdot, const void* dfext, void* tau_out, void* dtau_out, const rbd_opts_t* opts) {
-  BigOk big_ok;
-  const Opts o = read_opts(opts);
-  int st = tan_check(w, B, o);
+  Opts o;
+  int st = tan_check(w, B, opts, &o);
   if (st != RBD_OK) return st;
   const rbd_model* m = w->model;
   if (ntan <= 0 || missing(q, m->nq) || missing(v, m->nv) || missing(vdot, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
@@ -2924,15 +2811,13 @@ int rbd_inverse_dynamics_jvp(rbd_ws_t* w, int32_t B, int32_t ntan, const void* q
   if ((st = tan_ensure(w, ntan))) return st;
   Timed t(w);
   w->last_kernel = "tangent_rnea_kernel";
-  return w->dtype == RBD_F64 ? tan_id_jvp<double>(w, B, ntan, o.layout, q, v, vdot, fext, dq, dv, dvdot, dfext, tau_out, dtau_out)
-                             : tan_id_jvp<float>(w, B, ntan, o.layout, q, v, vdot, fext, dq, dv, dvdot, dfext, tau_out, dtau_out);
+  return by_dtype(w->dtype, [&](auto t) { return tan_id_jvp<decltype(t)>(w, B, ntan, o.layout, q, v, vdot, fext, dq, dv, dvdot, dfext, tau_out, dtau_out); });
 }
 
 int rbd_dynamics_jvp(rbd_ws_t* w, int32_t B, int32_t ntan, const void* q, const void* v, const void* tau, const void* fext, const void* dq, const void* dv,
                      const void* dtau, const void* dfext, void* vdot_out, void* dvdot_out, const rbd_opts_t* opts) {
-  BigOk big_ok;
-  const Opts o = read_opts(opts);
-  int st = tan_check(w, B, o);
+  Opts o;
+  int st = tan_check(w, B, opts, &o);
   if (st != RBD_OK) return st;
   const rbd_model* m = w->model;
   if (ntan <= 0 || missing(q, m->nq) || missing(v, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
@@ -2941,15 +2826,13 @@ int rbd_dynamics_jvp(rbd_ws_t* w, int32_t B, int32_t ntan, const void* q, const 
   if ((st = tan_ensure(w, ntan))) return st;
   Timed t(w);
   w->last_kernel = "tangent_rnea_kernel + tangent_solve_kernel";
-  return w->dtype == RBD_F64 ? tan_dyn_jvp<double>(w, B, ntan, o.layout, q, v, tau, fext, dq, dv, dtau, dfext, vdot_out, dvdot_out)
-                             : tan_dyn_jvp<float>(w, B, ntan, o.layout, q, v, tau, fext, dq, dv, dtau, dfext, vdot_out, dvdot_out);
+  return by_dtype(w->dtype, [&](auto t) { return tan_dyn_jvp<decltype(t)>(w, B, ntan, o.layout, q, v, tau, fext, dq, dv, dtau, dfext, vdot_out, dvdot_out); });
 }
 
 int rbd_inverse_dynamics_derivatives(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* vdot, const void* fext, void* tau_out, void* dtau_dq,
                                      void* dtau_dv, void* M_out, const rbd_opts_t* opts) {
-  BigOk big_ok;
-  const Opts o = read_opts(opts);
-  int st = tan_check(w, B, o);
+  Opts o;
+  int st = tan_check(w, B, opts, &o);
   if (st != RBD_OK) return st;
   const rbd_model* m = w->model;
   if (missing(q, m->nq) || missing(v, m->nv) || missing(vdot, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
@@ -2958,15 +2841,13 @@ int rbd_inverse_dynamics_derivatives(rbd_ws_t* w, int32_t B, const void* q, cons
   if ((st = tan_ensure(w, m->nq + m->nv))) return st;
   Timed t(w);
   w->last_kernel = "tangent_rnea_kernel";
-  return w->dtype == RBD_F64 ? tan_id_derivs<double>(w, B, o.layout, q, v, vdot, fext, tau_out, dtau_dq, dtau_dv, M_out)
-                             : tan_id_derivs<float>(w, B, o.layout, q, v, vdot, fext, tau_out, dtau_dq, dtau_dv, M_out);
+  return by_dtype(w->dtype, [&](auto t) { return tan_id_derivs<decltype(t)>(w, B, o.layout, q, v, vdot, fext, tau_out, dtau_dq, dtau_dv, M_out); });
 }
 
 int rbd_dynamics_derivatives(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* tau, const void* fext, void* vdot_out, void* dvdot_dq,
                              void* dvdot_dv, void* dvdot_dtau, const rbd_opts_t* opts) {
-  BigOk big_ok;
-  const Opts o = read_opts(opts);
-  int st = tan_check(w, B, o);
+  Opts o;
+  int st = tan_check(w, B, opts, &o);
   if (st != RBD_OK) return st;
   const rbd_model* m = w->model;
   if (missing(q, m->nq) || missing(v, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
@@ -2975,8 +2856,7 @@ int rbd_dynamics_derivatives(rbd_ws_t* w, int32_t B, const void* q, const void* 
   if ((st = tan_ensure(w, m->nq + m->nv))) return st;
   Timed t(w);
   w->last_kernel = "tangent_rnea_kernel + tangent_solve_kernel";
-  return w->dtype == RBD_F64 ? tan_dyn_derivs<double>(w, B, o.layout, q, v, tau, fext, vdot_out, dvdot_dq, dvdot_dv, dvdot_dtau)
-                             : tan_dyn_derivs<float>(w, B, o.layout, q, v, tau, fext, vdot_out, dvdot_dq, dvdot_dv, dvdot_dtau);
+  return by_dtype(w->dtype, [&](auto t) { return tan_dyn_derivs<decltype(t)>(w, B, o.layout, q, v, tau, fext, vdot_out, dvdot_dq, dvdot_dv, dvdot_dtau); });
 }
 
 }  // extern "C"

@@ -428,6 +428,185 @@ def test_c_abi_host_memory_mode(rbd, oracle, models):
     assert L.rbd_workspace_destroy(ws) == 0
 
 
+def _c_abi_workspace(model, B, dtype):
+    import ctypes
+    from rigidbodydynamics_jl_amd import _capi
+    from rigidbodydynamics_jl_amd.state import _Model
+    L = _capi.lib()
+    m = _Model(model)
+    ws = ctypes.c_void_p()
+    assert L.rbd_workspace_create(m.handle, B, 0, _capi.F64 if dtype == "f64" else _capi.F32, None, ctypes.byref(ws)) == 0
+    nc = ctypes.c_int32()
+    assert L.rbd_model_dims(m.handle, None, None, None, ctypes.byref(nc)) == 0
+    return L, m, ws, nc.value
+
+
+@pytest.mark.parametrize("layout", ["aos", "soa"])
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("name", ["atlas_floating", "four_bar", "70_bodies"])
+def test_c_abi_host_memory_equals_device_memory(rbd, models, name, dtype, layout):
+    """Every entry point that takes host buffers (RBD_MEM_HOST) returns, bit for bit, what the same call returns on device buffers: the same status, the same
+    outputs, the same kernel (rbd_workspace_last_kernel).  The batch stays below the thresholds of the programs compiled for the mechanism, so a compilation
+    cannot move a route between the two calls.  Every buffer carries a guard of NaN past its B states, every output starts as NaN: what a call leaves alone
+    stays NaN in both modes (apart from M's strict upper triangle, which is not to be read)."""
+    import ctypes
+    from rigidbodydynamics_jl_amd import _capi
+    B, G = 13, 7
+    model = _big_tree(rbd)[0] if name == "70_bodies" else models[name]
+    nq, nv, nb = model.nq, model.nv, model.n_bodies
+    rng = np.random.default_rng(77)
+    if name == "four_bar":
+        q, v, tau = four_bar_inputs(rbd, B, 78)
+    else:
+        q, v, tau = rbd.rand_configuration(model, B, rng), rbd.rand_velocity(model, B, rng), rng.random((B, nv))
+    fe, vd, rhs = rng.random((B, 6 * nb)), rng.standard_normal((B, nv)), rng.standard_normal((B, nv))
+    nd = ND[dtype]
+    L, m, ws, nc = _c_abi_workspace(model, B, dtype)
+
+    def lay(a):  # B states of n values in the call's layout, then the guard
+        a = np.asarray(a, dtype=nd)
+        return np.concatenate([(a if layout == "aos" else a.T).ravel(), np.full(G, np.nan, nd)])
+
+    def out(n):
+        return np.full(n * B + G, np.nan, nd) if n > 0 else None
+
+    # name -> (call(ws, pointers, opts), buffers): the inputs, then the outputs (NaN); None stays a NULL pointer
+    X = lambda *a: a
+    calls = {
+        "dynamics": (lambda p, o: L.rbd_dynamics(ws, B, *p, o), X(lay(q), lay(v), lay(tau), lay(fe), out(nv), out(nq), out(nc))),
+        "dynamics_crba+result": (lambda p, o: L.rbd_dynamics(ws, B, *p[:7], o) or L.rbd_dynamics_result(ws, B, *p[7:], o),
+                                 X(lay(q), lay(v), lay(tau), lay(fe), out(nv), out(nq), out(nc), out(nv * nv), out(nv), out(nc * nv), out(nc))),
+        "inverse_dynamics": (lambda p, o: L.rbd_inverse_dynamics(ws, B, *p, o), X(lay(q), lay(v), lay(vd), lay(fe), out(nv))),
+        "dynamics_bias": (lambda p, o: L.rbd_dynamics_bias(ws, B, *p, o), X(lay(q), lay(v), lay(fe), out(nv))),
+        "inverse_dynamics_bodies": (lambda p, o: L.rbd_inverse_dynamics_bodies(ws, B, *p, o), X(lay(q), lay(v), lay(vd), lay(fe), out(nv), out(6 * nb), out(6 * nb))),
+        "dynamics_bias_bodies": (lambda p, o: L.rbd_dynamics_bias_bodies(ws, B, *p, o), X(lay(q), lay(v), lay(fe), out(nv), out(6 * nb), out(6 * nb))),
+        "mass_matrix": (lambda p, o: L.rbd_mass_matrix(ws, B, *p, o), X(lay(q), out(nv * nv))),
+        "mass_matrix_solve": (lambda p, o: L.rbd_mass_matrix_solve(ws, B, *p, o), X(lay(q), lay(rhs), out(nv), out(nv * nv))),
+        "mass_matrix_solve_no_M": (lambda p, o: L.rbd_mass_matrix_solve(ws, B, *p, None, o), X(lay(q), lay(rhs), out(nv))),
+        "mass_matrix_solve_packed": (lambda p, o: L.rbd_mass_matrix_solve_packed(ws, B, *p, o), X(lay(q), lay(rhs), out(nv), out(nv * (nv + 1) // 2))),
+        "simulate": (lambda p, o: L.rbd_simulate(ws, B, *p, 1e-3, 2, o), X(lay(q), lay(v), lay(tau), lay(fe))),
+        "kinematics": (lambda p, o: L.rbd_kinematics(ws, B, *p, o), X(lay(q), lay(v), out(6 * nv), out(3), out(2))),
+        "geometric_jacobian": (lambda p, o: L.rbd_geometric_jacobian(ws, B, p[0], -1, nb - 1, p[1], o), X(lay(q), out(6 * nv))),
+        "momentum": (lambda p, o: L.rbd_momentum(ws, B, *p, o), X(lay(q), lay(v), out(12))),
+    }
+    written = {"simulate": (0, 1)}  # (q and v: in and out)
+    # M: the lower triangle is the result, the strict upper one is not to be read (include/rbd_hip.h) — a host call returns whatever its staging buffer held there
+    k = np.arange(nv * nv)
+    low = np.concatenate([np.tile(k % nv >= k // nv, B) if layout == "aos" else np.repeat(k % nv >= k // nv, B), np.ones(G, bool)])
+    square = {"mass_matrix": 1, "mass_matrix_solve": 3, "dynamics_crba+result": 7}
+    lay_c = _capi.LAYOUT_AOS if layout == "aos" else _capi.LAYOUT_SOA
+    try:
+        for what, (call, bufs) in calls.items():
+            algo = _capi.ALGO_CRBA_CHOLESKY if what == "dynamics_crba+result" else _capi.ALGO_ABA
+            res = {}
+            for mem in (_capi.MEM_HOST, _capi.MEM_DEVICE):
+                opts = _capi.Opts(lay_c, mem, algo, 1)
+                if mem == _capi.MEM_HOST:
+                    held = [None if b is None else b.copy() for b in bufs]
+                    ptrs = [None if b is None else b.ctypes.data_as(ctypes.c_void_p) for b in held]
+                else:
+                    held = [None if b is None else torch.from_numpy(b.copy()).cuda() for b in bufs]
+                    ptrs = [None if b is None else ctypes.c_void_p(b.data_ptr()) for b in held]
+                st = call(ptrs, ctypes.byref(opts))
+                sync = L.rbd_sync(ws)
+                got = [None if b is None else (b if isinstance(b, np.ndarray) else b.cpu().numpy()) for b in held]
+                res[mem] = (st, sync, L.rbd_workspace_last_kernel(ws), got)
+            (st_h, sy_h, k_h, got_h), (st_d, sy_d, k_d, got_d) = res[_capi.MEM_HOST], res[_capi.MEM_DEVICE]
+            assert (st_h, sy_h, k_h) == (st_d, sy_d, k_d), what
+            assert st_h == 0 or (name == "four_bar" and what not in ("dynamics", "dynamics_crba+result", "simulate")), (what, st_h)
+            for i, (a, b) in enumerate(zip(got_h, got_d)):
+                if a is None:
+                    continue
+                if square.get(what) == i:
+                    a, b = a[low], b[low]
+                assert np.array_equal(a, b, equal_nan=True), (what, i, k_h)
+                assert np.isnan(a[-G:]).all(), (what, i)  # the guard
+                if i not in written.get(what, ()) and not np.isnan(bufs[i][:-G]).all():
+                    assert np.array_equal(a, bufs[i], equal_nan=True), (what, i)  # an input stays as it was
+            if st_h == 0:
+                outs = written.get(what) or [i for i, b in enumerate(bufs) if b is not None and np.isnan(b).all()]
+                for i in outs:
+                    assert np.isfinite(got_h[i][:-G]).any(), (what, i)  # the call wrote it
+    finally:
+        assert L.rbd_workspace_destroy(ws) == 0
+
+
+def test_c_abi_status_codes(rbd, models):
+    """What every entry point that takes a workspace, a batch and options returns for each argument that its shared checks refuse, and in which order
+    they fire (what the Julia shim sees): a NULL workspace, B = -1, B = max_batch + 1, layout 7, memory 7, host memory where only device pointers are
+    accepted, a model of more than 64 bodies, B = -1 together with one of those, and B = 0 (RBD_OK).  None of these calls writes anything: every buffer
+    is NaN before and after."""
+    import ctypes
+    from rigidbodydynamics_jl_amd import _capi
+    from test_contact import ball
+    MAXB = 4
+    L, m_tree, ws_tree, _ = _c_abi_workspace(models["atlas_floating"], MAXB, "f64")
+    _, m_big, ws_big, _ = _c_abi_workspace(_big_tree(rbd)[0], MAXB, "f64")
+    _, m_contact, ws_contact, _ = _c_abi_workspace(rbd.flatten(ball(rbd, np.random.default_rng(5))[0]), MAXB, "f64")
+    bufs = [torch.full((1 << 16,), float("nan"), dtype=torch.float64, device="cuda") for _ in range(12)]
+    P = [ctypes.c_void_p(b.data_ptr()) for b in bufs]
+    ctl = {k: _capi.Control(k, 0, *(b.data_ptr() for b in bufs[2:6])) for k in (_capi.CONTROL_CONSTANT, _capi.CONTROL_TABLE, _capi.CONTROL_PD)}
+    dt = ctypes.c_double(1e-3)
+    calls = {  # name -> (call(ws, B, opts), the model's workspace)
+        "rbd_dynamics": (lambda w, B, o: L.rbd_dynamics(w, B, *P[:7], o), ws_tree),
+        "rbd_inverse_dynamics": (lambda w, B, o: L.rbd_inverse_dynamics(w, B, *P[:5], o), ws_tree),
+        "rbd_dynamics_bias": (lambda w, B, o: L.rbd_dynamics_bias(w, B, *P[:4], o), ws_tree),
+        "rbd_inverse_dynamics_bodies": (lambda w, B, o: L.rbd_inverse_dynamics_bodies(w, B, *P[:7], o), ws_tree),
+        "rbd_dynamics_bias_bodies": (lambda w, B, o: L.rbd_dynamics_bias_bodies(w, B, *P[:6], o), ws_tree),
+        "rbd_mass_matrix": (lambda w, B, o: L.rbd_mass_matrix(w, B, *P[:2], o), ws_tree),
+        "rbd_mass_matrix_solve": (lambda w, B, o: L.rbd_mass_matrix_solve(w, B, *P[:4], o), ws_tree),
+        "rbd_mass_matrix_solve_packed": (lambda w, B, o: L.rbd_mass_matrix_solve_packed(w, B, *P[:4], o), ws_tree),
+        "rbd_dynamics_result": (lambda w, B, o: L.rbd_dynamics_result(w, B, None, None, None, None, o), ws_tree),
+        "rbd_mk_stage": (lambda w, B, o: L.rbd_mk_stage(w, B, 0, dt, *P[:3], o), ws_tree),
+        "rbd_simulate": (lambda w, B, o: L.rbd_simulate(w, B, *P[:4], dt, 1, o), ws_tree),
+        "rbd_simulate_controlled[constant]": (lambda w, B, o: L.rbd_simulate_controlled(w, B, P[0], P[1], ctypes.byref(ctl[0]), P[6], dt, 1, o), ws_tree),
+        "rbd_simulate_controlled[table]": (lambda w, B, o: L.rbd_simulate_controlled(w, B, P[0], P[1], ctypes.byref(ctl[1]), P[6], dt, 1, o), ws_tree),
+        "rbd_simulate_controlled[pd]": (lambda w, B, o: L.rbd_simulate_controlled(w, B, P[0], P[1], ctypes.byref(ctl[2]), P[6], dt, 1, o), ws_tree),
+        "rbd_contact_dynamics": (lambda w, B, o: L.rbd_contact_dynamics(w, B, *P[:5], o), ws_contact),
+        "rbd_dynamics_contact": (lambda w, B, o: L.rbd_dynamics_contact(w, B, *P[:10], o), ws_contact),
+        "rbd_simulate_contact": (lambda w, B, o: L.rbd_simulate_contact(w, B, *P[:5], dt, 1, o), ws_contact),
+        "rbd_cholesky_solve": (lambda w, B, o: L.rbd_cholesky_solve(w, B, *P[:4], o), ws_tree),
+        "rbd_kinematics": (lambda w, B, o: L.rbd_kinematics(w, B, *P[:5], o), ws_tree),
+        "rbd_geometric_jacobian": (lambda w, B, o: L.rbd_geometric_jacobian(w, B, P[0], -1, 0, P[1], o), ws_tree),
+        "rbd_momentum": (lambda w, B, o: L.rbd_momentum(w, B, *P[:3], o), ws_tree),
+        "rbd_inverse_dynamics_jvp": (lambda w, B, o: L.rbd_inverse_dynamics_jvp(w, B, 1, *P[:10], o), ws_tree),
+        "rbd_dynamics_jvp": (lambda w, B, o: L.rbd_dynamics_jvp(w, B, 1, *P[:10], o), ws_tree),
+        "rbd_inverse_dynamics_derivatives": (lambda w, B, o: L.rbd_inverse_dynamics_derivatives(w, B, *P[:8], o), ws_tree),
+        "rbd_dynamics_derivatives": (lambda w, B, o: L.rbd_dynamics_derivatives(w, B, *P[:8], o), ws_tree),
+    }
+    SOA, AOS, DEV, HOST = _capi.LAYOUT_SOA, _capi.LAYOUT_AOS, _capi.MEM_DEVICE, _capi.MEM_HOST
+    cases = {  # column -> (which workspace, B, layout, memory)
+        "null": (None, MAXB, SOA, DEV), "b_neg": ("own", -1, SOA, DEV), "b_over": ("own", MAXB + 1, SOA, DEV), "layout7": ("own", MAXB, 7, DEV),
+        "memory7": ("own", MAXB, SOA, 7), "host": ("own", MAXB, AOS, HOST), "big": ("big", 0, SOA, DEV), "big_b_neg": ("big", -1, SOA, DEV),
+        "b_neg_layout7": ("own", -1, 7, DEV), "zero": ("own", 0, SOA, DEV),
+    }
+    OK, ARG, DIM, UNS = 0, 1, 2, 3
+    common = dict(null=ARG, b_neg=DIM, b_over=DIM, layout7=ARG, memory7=ARG, big=OK, big_b_neg=DIM, b_neg_layout7=DIM, zero=OK)
+    expected = {k: dict(common) for k in calls}  # ("host" only where the entry point takes device pointers alone)
+    expected["rbd_mk_stage"]["host"] = ARG
+    expected["rbd_simulate_controlled[table]"]["host"] = expected["rbd_simulate_controlled[pd]"]["host"] = UNS
+    for k in ("rbd_contact_dynamics", "rbd_dynamics_contact"):
+        expected[k].update(host=UNS, big=ARG)  # (the tree of more than 64 bodies is admitted, and has no contact points)
+    expected["rbd_simulate_contact"].update(host=UNS, big=UNS, big_b_neg=UNS)
+    expected["rbd_cholesky_solve"].update(host=ARG, big=UNS, big_b_neg=UNS)
+    for k in ("rbd_inverse_dynamics_jvp", "rbd_dynamics_jvp", "rbd_inverse_dynamics_derivatives", "rbd_dynamics_derivatives"):
+        expected[k]["host"] = UNS
+    got = {}
+    try:
+        for k, (call, own) in calls.items():
+            for col, (which, B, layout, memory) in cases.items():
+                if col not in expected[k]:
+                    continue
+                opts = _capi.Opts(layout, memory, _capi.ALGO_ABA, 1)
+                got.setdefault(k, {})[col] = call({"own": own, "big": ws_big, None: None}[which], B, ctypes.byref(opts))
+        torch.cuda.synchronize()
+        assert got == expected
+        assert all(torch.isnan(b).all() for b in bufs)
+    finally:
+        for w in (ws_tree, ws_big, ws_contact):
+            assert L.rbd_workspace_destroy(w) == 0
+
+
 # ---- batched `simulate` (Munthe-Kaas RK4 on the device) vs the numpy restatement of src/ode_integrators.jl:233-299 -----------
 def quat_blocks(model):
     from rigidbodydynamics_jl_amd.mechanism import JOINT_QUAT_FLOATING, JOINT_QUAT_SPHERICAL
