@@ -418,6 +418,26 @@ int rbd_inverse_dynamics_derivatives(rbd_ws_t* ws, int32_t B, const void* q, con
                                      void* tau_out, void* dtau_dq, void* dtau_dv, void* M_out, const rbd_opts_t* opts);
 int rbd_dynamics_derivatives(rbd_ws_t* ws, int32_t B, const void* q, const void* v, const void* tau, const void* fext,
                              void* vdot_out, void* dvdot_dq, void* dvdot_dv, void* dvdot_dtau, const rbd_opts_t* opts);
+/* Derivatives of simulate steps (700 additions): nsteps steps of rbd_simulate (the Munthe-Kaas RK4 step, src/ode_integrators.jl:233-299) with tangents
+ * carried through every stage — for iLQR / DDP, shooting and differentiable simulation.  Semantics as above: raw coordinates q, tree mechanisms only
+ * (RBD_ERR_HAS_LOOPS, RBD_ERR_UNSUPPORTED for contact points with an environment and for RBD_MEM_HOST), device pointers.
+ *  - The value path is the reference's own route at every stage state: CRBA, Cholesky with the factor in the workspace, the solve (as rbd_dynamics_jvp).
+ *    The updated q, v therefore equal rbd_simulate's to rounding, not bit for bit.
+ *  - The derivatives are those of the smooth step map: the integrator's small-angle branches (θ < eps in the rotation-vector and exp / log maps of
+ *    quaternion joints) are removable singularities, and their derivatives are taken in the limit, finite at θ = 0.
+ *  - ntan <= 0, dt <= 0, nsteps < 0, or a NULL q, v, dq or dv: RBD_ERR_INVALID_ARGUMENT; B == 0 or nsteps == 0: a successful no-op.
+ *  - Allocation: the first call of a workspace, and one with a wider pass of directions than any before; no other call allocates or synchronises.  The
+ *    tangent buffers of one pass hold at most 2 GiB (2·nq + 6·nv values per direction and state, for max_batch states): more directions run as
+ *    several passes, each starting again from the caller's (q, v).
+ *  - rbd_workspace_last_kernel names the tangent kernels afterwards.
+ * q, v, dq, dv are IN/OUT.  dtau and dfext are held over every stage of every step (zero-order hold, as rbd_simulate holds tau / fext); every one of
+ * tau, fext, dtau, dfext is nullable.  dq: nq·ntan, dv / dtau: nv·ntan, dfext: 6·n_bodies·ntan per state, in the layout of the tangents above. */
+int rbd_simulate_jvp(rbd_ws_t* ws, int32_t B, int32_t ntan, void* q, void* v, const void* tau, const void* fext, double dt, int32_t nsteps,
+                     void* dq, void* dv, const void* dtau, const void* dfext, const rbd_opts_t* opts);
+/* One step: q, v advanced in place.  x = (q; v), nx = nq + nv.  dx_dx: nx×nx, dx_dtau: nx×nv, column-major per state like rbd_geometric_jacobian;
+ * column j is the JVP along the j-th unit vector.  Both are nullable; fext is held fixed. */
+int rbd_simulate_step_derivatives(rbd_ws_t* ws, int32_t B, void* q, void* v, const void* tau, const void* fext, double dt,
+                                  void* dx_dx, void* dx_dtau, const rbd_opts_t* opts);
 
 /* ---- diagnostics ------------------------------------------------------------ */
 const char* rbd_status_string(int status);
@@ -432,7 +452,8 @@ const char* rbd_workspace_last_kernel(const rbd_ws_t* ws);
 /* 100·round + revision of this header.  rbd_flat_model_t grew its four contact fields at 200; a caller built against an older header must
  * not call a newer library (the Python and Julia loaders compare this with the value they were written for).  400: rbd_workspace_set_loop_gains.
  * 500: rbd_mass_matrix_solve_packed, rbd_gatherv.  600: rbd_jit_check_walk_object; no size limit left on any entry point; program family 11; family 1 in fp64.
- * 700: forward-mode derivatives — rbd_inverse_dynamics_jvp, rbd_dynamics_jvp, rbd_inverse_dynamics_derivatives, rbd_dynamics_derivatives. */
+ * 700: forward-mode derivatives — rbd_inverse_dynamics_jvp, rbd_dynamics_jvp, rbd_inverse_dynamics_derivatives, rbd_dynamics_derivatives;
+ *      added to 700 without a new version: rbd_simulate_jvp, rbd_simulate_step_derivatives (derivatives of simulate steps). */
 #define RBD_HIP_H_VERSION 700
 int rbd_version(void);
 /* Run-time specialisation.  The one-lane-per-state kernels (mass_matrix! and mass_matrix! + Cholesky at large batches) exist in a second form

@@ -29,7 +29,7 @@ import RigidBodyDynamics: dynamics!, inverse_dynamics!, mass_matrix!, dynamics_b
 using LinearAlgebra
 
 export BatchedMechanismState, BatchedDynamicsResult, DeviceMatrix, RbdComm, gather!, gatherv!, mass_matrix_solve_packed!, synchronize, librbd_hip, TorqueTable, PDControl,
-    inverse_dynamics_jvp!, dynamics_jvp!, inverse_dynamics_derivatives!, dynamics_derivatives!
+    inverse_dynamics_jvp!, dynamics_jvp!, inverse_dynamics_derivatives!, dynamics_derivatives!, simulate_jvp!, simulate_step_derivatives!
 
 const librbd_hip = Ref("librbd_hip.so")   # set to <repo>/rigidbodydynamics.jl_amd/csrc/librbd_hip.so
 const libhip = Ref("libamdhip64.so")
@@ -489,6 +489,46 @@ function dynamics_derivatives!(dv̇dq, dv̇dv, dv̇dτ, state::BatchedMechanismS
         nullable(dv̇dτ), opts(state)), "rbd_dynamics_derivatives")
     finish(state)
     dv̇dq, dv̇dv, dv̇dτ
+end
+
+"""`simulate_jvp!(dq, dv, state, ntan, Δt; nsteps = 1, torques, dτ, externalwrenches, dexternalwrenches)` — `nsteps` Munthe-Kaas RK4 steps of `simulate`
+with `ntan` directions per state carried along: `state.q`, `state.v`, `dq` ((nq·ntan) × B) and `dv` ((nv·ntan) × B) advanced in place; `dτ` and the wrench
+directions held over every stage, as the torques are (`rbd_simulate_jvp`)."""
+function simulate_jvp!(dq::Buffer{T}, dv::Buffer{T}, state::BatchedMechanismState{T}, ntan::Integer, Δt::Real; nsteps::Integer = 1, torques = nothing,
+        dτ = nothing, externalwrenches = nothing, dexternalwrenches = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, B = state.model.nq, state.model.nv, batchsize(state)
+    ntan > 0 || throw(ArgumentError("ntan must be positive"))
+    Δt > 0 || throw(ArgumentError("Δt must be positive"))
+    nsteps >= 0 || throw(ArgumentError("nsteps must be non-negative"))
+    for (x, n) in ((dq, nq), (dv, nv), (dτ, nv))
+        x === nothing || size(x) == (n * ntan, B) || throw(DimensionMismatch("tangent buffer has wrong size"))
+    end
+    check(ccall((:rbd_simulate_jvp, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Cdouble, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, ntan, state.q, state.v, nullable(torques), nullable(densewrenches(state, externalwrenches)), Float64(Δt), nsteps, dq, dv,
+        nullable(dτ), nullable(dexternalwrenches), opts(state)), "rbd_simulate_jvp")
+    finish(state)
+    dq, dv
+end
+
+"""`simulate_step_derivatives!(∂x∂x, ∂x∂τ, state, Δt; torques, externalwrenches)` — one step of `simulate` (`state` advanced in place) and its Jacobians
+with x = (q; v), nx = nq + nv: (nx·nx) × B and (nx·nv) × B, column-major per state, either one `nothing`; the wrenches held fixed
+(`rbd_simulate_step_derivatives`)."""
+function simulate_step_derivatives!(dxdx, dxdτ, state::BatchedMechanismState{T}, Δt::Real; torques = nothing, externalwrenches = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, B = state.model.nq, state.model.nv, batchsize(state)
+    nx = nq + nv
+    Δt > 0 || throw(ArgumentError("Δt must be positive"))
+    for (x, n) in ((dxdx, nx * nx), (dxdτ, nx * nv))
+        x === nothing || size(x) == (n, B) || throw(DimensionMismatch("Jacobian buffer has wrong size"))
+    end
+    check(ccall((:rbd_simulate_step_derivatives, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Cdouble, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, state.q, state.v, nullable(torques), nullable(densewrenches(state, externalwrenches)), Float64(Δt), nullable(dxdx), nullable(dxdτ),
+        opts(state)), "rbd_simulate_step_derivatives")
+    finish(state)
+    dxdx, dxdτ
 end
 
 """`mass_matrix_solve_packed!(x, Mpacked, state, rhs)` — `mass_matrix!` + the potrf!/potrs! of `dynamics_solve!` (:764, :819) with M as LAPACK's packed lower

@@ -25,6 +25,7 @@
 #include "rbd_jit.hpp"
 #include "rbd_mk_fuse.hpp"
 #include "rbd_tangent.hpp"
+#include "rbd_tangent_mk.hpp"
 enum { BANK_LDS_PAIRS_HOST = 30 };  // = BANK_LDS_PAIRS of rbd_bank.hpp (16 parked + 14 exchange pairs per lane; checked in rbd_bank_kernels.hip)
 
 using namespace rbd;
@@ -190,6 +191,8 @@ struct rbd_ws {
   bool tan_ready = false; BigModel tan{}; void* d_tan_tbl = nullptr; void* d_tan_rb = nullptr; void* d_tan_scratch = nullptr; size_t d_tan_scratch_bytes = 0; long tan_threads = 0; int tan_ntan = 0;
   void* d_tan_M = nullptr; void* d_tan_L = nullptr; void* d_tan_c = nullptr; void* d_tan_vd = nullptr; void* d_tan_rhs = nullptr; void* d_tan_x = nullptr;
   size_t d_tan_M_bytes = 0, d_tan_L_bytes = 0, d_tan_c_bytes = 0, d_tan_vd_bytes = 0, d_tan_rhs_bytes = 0, d_tan_x_bytes = 0;
+  // the simulate derivatives (rbd_simulate_jvp, rbd_simulate_step_derivatives): the stage states' values, and the tangents of one pass of sim_tan_w directions
+  void* d_sim_val = nullptr; void* d_sim_tan = nullptr; size_t d_sim_val_bytes = 0, d_sim_tan_bytes = 0; int sim_tan_w = 0;
 };
 
 // RBD_TUNE="key=value,key=value,...": the developer knobs of the tests and sweep scripts in ONE environment variable (batch thresholds between the lane
@@ -1081,7 +1084,8 @@ int rbd_workspace_destroy(rbd_ws_t* w) {
   if (!w) return RBD_OK;
   (void)hipSetDevice(w->device);
   void* ptrs[] = {w->d_big_L, w->d_big_tbl, w->d_big_rb, w->d_big_scratch, w->d_fused_i, w->d_tauwork, w->d_rr_chain_i, w->d_rr_chain_r, w->d_rrtrack_ri, w->d_rrtrack_rr, w->d_rrwalk_wk, w->d_cp_body, w->d_cp_r, w->d_hs_r, w->d_tw, w->d_cw, w->d_s0, w->d_sacc, w->d_sdot, w->d_rows, w->d_walk_wk, w->d_state_ops, w->d_state_cols, w->d_state_sr, w->d_Msoa, w->d_track_ri, w->d_track_rr, w->d_bank_ib[0], w->d_bank_ib[1], w->d_bank_rb[0], w->d_bank_rb[1], w->d_ib, w->d_rb, w->d_nslots, w->d_dof_body, w->d_anc, w->d_row_mask, w->d_M, w->d_c, w->d_K, w->d_k, (void*)w->d_notpd, w->d_body, w->d_scratch, w->d_loop_i, w->d_loop_r, w->d_loop_path, w->d_jt_ref, w->d_voff_ref, w->d_axis_ref, w->d_axis2_ref,
-                  w->d_tan_tbl, w->d_tan_rb, w->d_tan_scratch, w->d_tan_M, w->d_tan_L, w->d_tan_c, w->d_tan_vd, w->d_tan_rhs, w->d_tan_x};
+                  w->d_tan_tbl, w->d_tan_rb, w->d_tan_scratch, w->d_tan_M, w->d_tan_L, w->d_tan_c, w->d_tan_vd, w->d_tan_rhs, w->d_tan_x,
+                  w->d_sim_val, w->d_sim_tan};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (void* p : w->stage) if (p) (void)hipFree(p);
   {
@@ -2627,6 +2631,10 @@ template <typename T> hipError_t launch_tangent_rnea(const BigModel& M, const Ta
 template <typename T>
 hipError_t launch_tangent_solve(int nv, long B, int c0, int ncol, const void* L, Layout Ll, const void* rhs, int identity, const ColOut<T>& out, void* xmem, hipStream_t s);
 template <typename T> hipError_t launch_symmetrize(int nv, long B, void* M, Layout Lm, hipStream_t s);
+template <typename T> hipError_t launch_tangent_mk_stage(const MkTanArgs<T>& A, hipStream_t s);
+template <typename T>
+hipError_t launch_tangent_mk_load(long B, int ncol, int nq, int nv, int col0, int unit, const ColOut<T>& sq, const ColOut<T>& sv, const ColOut<T>& sd,
+                                  const ColOut<T>& dq, const ColOut<T>& dv, const ColOut<T>& dd, hipStream_t s);
 }  // namespace rbd
 
 namespace {
@@ -2795,6 +2803,110 @@ int tan_dyn_derivs(rbd_ws* w, int32_t B, int layout, const void* q, const void* 
   }
   return RBD_OK;
 }
+
+// ---- derivatives of simulate steps (header 700 additions) -----------------------------------------------------------------------------------------------
+enum : long { SIM_TAN_CAP = 1L << 31 };  // bytes of the simulate tangent buffers at most: more directions run as several passes
+
+// tangents per (direction, state) of one pass: initial dq, dv, dτ; the stage state's dq, dv; the running sums' two; dv̇
+size_t sim_tan_per_dir(const rbd_model* m) { return 2 * (size_t)m->nq + 6 * (size_t)m->nv; }
+int sim_pass_width(rbd_ws* w, int ndir) {
+  const long per = (long)(esize(w) * sim_tan_per_dir(w->model) * (size_t)w->max_batch);
+  const int N = tangent_chunk((int)esize(w));
+  const long cap = std::max<long>(N, SIM_TAN_CAP / std::max<long>(1, per) / N * N);
+  return (int)std::min<long>(ndir, cap);
+}
+// the first call of a workspace allocates, and one whose pass is wider than any before; nothing else allocates
+int sim_ensure(rbd_ws* w, int width) {
+  const rbd_model* m = w->model;
+  const size_t es = esize(w), B = (size_t)w->max_batch;
+  int st;
+  if ((st = tan_ensure(w, width))) return st;
+  if ((st = ensure(&w->d_sim_val, &w->d_sim_val_bytes, es * B * (4 * (size_t)m->nq + 6 * (size_t)m->nv)))) return st;
+  if (width > w->sim_tan_w) {
+    if ((st = ensure(&w->d_sim_tan, &w->d_sim_tan_bytes, es * B * sim_tan_per_dir(m) * (size_t)width))) return st;
+    w->sim_tan_w = width;
+  }
+  return RBD_OK;
+}
+
+// nsteps steps of the RK4 integrator with ndir directions carried along, in passes of at most sim_tan_w directions.  JVP (jac == false): the caller's
+// dq, dv (in/out), dτ, dfext, ndir directions in the call's layout.  Jacobians (jac): the columns g0 … g0 + ndir − 1 of [∂x⁺/∂x  ∂x⁺/∂τ], unit directions
+// made on the device, written to dxdx (columns < nx) and dxdtau.  Each stage: dynamics! at the stage state (CRBA + Cholesky, the factor in the workspace),
+// the tangent RNEA (sign −1, dadd = dτ), the solve for dv̇, the stage kernel.
+template <typename T>
+int sim_tan_run(rbd_ws* w, int32_t B, int layout, void* q, void* v, const void* tau, const void* fext, double dt, int nsteps, int ndir, bool jac, int g0,
+                void* dq, void* dv, const void* dtau, const void* dfext, void* dxdx, void* dxdtau) {
+  const rbd_model* m = w->model;
+  const int nq = m->nq, nv = m->nv, nx = nq + nv, W = w->sim_tan_w;
+  const long Bm = w->max_batch;
+  const size_t es = sizeof(T);
+  const Layout Lq = layout_of(layout, nq, B), Lv = layout_of(layout, nv, B), Li{B, 1};
+  const Layout Ldq = layout_of(layout, (long)nq * ndir, B), Ldv = layout_of(layout, (long)nv * ndir, B), Ldf = layout_of(layout, 6L * m->nb * ndir, B);
+  // values (the call's layout): q0, the two stage-state buffers, the saved initial state; v0, two stage states, the running sum, the saved state
+  T* val = (T*)w->d_sim_val;
+  T *q0 = val, *qa = q0 + nq * Bm, *qb = qa + nq * Bm, *qi = qb + nq * Bm, *v0 = qi + nq * Bm, *va = v0 + nv * Bm, *vb = va + nv * Bm;
+  T *accp = vb + nv * Bm, *accv = accp + nv * Bm, *vi = accv + nv * Bm;
+  // tangents of one pass, batch-innermost
+  T* tb = (T*)w->d_sim_tan;
+  const long tw = (long)W * Bm;
+  T *dq0 = tb, *dv0 = dq0 + nq * tw, *dd0 = dv0 + nv * tw, *dqs = dd0 + nv * tw, *dvs = dqs + nq * tw, *dap = dvs + nv * tw, *dav = dap + nv * tw,
+    *dvd = dav + nv * tw;
+  auto col = [&](T* p, int n) { return ColOut<T>{p, Li, nullptr, Layout{0, 0}, INT32_MAX, n}; };
+  auto user = [&](const void* p, Layout L, int n) { return ColOut<T>{(T*)p, L, nullptr, Layout{0, 0}, INT32_MAX, n}; };
+  const int npass = (ndir + W - 1) / W;
+  if (npass > 1) {
+    HIP_TRY(hipMemcpyAsync(qi, q, es * nq * B, hipMemcpyDeviceToDevice, w->stream));
+    HIP_TRY(hipMemcpyAsync(vi, v, es * nv * B, hipMemcpyDeviceToDevice, w->stream));
+  }
+  for (int p = 0; p < npass; ++p) {
+    const int e0 = p * W, nw = std::min(W, ndir - e0);
+    if (p > 0) {  // every pass starts from the caller's state (each one writes the same state after the step)
+      HIP_TRY(hipMemcpyAsync(q, qi, es * nq * B, hipMemcpyDeviceToDevice, w->stream));
+      HIP_TRY(hipMemcpyAsync(v, vi, es * nv * B, hipMemcpyDeviceToDevice, w->stream));
+    }
+    HIP_TRY(launch_tangent_mk_load<T>(B, nw, nq, nv, jac ? g0 + e0 : e0, jac ? 1 : 0, user(dq, Ldq, nq), user(dv, Ldv, nv), user(dtau, Ldv, nv), col(dq0, nq),
+                                      col(dv0, nv), col(dd0, nv), w->stream));
+    for (int step = 0; step < nsteps; ++step) {
+      HIP_TRY(hipMemcpyAsync(q0, q, es * nq * B, hipMemcpyDeviceToDevice, w->stream));
+      HIP_TRY(hipMemcpyAsync(v0, v, es * nv * B, hipMemcpyDeviceToDevice, w->stream));
+      for (int stage = 0; stage < 4; ++stage) {
+        // the stage state: (q, v) at stage 0, then qa/va, qb/vb, qa/va; stage 3 writes the state after the step over (q, v)
+        T* qs = stage == 0 ? (T*)q : (stage == 2 ? qb : qa);
+        T* vs = stage == 0 ? (T*)v : (stage == 2 ? vb : va);
+        int st;
+        if ((st = tan_dynamics_value<T>(w, B, layout, qs, vs, tau, fext, w->d_tan_vd))) return st;
+        TanArgs<T> A = tan_args<T>(w, B, layout, nw, qs, vs, w->d_tan_vd, fext);
+        A.dq = stage == 0 ? dq0 : dqs; A.dv = stage == 0 ? dv0 : dvs; A.Ldq = Li; A.Ldv = Li;
+        A.dfext = (!jac && dfext) ? (const T*)dfext + (long)e0 * 6 * m->nb * Ldf.sk : nullptr; A.Ldf = Ldf;
+        A.out.a = (T*)w->d_tan_rhs; A.out.La = Li;
+        A.sign = T(-1); A.dadd = dd0;
+        HIP_TRY(launch_tangent_rnea<T>(w->tan, A, w->d_tan_scratch, w->tan_threads, w->stream));
+        HIP_TRY(launch_tangent_solve<T>(nv, B, 0, nw, w->d_tan_L, Li, w->d_tan_rhs, 0, col(dvd, nv), w->d_tan_x, w->stream));
+        MkTanArgs<T> S{};
+        S.B = B; S.ntan = nw; S.nb = w->tan.nb; S.stage = stage; S.dt = (T)dt; S.tbl = w->tan.tbl;
+        S.q0 = q0; S.v0 = v0; S.qs = qs; S.vs = vs; S.vd = (const T*)w->d_tan_vd; S.accp = accp; S.accv = accv;
+        S.qn = stage == 3 ? (T*)q : (stage == 1 ? qb : qa);
+        S.vn = stage == 3 ? (T*)v : (stage == 1 ? vb : va);
+        S.Lq = Lq; S.Lv = Lv;
+        S.dq0 = col(dq0, nq); S.dv0 = col(dv0, nv); S.dqs = stage == 0 ? S.dq0 : col(dqs, nq); S.dvs = stage == 0 ? S.dv0 : col(dvs, nv);
+        S.dvd = col(dvd, nv); S.daccp = col(dap, nv); S.daccv = col(dav, nv);
+        S.ocol = 0; S.ovrow = 0;
+        if (stage < 3) {
+          S.oq = col(dqs, nq); S.ov = col(dvs, nv);
+        } else if (step < nsteps - 1) {  // (the next step's base point, in place)
+          S.oq = S.dq0; S.ov = S.dv0;
+        } else if (jac) {
+          S.oq = S.ov = ColOut<T>{(T*)dxdx, layout_of(layout, (long)nx * nx, B), (T*)dxdtau, layout_of(layout, (long)nx * nv, B), nx, nx};
+          S.ocol = g0 + e0; S.ovrow = nq;
+        } else {
+          S.oq = user(dq, Ldq, nq); S.ov = user(dv, Ldv, nv); S.ocol = e0;
+        }
+        HIP_TRY(launch_tangent_mk_stage<T>(S, w->stream));
+      }
+    }
+  }
+  return RBD_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2857,6 +2969,43 @@ int rbd_dynamics_derivatives(rbd_ws_t* w, int32_t B, const void* q, const void* 
   Timed t(w);
   w->last_kernel = "tangent_rnea_kernel + tangent_solve_kernel";
   return by_dtype(w->dtype, [&](auto t) { return tan_dyn_derivs<decltype(t)>(w, B, o.layout, q, v, tau, fext, vdot_out, dvdot_dq, dvdot_dv, dvdot_dtau); });
+}
+
+int rbd_simulate_jvp(rbd_ws_t* w, int32_t B, int32_t ntan, void* q, void* v, const void* tau, const void* fext, double dt, int32_t nsteps, void* dq,
+                     void* dv, const void* dtau, const void* dfext, const rbd_opts_t* opts) {
+  Opts o;
+  int st = tan_check(w, B, opts, &o);
+  if (st != RBD_OK) return st;
+  if (ntan <= 0 || !(dt > 0) || nsteps < 0 || !q || !v || !dq || !dv) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0 || nsteps == 0 || w->model->nv == 0) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  const int width = sim_pass_width(w, ntan);
+  if ((st = sim_ensure(w, width))) return st;
+  Timed t(w);
+  w->last_kernel = "tangent_rnea_kernel + tangent_solve_kernel + tangent_mk_stage_kernel";
+  return by_dtype(w->dtype, [&](auto t) {
+    return sim_tan_run<decltype(t)>(w, B, o.layout, q, v, tau, fext, dt, nsteps, ntan, false, 0, dq, dv, dtau, dfext, nullptr, nullptr);
+  });
+}
+
+int rbd_simulate_step_derivatives(rbd_ws_t* w, int32_t B, void* q, void* v, const void* tau, const void* fext, double dt, void* dx_dx, void* dx_dtau,
+                                  const rbd_opts_t* opts) {
+  Opts o;
+  int st = tan_check(w, B, opts, &o);
+  if (st != RBD_OK) return st;
+  const rbd_model* m = w->model;
+  if (!(dt > 0) || !q || !v) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0 || m->nv == 0) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  // the columns asked for: those of ∂x⁺/∂x (0 … nx − 1), then those of ∂x⁺/∂τ (a pass of one column that writes nowhere when neither is)
+  const int nx = m->nq + m->nv, g0 = dx_dx ? 0 : nx, g1 = dx_dtau ? nx + m->nv : nx, ncol = std::max(1, g1 - g0);
+  const int width = sim_pass_width(w, std::max(ncol, nx + m->nv));  // (allocated for every column: a call with the other output allocates nothing)
+  if ((st = sim_ensure(w, width))) return st;
+  Timed t(w);
+  w->last_kernel = "tangent_rnea_kernel + tangent_solve_kernel + tangent_mk_stage_kernel";
+  return by_dtype(w->dtype, [&](auto t) {
+    return sim_tan_run<decltype(t)>(w, B, o.layout, q, v, tau, fext, dt, 1, ncol, true, g0, nullptr, nullptr, nullptr, nullptr, dx_dx, dx_dtau);
+  });
 }
 
 }  // extern "C"

@@ -1,8 +1,10 @@
 // rbd_tangent_kernels.hip — the kernels of the derivative entry points (rbd_inverse_dynamics_jvp, rbd_dynamics_jvp, rbd_inverse_dynamics_derivatives,
-// rbd_dynamics_derivatives): the tangent RNEA (rbd_tangent.hpp) with one thread per (state, chunk of TAN_CHUNK directions), and the multi-right-hand-side
-// triangular solve of dynamics! tangents against the Cholesky factor of M.  Compiled with -ffinite-math-only -fno-signed-zeros (build.sh): the zero
+// rbd_dynamics_derivatives, rbd_simulate_jvp, rbd_simulate_step_derivatives): the tangent RNEA (rbd_tangent.hpp) with one thread per (state, chunk of
+// TAN_CHUNK directions), the multi-right-hand-side triangular solve of dynamics! tangents against the Cholesky factor of M, and the tangent of the
+// integrator's stage map (rbd_tangent_mk.hpp) with one thread per (state, joint, chunk).  Compiled with -ffinite-math-only -fno-signed-zeros (build.sh): the zero
 // tangents of the mechanism's constants fold out of the products.
 #include "rbd_tangent.hpp"
+#include "rbd_tangent_mk.hpp"
 #include "rbd_internal.hpp"
 
 namespace rbd {
@@ -93,10 +95,106 @@ template <typename T> hipError_t launch_symmetrize(int nv, long B, void* M, Layo
   return hipGetLastError();
 }
 
+// ---- simulate tangents: one thread per (state, joint, chunk of N directions), thread = (chunk · nb + joint) · B + state ----------------------------------
+template <typename T, int N>
+__global__ __launch_bounds__(64) void tangent_mk_stage_kernel(MkTanArgs<T> A) {
+  using D = Dual<T, N>;
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long nchunks = (A.ntan + N - 1) / N;
+  if (t >= nchunks * A.nb * A.B) return;
+  const long st = t % A.B, r = t / A.B;
+  const int i = (int)(r % A.nb), chunk = (int)(r / A.nb);
+  const int jt = A.tbl[4 * i + 1], qoff = A.tbl[4 * i + 2], voff = A.tbl[4 * i + 3];
+  const int nqi = joint_nq<T>(jt), nvi = joint_nv(jt);
+  if (nvi == 0) return;
+  const int e0 = chunk * N;
+  // value of row `row` (nullable: not needed by this thread) and the tangents of the chunk's directions (zero past the pass's directions)
+  auto load = [&](const T* val, Layout L, const ColOut<T>& tan, int row) {
+    D x(val ? val[(long)row * L.sk + layout_base(L, st)] : T(0));
+#pragma unroll
+    for (int j = 0; j < N; ++j) x.d[j] = e0 + j < A.ntan ? *tan.at(e0 + j, row, st) : T(0);
+    return x;
+  };
+  D q0[7], qs[7], v0[6], vs[6], vd[6], ap[6], av[6], qn[7], vn[6];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    q0[k] = k < nqi ? load(A.q0, A.Lq, A.dq0, qoff + k) : D(T(0));
+    qs[k] = k < nqi ? load(A.qs, A.Lq, A.dqs, qoff + k) : D(T(0));
+  }
+  // (the running sums: only chunk 0 reads and writes their values before the last stage, which reads them everywhere)
+  const bool accval = A.stage == 3 || chunk == 0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const bool in = k < nvi;
+    v0[k] = in ? load(A.v0, A.Lv, A.dv0, voff + k) : D(T(0));
+    vs[k] = in ? load(A.vs, A.Lv, A.dvs, voff + k) : D(T(0));
+    vd[k] = in ? load(A.vd, A.Lv, A.dvd, voff + k) : D(T(0));
+    ap[k] = in && A.stage > 0 ? load(accval ? A.accp : nullptr, A.Lv, A.daccp, voff + k) : D(T(0));
+    av[k] = in && A.stage > 0 ? load(accval ? A.accv : nullptr, A.Lv, A.daccv, voff + k) : D(T(0));
+  }
+  tan_mk_stage_joint<T, N>(jt, A.stage, A.dt, q0, v0, qs, vs, vd, ap, av, qn, vn);
+  auto store = [&](T* val, Layout L, const ColOut<T>& tan, int col0, int row, int trow, const D& x) {
+    if (chunk == 0 && val) val[(long)row * L.sk + layout_base(L, st)] = x.v;
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+      if (e0 + j < A.ntan)
+        if (T* o = tan.at(col0 + e0 + j, trow, st)) *o = x.d[j];
+  };
+#pragma unroll
+  for (int k = 0; k < 7; ++k)
+    if (k < nqi) store(A.qn, A.Lq, A.oq, A.ocol, qoff + k, qoff + k, qn[k]);
+#pragma unroll
+  for (int k = 0; k < 6; ++k)
+    if (k < nvi) {
+      store(A.vn, A.Lv, A.ov, A.ocol, voff + k, A.ovrow + voff + k, vn[k]);
+      if (A.stage < 3) {
+        store(A.accp, A.Lv, A.daccp, 0, voff + k, voff + k, ap[k]);
+        store(A.accv, A.Lv, A.daccv, 0, voff + k, voff + k, av[k]);
+      }
+    }
+}
+
+template <typename T> hipError_t launch_tangent_mk_stage(const MkTanArgs<T>& A, hipStream_t s) {
+  constexpr int N = TanChunk<T>::N;
+  const long total = (long)((A.ntan + N - 1) / N) * A.nb * A.B;
+  if (total == 0) return hipSuccess;
+  hipLaunchKernelGGL((tangent_mk_stage_kernel<T, N>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, A);
+  return hipGetLastError();
+}
+
+// the initial tangents of a pass of ncol directions (thread = direction · B + state): columns col0 … of the caller's (dq, dv, dτ) (nullable: zero), or
+// with `unit` the unit vectors of the step Jacobians' columns — column g is e_g of (q; v) for g < nq + nv, else e_{g − nq − nv} of τ
+template <typename T>
+__global__ __launch_bounds__(256) void tangent_mk_load_kernel(long B, int ncol, int nq, int nv, int col0, int unit, ColOut<T> sq, ColOut<T> sv, ColOut<T> sd,
+                                                              ColOut<T> dq, ColOut<T> dv, ColOut<T> dd) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)ncol * B) return;
+  const int e = (int)(t / B), g = col0 + e;
+  const long st = t % B;
+  auto src = [&](const ColOut<T>& s, int r) -> T { const T* p = s.at(g, r, st); return p ? *p : T(0); };
+  for (int r = 0; r < nq; ++r) *dq.at(e, r, st) = unit ? T(g == r ? 1 : 0) : src(sq, r);
+  for (int r = 0; r < nv; ++r) {
+    *dv.at(e, r, st) = unit ? T(g == nq + r ? 1 : 0) : src(sv, r);
+    *dd.at(e, r, st) = unit ? T(g == nq + nv + r ? 1 : 0) : src(sd, r);
+  }
+}
+
+template <typename T>
+hipError_t launch_tangent_mk_load(long B, int ncol, int nq, int nv, int col0, int unit, const ColOut<T>& sq, const ColOut<T>& sv, const ColOut<T>& sd,
+                                  const ColOut<T>& dq, const ColOut<T>& dv, const ColOut<T>& dd, hipStream_t s) {
+  const long total = (long)ncol * B;
+  if (total == 0) return hipSuccess;
+  hipLaunchKernelGGL(tangent_mk_load_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, B, ncol, nq, nv, col0, unit, sq, sv, sd, dq, dv, dd);
+  return hipGetLastError();
+}
+
 #define RBD_TAN_INST(T)                                                                                                                                    \
   template hipError_t launch_tangent_rnea<T>(const BigModel&, const TanArgs<T>&, void*, long, hipStream_t);                                              \
   template hipError_t launch_tangent_solve<T>(int, long, int, int, const void*, Layout, const void*, int, const ColOut<T>&, void*, hipStream_t);          \
-  template hipError_t launch_symmetrize<T>(int, long, void*, Layout, hipStream_t);
+  template hipError_t launch_symmetrize<T>(int, long, void*, Layout, hipStream_t);                                                                   \
+  template hipError_t launch_tangent_mk_stage<T>(const MkTanArgs<T>&, hipStream_t);                                                                     \
+  template hipError_t launch_tangent_mk_load<T>(long, int, int, int, int, int, const ColOut<T>&, const ColOut<T>&, const ColOut<T>&, const ColOut<T>&,   \
+                                                const ColOut<T>&, const ColOut<T>&, hipStream_t);
 RBD_TAN_INST(double)
 RBD_TAN_INST(float)
 

@@ -552,6 +552,54 @@ def dynamics_derivatives_(state: MechanismState, torques: Optional[torch.Tensor]
     return dvd_dq, dvd_dv, dvd_dtau
 
 
+def simulate_jvp_(dq: torch.Tensor, dv: torch.Tensor, state: MechanismState, ntan: int, dt: float, nsteps: int = 1, torques: Optional[torch.Tensor] = None,
+                  dtorques: Optional[torch.Tensor] = None, externalwrenches: Optional[torch.Tensor] = None, dexternalwrenches: Optional[torch.Tensor] = None):
+    """`nsteps` steps of `simulate_` (constant `torques`, the Munthe-Kaas RK4 step) with `ntan` tangent directions carried along: `state.q`, `state.v`
+    and the tangents `dq` (B, ntan·nq), `dv` (B, ntan·nv) are advanced in place.  `dtorques` / `dexternalwrenches` are held over every stage of every
+    step, as the torques and wrenches are.  The value path is dynamics!'s CRBA + Cholesky route at every stage, so q, v equal `simulate_`'s to rounding."""
+    f = state.flat
+    if int(ntan) <= 0:
+        raise ValueError("ntan must be positive")
+    if not float(dt) > 0:
+        raise ValueError("dt must be positive")
+    if int(nsteps) < 0:
+        raise ValueError("nsteps must be non-negative")
+    if dq is None or dv is None:
+        raise ValueError("dq and dv are required (in / out)")
+    _check_tangent(state, dq, f.nq, ntan, "dq")
+    _check_tangent(state, dv, f.nv, ntan, "dv")
+    state._check(torques, f.nv, "torques")
+    _check_tangent(state, dtorques, f.nv, ntan, "dτ")
+    state._check(externalwrenches, 6 * f.n_bodies, "externalwrenches")
+    _check_tangent(state, dexternalwrenches, 6 * f.n_bodies, ntan, "dexternalwrenches")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_simulate_jvp(state.ws.handle, state.batch, int(ntan), _ptr(state.q), _ptr(state.v), _ptr(torques), _ptr(externalwrenches),
+                                      ctypes.c_double(dt), int(nsteps), _ptr(dq), _ptr(dv), _ptr(dtorques), _ptr(dexternalwrenches), ctypes.byref(opts))
+    _raise(st, "rbd_simulate_jvp")
+    return dq, dv
+
+
+def simulate_step_derivatives_(state: MechanismState, dt: float, torques: Optional[torch.Tensor] = None, dx_dx: Optional[torch.Tensor] = None,
+                               dx_dtau: Optional[torch.Tensor] = None, externalwrenches: Optional[torch.Tensor] = None):
+    """One step of `simulate_` (`state.q`, `state.v` advanced in place) and its Jacobians with x = (q; v), nx = nq + nv: dx_dx = ∂x⁺/∂x (B, nx·nx),
+    dx_dtau = ∂x⁺/∂τ (B, nx·nv), column-major per state (jacobian_view(t, state, nx, cols)); both optional; the external wrenches held fixed."""
+    f = state.flat
+    nx = f.nq + f.nv
+    if not float(dt) > 0:
+        raise ValueError("dt must be positive")
+    state._check(torques, f.nv, "torques")
+    state._check(dx_dx, nx * nx, "dx_dx")
+    state._check(dx_dtau, nx * f.nv, "dx_dtau")
+    state._check(externalwrenches, 6 * f.n_bodies, "externalwrenches")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_simulate_step_derivatives(state.ws.handle, state.batch, _ptr(state.q), _ptr(state.v), _ptr(torques), _ptr(externalwrenches),
+                                                   ctypes.c_double(dt), _ptr(dx_dx), _ptr(dx_dtau), ctypes.byref(opts))
+    _raise(st, "rbd_simulate_step_derivatives")
+    return dx_dx, dx_dtau
+
+
 def jacobian_view(t: torch.Tensor, state: MechanismState, rows: int, cols: int) -> torch.Tensor:
     """A derivative output as (B, rows, cols): a Jacobian (rows × cols, column-major per state: (B, rows·cols), or (rows·cols, B) with layout="soa"), or a
     tangent output of `cols` directions of `rows` coordinates (direction d = column d).  A view when the layout allows, else a copy."""
