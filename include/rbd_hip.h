@@ -438,6 +438,25 @@ int rbd_simulate_jvp(rbd_ws_t* ws, int32_t B, int32_t ntan, void* q, void* v, co
  * column j is the JVP along the j-th unit vector.  Both are nullable; fext is held fixed. */
 int rbd_simulate_step_derivatives(rbd_ws_t* ws, int32_t B, void* q, void* v, const void* tau, const void* fext, double dt,
                                   void* dx_dx, void* dx_dtau, const rbd_opts_t* opts);
+/* Reverse mode (700 additions): vector-Jacobian products, the gradient of a scalar loss through inverse_dynamics! / dynamics! from one adjoint RNEA
+ * pass per state, where the Jacobians above cost nq + nv tangent directions.  Semantics as the JVPs: raw coordinates q, tree mechanisms only
+ * (RBD_ERR_HAS_LOOPS; RBD_ERR_UNSUPPORTED for contact points with an environment and for RBD_MEM_HOST), device pointers, fp32 and fp64, both layouts.
+ *  - One cotangent per state, in the batch layout of opts: tau_bar (nv) for inverse dynamics, vdot_bar (nv) for dynamics.
+ *  - Every output is nullable and OVERWRITTEN (not accumulated): q_bar = (∂/∂q)ᵀ·cotangent has nq rows, v_bar, vdot_bar and tau_bar nv, fext_bar 6·n_bodies.
+ *  - A NULL q, v or cotangent, or a NULL vdot for inverse dynamics: RBD_ERR_INVALID_ARGUMENT; B == 0 is a successful no-op.
+ *  - The value outputs (tau_out, vdot_out, nullable) equal rbd_inverse_dynamics / the CRBA + Cholesky route of rbd_dynamics to rounding.
+ *  - Allocation: the first reverse-mode call of a workspace allocates its adjoint scratch for max_batch states (at most 1 GiB; larger batches run in
+ *    slabs) and the buffers every derivative call shares; no later call allocates or synchronises.
+ *  - rbd_workspace_last_kernel names the adjoint kernel afterwards.
+ * rbd_inverse_dynamics_vjp: τ = ID(q, v, v̇, fext) and, with λ = tau_bar, q̄ = (∂τ/∂q)ᵀλ, v̄ = (∂τ/∂v)ᵀλ, v̇̄ = Mλ, f̄ext = (∂τ/∂fext)ᵀλ. */
+int rbd_inverse_dynamics_vjp(rbd_ws_t* ws, int32_t B, const void* q, const void* v, const void* vdot, const void* fext,
+                             const void* tau_bar, void* tau_out, void* q_bar, void* v_bar, void* vdot_bar, void* fext_bar,
+                             const rbd_opts_t* opts);
+/* rbd_dynamics_vjp: v̇ by CRBA + Cholesky (the factor kept), λ = M⁻¹ vdot_bar with one triangular solve pair against it, τ̄ = λ and
+ * (q̄, v̄, f̄ext) = −(∂ID/∂(q, v, fext))ᵀλ at (q, v, v̇) — the implicit-function identity of rbd_dynamics_jvp, transposed. */
+int rbd_dynamics_vjp(rbd_ws_t* ws, int32_t B, const void* q, const void* v, const void* tau, const void* fext,
+                     const void* vdot_bar, void* vdot_out, void* q_bar, void* v_bar, void* tau_bar, void* fext_bar,
+                     const rbd_opts_t* opts);
 
 /* ---- diagnostics ------------------------------------------------------------ */
 const char* rbd_status_string(int status);
@@ -453,7 +472,8 @@ const char* rbd_workspace_last_kernel(const rbd_ws_t* ws);
  * not call a newer library (the Python and Julia loaders compare this with the value they were written for).  400: rbd_workspace_set_loop_gains.
  * 500: rbd_mass_matrix_solve_packed, rbd_gatherv.  600: rbd_jit_check_walk_object; no size limit left on any entry point; program family 11; family 1 in fp64.
  * 700: forward-mode derivatives — rbd_inverse_dynamics_jvp, rbd_dynamics_jvp, rbd_inverse_dynamics_derivatives, rbd_dynamics_derivatives;
- *      added to 700 without a new version: rbd_simulate_jvp, rbd_simulate_step_derivatives (derivatives of simulate steps). */
+ *      added to 700 without a new version: rbd_simulate_jvp, rbd_simulate_step_derivatives (derivatives of simulate steps);
+ *      rbd_inverse_dynamics_vjp, rbd_dynamics_vjp (reverse mode). */
 #define RBD_HIP_H_VERSION 700
 int rbd_version(void);
 /* Run-time specialisation.  The one-lane-per-state kernels (mass_matrix! and mass_matrix! + Cholesky at large batches) exist in a second form

@@ -29,7 +29,8 @@ import RigidBodyDynamics: dynamics!, inverse_dynamics!, mass_matrix!, dynamics_b
 using LinearAlgebra
 
 export BatchedMechanismState, BatchedDynamicsResult, DeviceMatrix, RbdComm, gather!, gatherv!, mass_matrix_solve_packed!, synchronize, librbd_hip, TorqueTable, PDControl,
-    inverse_dynamics_jvp!, dynamics_jvp!, inverse_dynamics_derivatives!, dynamics_derivatives!, simulate_jvp!, simulate_step_derivatives!
+    inverse_dynamics_jvp!, dynamics_jvp!, inverse_dynamics_derivatives!, dynamics_derivatives!, simulate_jvp!, simulate_step_derivatives!,
+    inverse_dynamics_vjp!, dynamics_vjp!
 
 const librbd_hip = Ref("librbd_hip.so")   # set to <repo>/rigidbodydynamics.jl_amd/csrc/librbd_hip.so
 const libhip = Ref("libamdhip64.so")
@@ -529,6 +530,43 @@ function simulate_step_derivatives!(dxdx, dxdτ, state::BatchedMechanismState{T}
         opts(state)), "rbd_simulate_step_derivatives")
     finish(state)
     dxdx, dxdτ
+end
+
+# ---- reverse mode (700 additions): vector-Jacobian products, one cotangent per state (nv × B), raw coordinates q as above.  Every output may be
+# `nothing` and is overwritten; q̄ is nq × B, v̄ / v̇̄ / τ̄ nv × B, f̄ext (6·n_bodies) × B.  (A ChainRules `rrule` would wrap these.)
+
+"""`inverse_dynamics_vjp!(q̄, v̄, v̇̄, state, v̇, τ̄; externalwrenches, f̄ext, torquesout)` — `inverse_dynamics!` pulled back: q̄ = (∂τ/∂q)ᵀτ̄,
+v̄ = (∂τ/∂v)ᵀτ̄, v̇̄ = M τ̄, f̄ext = (∂τ/∂fext)ᵀτ̄ (`rbd_inverse_dynamics_vjp`)."""
+function inverse_dynamics_vjp!(q̄, v̄, v̇̄, state::BatchedMechanismState{T}, v̇::Buffer{T}, τ̄::Buffer{T}; externalwrenches = nothing, f̄ext = nothing,
+        torquesout = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, B = state.model.nq, state.model.nv, batchsize(state)
+    for (x, n) in ((q̄, nq), (v̄, nv), (v̇̄, nv), (τ̄, nv), (torquesout, nv))
+        x === nothing || size(x) == (n, B) || throw(DimensionMismatch("cotangent buffer has wrong size"))
+    end
+    check(ccall((:rbd_inverse_dynamics_vjp, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, state.q, state.v, v̇, nullable(densewrenches(state, externalwrenches)), τ̄, nullable(torquesout), nullable(q̄), nullable(v̄),
+        nullable(v̇̄), nullable(f̄ext), opts(state)), "rbd_inverse_dynamics_vjp")
+    finish(state)
+    q̄, v̄, v̇̄
+end
+
+"""`dynamics_vjp!(q̄, v̄, τ̄, state, v̇̄; torques, externalwrenches, f̄ext, v̇out)` — `dynamics!` pulled back at the v̇ of the same call: λ = M⁻¹v̇̄, τ̄ = λ,
+(q̄, v̄, f̄ext) = −(∂ID/∂(q, v, fext))ᵀλ (`rbd_dynamics_vjp`)."""
+function dynamics_vjp!(q̄, v̄, τ̄, state::BatchedMechanismState{T}, v̇̄::Buffer{T}; torques = nothing, externalwrenches = nothing, f̄ext = nothing,
+        v̇out = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, B = state.model.nq, state.model.nv, batchsize(state)
+    for (x, n) in ((q̄, nq), (v̄, nv), (τ̄, nv), (v̇̄, nv), (v̇out, nv))
+        x === nothing || size(x) == (n, B) || throw(DimensionMismatch("cotangent buffer has wrong size"))
+    end
+    check(ccall((:rbd_dynamics_vjp, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, state.q, state.v, nullable(torques), nullable(densewrenches(state, externalwrenches)), v̇̄, nullable(v̇out), nullable(q̄), nullable(v̄),
+        nullable(τ̄), nullable(f̄ext), opts(state)), "rbd_dynamics_vjp")
+    finish(state)
+    q̄, v̄, τ̄
 end
 
 """`mass_matrix_solve_packed!(x, Mpacked, state, rhs)` — `mass_matrix!` + the potrf!/potrs! of `dynamics_solve!` (:764, :819) with M as LAPACK's packed lower

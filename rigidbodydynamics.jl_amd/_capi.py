@@ -26,6 +26,7 @@ SYMBOLS = (
     "rbd_workspace_bind_result", "rbd_workspace_set_loop_gains", "rbd_jit_precompile", "rbd_jit_source", "rbd_jit_status", "rbd_jit_wait_idle", "rbd_simulate_controlled", "rbd_comm_unique_id", "rbd_comm_create", "rbd_comm_destroy", "rbd_comm_info", "rbd_gather", "rbd_gatherv", "rbd_mass_matrix_solve_packed", "rbd_comm_last_error", "rbd_jit_check_walk_object",
     "rbd_inverse_dynamics_jvp", "rbd_dynamics_jvp", "rbd_inverse_dynamics_derivatives", "rbd_dynamics_derivatives",
     "rbd_simulate_jvp", "rbd_simulate_step_derivatives",
+    "rbd_inverse_dynamics_vjp", "rbd_dynamics_vjp",
 )
 
 
@@ -88,6 +89,8 @@ def lib():
         L.rbd_dynamics_derivatives.argtypes = [vp, i32] + [vp] * 8 + [ctypes.POINTER(Opts)]
         L.rbd_simulate_jvp.argtypes = [vp, i32, i32, vp, vp, vp, vp, ctypes.c_double, i32, vp, vp, vp, vp, ctypes.POINTER(Opts)]
         L.rbd_simulate_step_derivatives.argtypes = [vp, i32, vp, vp, vp, vp, ctypes.c_double, vp, vp, ctypes.POINTER(Opts)]
+        L.rbd_inverse_dynamics_vjp.argtypes = [vp, i32] + [vp] * 10 + [ctypes.POINTER(Opts)]
+        L.rbd_dynamics_vjp.argtypes = [vp, i32] + [vp] * 10 + [ctypes.POINTER(Opts)]
         L.rbd_model_chain_plan.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), i32]
         L.rbd_model_track_plan.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(ctypes.c_double), i32]
         L.rbd_comm_unique_id.argtypes = [vp]

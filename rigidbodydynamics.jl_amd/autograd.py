@@ -1,0 +1,135 @@
+"""torch.autograd through the library: `tau = inverse_dynamics(state, q, v, vd, fext)` and `vd = dynamics(state, q, v, tau, fext)` are differentiable
+functions of their tensor arguments, so `loss.backward()` (reverse mode) and `torch.func.jvp` / `torch.autograd.forward_ad` (forward mode) work through
+them.
+
+  - `state` (a MechanismState) supplies the workspace, the batch, the dtype and the layout; q, v, … are tensors of that layout ((B, n) with "aos",
+    (n, B) with "soa"); `state.q` / `state.v` are neither read nor written.
+  - The forward pass is the library's normal call (rbd_inverse_dynamics / rbd_dynamics), so the value stays on the fast routes.
+  - backward is one vector-Jacobian product per call (rbd_inverse_dynamics_vjp / rbd_dynamics_vjp) on the current torch stream; forward-mode AD is one
+    JVP with one direction (rbd_inverse_dynamics_jvp / rbd_dynamics_jvp).
+  - The derivatives are those of the raw coordinates q (a quaternion joint's unnormalised rotation formula; a SinCosRevolute's (s, c) as two
+    coordinates), as every derivative entry point of the library.
+  - Double backward is not supported (once_differentiable)."""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional
+
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _capi
+from .state import MechanismState, _ptr, _raise, dynamics_vjp_, inverse_dynamics_vjp_
+
+
+def _prep(state: MechanismState, t: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    t = t.detach().contiguous()
+    state._check(t, n, what)
+    return t
+
+
+def _empty(state: MechanismState, n: int, need: bool = True) -> Optional[torch.Tensor]:
+    if not need:
+        return None
+    shape = (state.batch, n) if state.layout == "aos" else (n, state.batch)
+    return torch.empty(shape, dtype=state.dtype, device=state.device)
+
+
+class _InverseDynamics(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, state, q, v, vd, fext):
+        f = state.flat
+        q, v, vd = _prep(state, q, f.nq, "q"), _prep(state, v, f.nv, "v"), _prep(state, vd, f.nv, "v̇")
+        fext = _prep(state, fext, 6 * f.n_bodies, "externalwrenches")
+        tau = _empty(state, f.nv)
+        state.ws.use_current_stream()
+        opts = state._opts()
+        _raise(_capi.lib().rbd_inverse_dynamics(state.ws.handle, state.batch, _ptr(q), _ptr(v), _ptr(vd), _ptr(fext), _ptr(tau), ctypes.byref(opts)),
+               "rbd_inverse_dynamics")
+        ctx.state = state
+        ctx.save_for_backward(q, v, vd, fext)
+        ctx.save_for_forward(q, v, vd, fext)
+        return tau
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, tau_bar):
+        state, f = ctx.state, ctx.state.flat
+        q, v, vd, fext = ctx.saved_tensors
+        _, nq_, nv_, nvd_, nf_ = ctx.needs_input_grad
+        out = (_empty(state, f.nq, nq_), _empty(state, f.nv, nv_), _empty(state, f.nv, nvd_), _empty(state, 6 * f.n_bodies, nf_ and fext is not None))
+        if any(o is not None for o in out):
+            inverse_dynamics_vjp_(state, vd, _prep(state, tau_bar, f.nv, "tau_bar"), *out[:3], externalwrenches=fext, fext_bar=out[3], q=q, v=v)
+        return (None,) + out
+
+    @staticmethod
+    def jvp(ctx, _dstate, dq, dv, dvd, dfext):
+        state, f = ctx.state, ctx.state.flat
+        q, v, vd, fext = ctx.saved_tensors
+        dq, dv, dvd = _prep(state, dq, f.nq, "dq"), _prep(state, dv, f.nv, "dv"), _prep(state, dvd, f.nv, "dv̇")
+        dfext = _prep(state, dfext, 6 * f.n_bodies, "dexternalwrenches") if fext is not None else None
+        dtau = _empty(state, f.nv)
+        state.ws.use_current_stream()
+        opts = state._opts()
+        _raise(_capi.lib().rbd_inverse_dynamics_jvp(state.ws.handle, state.batch, 1, _ptr(q), _ptr(v), _ptr(vd), _ptr(fext), _ptr(dq), _ptr(dv), _ptr(dvd),
+                                                    _ptr(dfext), None, _ptr(dtau), ctypes.byref(opts)), "rbd_inverse_dynamics_jvp")
+        return dtau
+
+
+class _Dynamics(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, state, q, v, tau, fext, algorithm):
+        f = state.flat
+        q, v, tau = _prep(state, q, f.nq, "q"), _prep(state, v, f.nv, "v"), _prep(state, tau, f.nv, "torques")
+        fext = _prep(state, fext, 6 * f.n_bodies, "externalwrenches")
+        vd = _empty(state, f.nv)
+        state.ws.use_current_stream()
+        opts = state._opts({"aba": _capi.ALGO_ABA, "crba": _capi.ALGO_CRBA_CHOLESKY}[algorithm])
+        _raise(_capi.lib().rbd_dynamics(state.ws.handle, state.batch, _ptr(q), _ptr(v), _ptr(tau), _ptr(fext), _ptr(vd), None, None, ctypes.byref(opts)),
+               "rbd_dynamics")
+        ctx.state = state
+        ctx.save_for_backward(q, v, tau, fext)
+        ctx.save_for_forward(q, v, tau, fext)
+        return vd
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, vd_bar):
+        state, f = ctx.state, ctx.state.flat
+        q, v, tau, fext = ctx.saved_tensors
+        _, nq_, nv_, nt_, nf_, _ = ctx.needs_input_grad
+        out = (_empty(state, f.nq, nq_), _empty(state, f.nv, nv_), _empty(state, f.nv, nt_ and tau is not None), _empty(state, 6 * f.n_bodies, nf_ and fext is not None))
+        if any(o is not None for o in out):
+            dynamics_vjp_(state, _prep(state, vd_bar, f.nv, "vd_bar"), tau, out[0], out[1], out[2], externalwrenches=fext, fext_bar=out[3], q=q, v=v)
+        return (None,) + out + (None,)
+
+    @staticmethod
+    def jvp(ctx, _dstate, dq, dv, dtau, dfext, _dalgorithm):
+        state, f = ctx.state, ctx.state.flat
+        q, v, tau, fext = ctx.saved_tensors
+        dq, dv = _prep(state, dq, f.nq, "dq"), _prep(state, dv, f.nv, "dv")
+        dtau = _prep(state, dtau, f.nv, "dτ") if tau is not None else None
+        dfext = _prep(state, dfext, 6 * f.n_bodies, "dexternalwrenches") if fext is not None else None
+        dvd = _empty(state, f.nv)
+        state.ws.use_current_stream()
+        opts = state._opts()
+        _raise(_capi.lib().rbd_dynamics_jvp(state.ws.handle, state.batch, 1, _ptr(q), _ptr(v), _ptr(tau), _ptr(fext), _ptr(dq), _ptr(dv), _ptr(dtau),
+                                            _ptr(dfext), None, _ptr(dvd), ctypes.byref(opts)), "rbd_dynamics_jvp")
+        return dvd
+
+
+def inverse_dynamics(state: MechanismState, q: torch.Tensor, v: torch.Tensor, vd: torch.Tensor, fext: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """τ = inverse_dynamics!(q, v, v̇, f_ext), differentiable in q, v, vd and fext (None: no external wrenches)."""
+    return _InverseDynamics.apply(state, q, v, vd, fext)
+
+
+def dynamics(state: MechanismState, q: torch.Tensor, v: torch.Tensor, tau: Optional[torch.Tensor] = None, fext: Optional[torch.Tensor] = None,
+             algorithm: str = "aba") -> torch.Tensor:
+    """v̇ = dynamics!(q, v, τ, f_ext), differentiable in q, v, tau and fext (None: zero torques / no external wrenches).  The value is rbd_dynamics's
+    (algorithm="aba": the articulated-body route the workspace picks; "crba": the reference's CRBA + Cholesky route).  The derivatives are those of the
+    CRBA + Cholesky route of the same function (the implicit-function identity through M(q)), which equal the articulated-body value's to rounding.
+    In the raw coordinates OFF the unit sphere of a quaternion (or circle of a SinCosRevolute's (s, c)) the two routes are different functions of q; the
+    derivatives there are the CRBA route's, so finite differences of raw q off the sphere match algorithm="crba"."""
+    return _Dynamics.apply(state, q, v, tau, fext, algorithm)

@@ -26,6 +26,7 @@
 #include "rbd_mk_fuse.hpp"
 #include "rbd_tangent.hpp"
 #include "rbd_tangent_mk.hpp"
+#include "rbd_adjoint.hpp"
 enum { BANK_LDS_PAIRS_HOST = 30 };  // = BANK_LDS_PAIRS of rbd_bank.hpp (16 parked + 14 exchange pairs per lane; checked in rbd_bank_kernels.hip)
 
 using namespace rbd;
@@ -193,6 +194,11 @@ struct rbd_ws {
   size_t d_tan_M_bytes = 0, d_tan_L_bytes = 0, d_tan_c_bytes = 0, d_tan_vd_bytes = 0, d_tan_rhs_bytes = 0, d_tan_x_bytes = 0;
   // the simulate derivatives (rbd_simulate_jvp, rbd_simulate_step_derivatives): the stage states' values, and the tangents of one pass of sim_tan_w directions
   void* d_sim_val = nullptr; void* d_sim_tan = nullptr; size_t d_sim_val_bytes = 0, d_sim_tan_bytes = 0; int sim_tan_w = 0;
+  // the reverse-mode entry points (rbd_inverse_dynamics_vjp, rbd_dynamics_vjp): the adjoint scratch (adj_states states per launch), the cotangent of v̇
+  // staged batch-innermost, λ = M⁻¹ v̇̄ when the caller passes no τ̄, and for more than 64 coordinates the solve's own vector
+  bool adj_ready = false; long adj_states = 0;
+  void* d_adj_scratch = nullptr; void* d_adj_rhs = nullptr; void* d_adj_lam = nullptr; void* d_adj_x = nullptr;
+  size_t d_adj_scratch_bytes = 0, d_adj_rhs_bytes = 0, d_adj_lam_bytes = 0, d_adj_x_bytes = 0;
 };
 
 // RBD_TUNE="key=value,key=value,...": the developer knobs of the tests and sweep scripts in ONE environment variable (batch thresholds between the lane
@@ -1085,7 +1091,7 @@ int rbd_workspace_destroy(rbd_ws_t* w) {
   (void)hipSetDevice(w->device);
   void* ptrs[] = {w->d_big_L, w->d_big_tbl, w->d_big_rb, w->d_big_scratch, w->d_fused_i, w->d_tauwork, w->d_rr_chain_i, w->d_rr_chain_r, w->d_rrtrack_ri, w->d_rrtrack_rr, w->d_rrwalk_wk, w->d_cp_body, w->d_cp_r, w->d_hs_r, w->d_tw, w->d_cw, w->d_s0, w->d_sacc, w->d_sdot, w->d_rows, w->d_walk_wk, w->d_state_ops, w->d_state_cols, w->d_state_sr, w->d_Msoa, w->d_track_ri, w->d_track_rr, w->d_bank_ib[0], w->d_bank_ib[1], w->d_bank_rb[0], w->d_bank_rb[1], w->d_ib, w->d_rb, w->d_nslots, w->d_dof_body, w->d_anc, w->d_row_mask, w->d_M, w->d_c, w->d_K, w->d_k, (void*)w->d_notpd, w->d_body, w->d_scratch, w->d_loop_i, w->d_loop_r, w->d_loop_path, w->d_jt_ref, w->d_voff_ref, w->d_axis_ref, w->d_axis2_ref,
                   w->d_tan_tbl, w->d_tan_rb, w->d_tan_scratch, w->d_tan_M, w->d_tan_L, w->d_tan_c, w->d_tan_vd, w->d_tan_rhs, w->d_tan_x,
-                  w->d_sim_val, w->d_sim_tan};
+                  w->d_sim_val, w->d_sim_tan, w->d_adj_scratch, w->d_adj_rhs, w->d_adj_lam, w->d_adj_x};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (void* p : w->stage) if (p) (void)hipFree(p);
   {
@@ -2632,6 +2638,9 @@ template <typename T>
 hipError_t launch_tangent_solve(int nv, long B, int c0, int ncol, const void* L, Layout Ll, const void* rhs, int identity, const ColOut<T>& out, void* xmem, hipStream_t s);
 template <typename T> hipError_t launch_symmetrize(int nv, long B, void* M, Layout Lm, hipStream_t s);
 template <typename T> hipError_t launch_tangent_mk_stage(const MkTanArgs<T>& A, hipStream_t s);
+size_t adjoint_scratch_elems_per_state(const BigModel& M);
+template <typename T> hipError_t launch_adjoint_rnea(const BigModel& M, const AdjArgs<T>& A, void* scratch, long max_states, hipStream_t s);
+template <typename T> hipError_t launch_stage_rows(int n, long B, const void* x, Layout L, void* out, hipStream_t s);
 template <typename T>
 hipError_t launch_tangent_mk_load(long B, int ncol, int nq, int nv, int col0, int unit, const ColOut<T>& sq, const ColOut<T>& sv, const ColOut<T>& sd,
                                   const ColOut<T>& dq, const ColOut<T>& dv, const ColOut<T>& dd, hipStream_t s);
@@ -2640,8 +2649,8 @@ hipError_t launch_tangent_mk_load(long B, int ncol, int nq, int nv, int col0, in
 namespace {
 enum : long { TAN_SCRATCH_CAP = 1L << 30 };  // bytes of tangent scratch at most: larger calls run in slabs of (state, chunk) threads
 
-// the first derivative call of a workspace (and one with more directions than before) allocates; every later call only launches
-int tan_ensure(rbd_ws* w, int ntan) {
+// what every derivative entry point shares, allocated by the first one: the tables in the reference's order, M, its factor, c and v̇
+int tan_base(rbd_ws* w) {
   const rbd_model* m = w->model;
   const size_t es = esize(w);
   const long B = w->max_batch;
@@ -2673,6 +2682,16 @@ int tan_ensure(rbd_ws* w, int ntan) {
       return st;
     w->tan_ready = true;
   }
+  return RBD_OK;
+}
+
+// the first derivative call of a workspace (and one with more directions than before) allocates; every later call only launches
+int tan_ensure(rbd_ws* w, int ntan) {
+  const rbd_model* m = w->model;
+  const size_t es = esize(w);
+  const long B = w->max_batch;
+  int st;
+  if ((st = tan_base(w))) return st;
   ntan = std::max(ntan, m->nq + m->nv);  // (the Jacobians' directions: a JVP call after a derivatives call allocates nothing)
   if (ntan > w->tan_ntan) {
     const int N = tangent_chunk((int)es);
@@ -2907,6 +2926,75 @@ int sim_tan_run(rbd_ws* w, int32_t B, int layout, void* q, void* v, const void* 
   }
   return RBD_OK;
 }
+
+// ---- reverse mode (header 700 additions): the adjoint RNEA, one thread per state -------------------------------------------------------------------------
+enum : long { ADJ_SCRATCH_CAP = TAN_SCRATCH_CAP };  // bytes of adjoint scratch at most: larger calls run in slabs of states
+
+// the first reverse-mode call of a workspace allocates (for max_batch states); every later call only launches
+int adj_ensure(rbd_ws* w) {
+  const rbd_model* m = w->model;
+  const size_t es = esize(w), nv = (size_t)m->nv;
+  const long B = w->max_batch;
+  int st;
+  if ((st = tan_base(w))) return st;
+  if (w->adj_ready) return RBD_OK;
+  const size_t per = std::max<size_t>(1, adjoint_scratch_elems_per_state(w->tan) * es);
+  const long states = std::min<long>(B, std::max<long>(64, (long)(ADJ_SCRATCH_CAP / per) / 64 * 64));
+  if ((st = ensure(&w->d_adj_scratch, &w->d_adj_scratch_bytes, per * states))) return st;
+  if ((st = ensure(&w->d_adj_rhs, &w->d_adj_rhs_bytes, es * std::max<size_t>(1, nv * B))) || (st = ensure(&w->d_adj_lam, &w->d_adj_lam_bytes, es * std::max<size_t>(1, nv * B))))
+    return st;
+  if (m->nv > 64 && (st = ensure(&w->d_adj_x, &w->d_adj_x_bytes, es * nv * B))) return st;
+  w->adj_states = states;
+  w->adj_ready = true;
+  return RBD_OK;
+}
+
+template <typename T> AdjArgs<T> adj_args(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, const void* vdot, const void* fext) {
+  const rbd_model* m = w->model;
+  AdjArgs<T> A{};
+  A.B = B;
+  A.q = (const T*)q; A.v = (const T*)v; A.vdot = (const T*)vdot; A.fext = (const T*)fext;
+  A.Lq = layout_of(layout, m->nq, B); A.Lv = layout_of(layout, m->nv, B); A.Lf = layout_of(layout, 6L * m->nb, B); A.Llam = A.Lv;
+  A.sign = T(1);
+  return A;
+}
+
+template <typename T>
+int adj_id_vjp(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, const void* vdot, const void* fext, const void* tau_bar, void* tau_out,
+               void* q_bar, void* v_bar, void* vdot_bar, void* fext_bar) {
+  AdjArgs<T> A = adj_args<T>(w, B, layout, q, v, vdot, fext);
+  A.lam = (const T*)tau_bar;
+  A.tau = (T*)tau_out; A.qbar = (T*)q_bar; A.vbar = (T*)v_bar; A.vdbar = (T*)vdot_bar; A.fbar = (T*)fext_bar;
+  HIP_TRY(launch_adjoint_rnea<T>(w->tan, A, w->d_adj_scratch, w->adj_states, w->stream));
+  return RBD_OK;
+}
+
+// v̇ = M⁻¹(τ − c) the reference's way (as rbd_dynamics_jvp), λ = M⁻¹ v̇̄ against the same factor, τ̄ = λ, (q̄, v̄, f̄ext) = −(adjoint RNEA at (q, v, v̇), λ)
+template <typename T>
+int adj_dyn_vjp(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, const void* tau, const void* fext, const void* vdot_bar, void* vdot_out,
+                void* q_bar, void* v_bar, void* tau_bar, void* fext_bar) {
+  const rbd_model* m = w->model;
+  void* vd = vdot_out ? vdot_out : w->d_tan_vd;
+  int st;
+  if ((st = tan_dynamics_value<T>(w, B, layout, q, v, tau, fext, vd))) return st;
+  if (!q_bar && !v_bar && !tau_bar && !fext_bar) return RBD_OK;
+  const Layout Lv = layout_of(layout, m->nv, B), Li{B, 1};
+  const void* rhs = vdot_bar;
+  if (layout != RBD_LAYOUT_SOA) {  // (tri_solve_col reads its right-hand side batch-innermost: SOA as it stands)
+    HIP_TRY(launch_stage_rows<T>(m->nv, B, vdot_bar, Lv, w->d_adj_rhs, w->stream));
+    rhs = w->d_adj_rhs;
+  }
+  // λ straight into τ̄ when the caller asks for it (the adjoint pass reads it from there)
+  const ColOut<T> lam = tau_bar ? ColOut<T>{(T*)tau_bar, Lv, nullptr, Layout{0, 0}, INT32_MAX, m->nv} : ColOut<T>{(T*)w->d_adj_lam, Li, nullptr, Layout{0, 0}, INT32_MAX, m->nv};
+  HIP_TRY(launch_tangent_solve<T>(m->nv, B, 0, 1, w->d_tan_L, Li, rhs, 0, lam, w->d_adj_x, w->stream));
+  if (!q_bar && !v_bar && !fext_bar) return RBD_OK;
+  AdjArgs<T> A = adj_args<T>(w, B, layout, q, v, vd, fext);
+  A.lam = lam.a; A.Llam = lam.La;
+  A.qbar = (T*)q_bar; A.vbar = (T*)v_bar; A.fbar = (T*)fext_bar;
+  A.sign = T(-1);
+  HIP_TRY(launch_adjoint_rnea<T>(w->tan, A, w->d_adj_scratch, w->adj_states, w->stream));
+  return RBD_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -3006,6 +3094,36 @@ int rbd_simulate_step_derivatives(rbd_ws_t* w, int32_t B, void* q, void* v, cons
   return by_dtype(w->dtype, [&](auto t) {
     return sim_tan_run<decltype(t)>(w, B, o.layout, q, v, tau, fext, dt, 1, ncol, true, g0, nullptr, nullptr, nullptr, nullptr, dx_dx, dx_dtau);
   });
+}
+
+int rbd_inverse_dynamics_vjp(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* vdot, const void* fext, const void* tau_bar, void* tau_out,
+                             void* q_bar, void* v_bar, void* vdot_bar, void* fext_bar, const rbd_opts_t* opts) {
+  Opts o;
+  int st = tan_check(w, B, opts, &o);
+  if (st != RBD_OK) return st;
+  const rbd_model* m = w->model;
+  if (missing(q, m->nq) || missing(v, m->nv) || missing(vdot, m->nv) || missing(tau_bar, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0 || m->nv == 0) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  if ((st = adj_ensure(w))) return st;
+  Timed t(w);
+  w->last_kernel = "adjoint_rnea_kernel";
+  return by_dtype(w->dtype, [&](auto t) { return adj_id_vjp<decltype(t)>(w, B, o.layout, q, v, vdot, fext, tau_bar, tau_out, q_bar, v_bar, vdot_bar, fext_bar); });
+}
+
+int rbd_dynamics_vjp(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* tau, const void* fext, const void* vdot_bar, void* vdot_out,
+                     void* q_bar, void* v_bar, void* tau_bar, void* fext_bar, const rbd_opts_t* opts) {
+  Opts o;
+  int st = tan_check(w, B, opts, &o);
+  if (st != RBD_OK) return st;
+  const rbd_model* m = w->model;
+  if (missing(q, m->nq) || missing(v, m->nv) || missing(vdot_bar, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0 || m->nv == 0) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  if ((st = adj_ensure(w))) return st;
+  Timed t(w);
+  w->last_kernel = "tangent_solve_kernel + adjoint_rnea_kernel";
+  return by_dtype(w->dtype, [&](auto t) { return adj_dyn_vjp<decltype(t)>(w, B, o.layout, q, v, tau, fext, vdot_bar, vdot_out, q_bar, v_bar, tau_bar, fext_bar); });
 }
 
 }  // extern "C"

@@ -1,9 +1,11 @@
 // rbd_tangent_kernels.hip — the kernels of the derivative entry points (rbd_inverse_dynamics_jvp, rbd_dynamics_jvp, rbd_inverse_dynamics_derivatives,
-// rbd_dynamics_derivatives, rbd_simulate_jvp, rbd_simulate_step_derivatives): the tangent RNEA (rbd_tangent.hpp) with one thread per (state, chunk of
-// TAN_CHUNK directions), the multi-right-hand-side triangular solve of dynamics! tangents against the Cholesky factor of M, and the tangent of the
-// integrator's stage map (rbd_tangent_mk.hpp) with one thread per (state, joint, chunk).  Compiled with -ffinite-math-only -fno-signed-zeros (build.sh): the zero
+// rbd_dynamics_derivatives, rbd_simulate_jvp, rbd_simulate_step_derivatives, rbd_inverse_dynamics_vjp, rbd_dynamics_vjp): the tangent RNEA (rbd_tangent.hpp)
+// with one thread per (state, chunk of TAN_CHUNK directions), the multi-right-hand-side triangular solve of dynamics! tangents against the Cholesky factor of
+// M, the tangent of the integrator's stage map (rbd_tangent_mk.hpp) with one thread per (state, joint, chunk), and the adjoint RNEA (rbd_adjoint.hpp) with
+// one thread per state.  Compiled with -ffinite-math-only -fno-signed-zeros (build.sh): the zero
 // tangents of the mechanism's constants fold out of the products.
 #include "rbd_tangent.hpp"
+#include "rbd_adjoint.hpp"
 #include "rbd_tangent_mk.hpp"
 #include "rbd_internal.hpp"
 
@@ -188,13 +190,50 @@ hipError_t launch_tangent_mk_load(long B, int ncol, int nq, int nv, int col0, in
   return hipGetLastError();
 }
 
+// ---- reverse mode: the adjoint RNEA, one thread per state ---------------------------------------------------------------------------------------------
+size_t adjoint_scratch_elems_per_state(const BigModel& M) { return (size_t)ADJ_FIELDS * (size_t)M.nb; }
+
+// states s0 … s0 + ns − 1; the scratch holds ns states
+template <typename T>
+__global__ __launch_bounds__(64) void adjoint_rnea_kernel(BigModel M, AdjArgs<T> A, long s0, long ns, T* __restrict__ scratch) {
+  const long slot = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= ns) return;
+  adjoint_rnea_state<T>(M, A, s0 + slot, scratch, ns, slot);
+}
+
+template <typename T> hipError_t launch_adjoint_rnea(const BigModel& M, const AdjArgs<T>& A, void* scratch, long max_states, hipStream_t s) {
+  for (long s0 = 0; s0 < A.B; s0 += max_states) {  // slabs of the scratch's size
+    const long ns = A.B - s0 < max_states ? A.B - s0 : max_states;
+    hipLaunchKernelGGL((adjoint_rnea_kernel<T>), dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, s, M, A, s0, ns, (T*)scratch);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// an n × B batch buffer of layout L copied batch-innermost (row r of state b at r B + b: the right-hand side tri_solve_col reads)
+template <typename T> __global__ __launch_bounds__(256) void stage_rows_kernel(int n, long B, const T* __restrict__ x, Layout L, T* __restrict__ out) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= (long)n * B) return;
+  const long r = e / B, st = e - r * B;
+  out[e] = x[r * L.sk + layout_base(L, st)];
+}
+template <typename T> hipError_t launch_stage_rows(int n, long B, const void* x, Layout L, void* out, hipStream_t s) {
+  const long total = (long)n * B;
+  if (total == 0) return hipSuccess;
+  hipLaunchKernelGGL(stage_rows_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, n, B, (const T*)x, L, (T*)out);
+  return hipGetLastError();
+}
+
 #define RBD_TAN_INST(T)                                                                                                                                    \
   template hipError_t launch_tangent_rnea<T>(const BigModel&, const TanArgs<T>&, void*, long, hipStream_t);                                              \
   template hipError_t launch_tangent_solve<T>(int, long, int, int, const void*, Layout, const void*, int, const ColOut<T>&, void*, hipStream_t);          \
   template hipError_t launch_symmetrize<T>(int, long, void*, Layout, hipStream_t);                                                                   \
   template hipError_t launch_tangent_mk_stage<T>(const MkTanArgs<T>&, hipStream_t);                                                                     \
   template hipError_t launch_tangent_mk_load<T>(long, int, int, int, int, int, const ColOut<T>&, const ColOut<T>&, const ColOut<T>&, const ColOut<T>&,   \
-                                                const ColOut<T>&, const ColOut<T>&, hipStream_t);
+                                                const ColOut<T>&, const ColOut<T>&, hipStream_t);                                                        \
+  template hipError_t launch_adjoint_rnea<T>(const BigModel&, const AdjArgs<T>&, void*, long, hipStream_t);                                              \
+  template hipError_t launch_stage_rows<T>(int, long, const void*, Layout, void*, hipStream_t);
 RBD_TAN_INST(double)
 RBD_TAN_INST(float)
 

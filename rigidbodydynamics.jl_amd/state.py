@@ -600,6 +600,68 @@ def simulate_step_derivatives_(state: MechanismState, dt: float, torques: Option
     return dx_dx, dx_dtau
 
 
+# ---- reverse mode (rbd_*_vjp, header 700 additions): vector-Jacobian products, ONE cotangent per state, in the raw coordinates q as the JVPs above.  The
+# gradient of a scalar loss from one adjoint RNEA pass per state (autograd.py wraps these as torch.autograd.Functions).  Every output is optional and
+# overwritten; `q` / `v` default to the state's own.
+
+def inverse_dynamics_vjp_(state: MechanismState, vd: torch.Tensor, tau_bar: torch.Tensor, q_bar: Optional[torch.Tensor] = None,
+                          v_bar: Optional[torch.Tensor] = None, vd_bar: Optional[torch.Tensor] = None, externalwrenches: Optional[torch.Tensor] = None,
+                          fext_bar: Optional[torch.Tensor] = None, torquesout: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None,
+                          v: Optional[torch.Tensor] = None):
+    """`inverse_dynamics!` pulled back: with λ = tau_bar (B, nv), q_bar = (∂τ/∂q)ᵀλ (B, nq), v_bar = (∂τ/∂v)ᵀλ, vd_bar = Mλ, fext_bar = (∂τ/∂f_ext)ᵀλ
+    (B, 6·n_bodies); `torquesout` receives τ itself."""
+    f = state.flat
+    q = state.q if q is None else q
+    v = state.v if v is None else v
+    if tau_bar is None or vd is None:
+        raise ValueError("vd and tau_bar are required")
+    state._check(q, f.nq, "q")
+    state._check(v, f.nv, "v")
+    state._check(vd, f.nv, "v̇")
+    state._check(tau_bar, f.nv, "tau_bar")
+    state._check(q_bar, f.nq, "q_bar")
+    state._check(v_bar, f.nv, "v_bar")
+    state._check(vd_bar, f.nv, "vd_bar")
+    state._check(externalwrenches, 6 * f.n_bodies, "externalwrenches")
+    state._check(fext_bar, 6 * f.n_bodies, "fext_bar")
+    state._check(torquesout, f.nv, "torquesout")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_inverse_dynamics_vjp(state.ws.handle, state.batch, _ptr(q), _ptr(v), _ptr(vd), _ptr(externalwrenches), _ptr(tau_bar),
+                                              _ptr(torquesout), _ptr(q_bar), _ptr(v_bar), _ptr(vd_bar), _ptr(fext_bar), ctypes.byref(opts))
+    _raise(st, "rbd_inverse_dynamics_vjp")
+    return q_bar, v_bar, vd_bar, fext_bar
+
+
+def dynamics_vjp_(state: MechanismState, vd_bar: torch.Tensor, torques: Optional[torch.Tensor] = None, q_bar: Optional[torch.Tensor] = None,
+                  v_bar: Optional[torch.Tensor] = None, tau_bar: Optional[torch.Tensor] = None, externalwrenches: Optional[torch.Tensor] = None,
+                  fext_bar: Optional[torch.Tensor] = None, vdout: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None,
+                  v: Optional[torch.Tensor] = None):
+    """`dynamics!` pulled back by the implicit-function identity at the v̇ this call computes (the CRBA + Cholesky route): λ = M⁻¹ vd_bar,
+    tau_bar = λ, (q_bar, v_bar, fext_bar) = −(∂ID/∂(q, v, f_ext))ᵀλ; `vdout` receives v̇ itself."""
+    f = state.flat
+    q = state.q if q is None else q
+    v = state.v if v is None else v
+    if vd_bar is None:
+        raise ValueError("vd_bar is required")
+    state._check(q, f.nq, "q")
+    state._check(v, f.nv, "v")
+    state._check(vd_bar, f.nv, "vd_bar")
+    state._check(torques, f.nv, "torques")
+    state._check(q_bar, f.nq, "q_bar")
+    state._check(v_bar, f.nv, "v_bar")
+    state._check(tau_bar, f.nv, "tau_bar")
+    state._check(externalwrenches, 6 * f.n_bodies, "externalwrenches")
+    state._check(fext_bar, 6 * f.n_bodies, "fext_bar")
+    state._check(vdout, f.nv, "vdout")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_dynamics_vjp(state.ws.handle, state.batch, _ptr(q), _ptr(v), _ptr(torques), _ptr(externalwrenches), _ptr(vd_bar), _ptr(vdout),
+                                      _ptr(q_bar), _ptr(v_bar), _ptr(tau_bar), _ptr(fext_bar), ctypes.byref(opts))
+    _raise(st, "rbd_dynamics_vjp")
+    return q_bar, v_bar, tau_bar, fext_bar
+
+
 def jacobian_view(t: torch.Tensor, state: MechanismState, rows: int, cols: int) -> torch.Tensor:
     """A derivative output as (B, rows, cols): a Jacobian (rows × cols, column-major per state: (B, rows·cols), or (rows·cols, B) with layout="soa"), or a
     tangent output of `cols` directions of `rows` coordinates (direction d = column d).  A view when the layout allows, else a copy."""
