@@ -457,6 +457,19 @@ int rbd_inverse_dynamics_vjp(rbd_ws_t* ws, int32_t B, const void* q, const void*
 int rbd_dynamics_vjp(rbd_ws_t* ws, int32_t B, const void* q, const void* v, const void* tau, const void* fext,
                      const void* vdot_bar, void* vdot_out, void* q_bar, void* v_bar, void* tau_bar, void* fext_bar,
                      const rbd_opts_t* opts);
+/* rbd_simulate_vjp (700 addition): reverse mode through nsteps steps of rbd_simulate_jvp's integrator — the gradient of a scalar loss of the final state,
+ * one cotangent per state, from a forward pass that keeps the step starts and a backward pass of four dynamics VJPs and stage-map pullbacks per step.
+ *  - q, v: IN/OUT, advanced by nsteps as rbd_simulate_jvp does (the CRBA + Cholesky value route at every stage: rbd_simulate's state to rounding).
+ *  - q_bar (nq), v_bar (nv): IN/OUT — the cotangent of the final (q, v) on entry, that of the initial (q, v) on return.
+ *  - tau_bar (nv), fext_bar (6·n_bodies): nullable, OVERWRITTEN with the gradient in the held τ / fext, summed over every stage of every step.
+ *  - Semantics as the other derivative entry points (raw coordinates, tree mechanisms only, RBD_ERR_UNSUPPORTED for contact points with an environment
+ *    and for RBD_MEM_HOST, device pointers, fp32 and fp64, both layouts); dt <= 0, nsteps < 0 or a NULL q, v, q_bar or v_bar:
+ *    RBD_ERR_INVALID_ARGUMENT; B == 0 is a no-op; nsteps == 0 leaves q, v, q_bar, v_bar and zeroes tau_bar / fext_bar.
+ *  - Step starts are kept while nsteps·(nq + nv)·B values fit in 1 GiB, else every ⌈√nsteps⌉-th, one segment's others recomputed (two-level
+ *    checkpointing).  The first call of a workspace allocates, and a call that needs more room for step starts than any before; nothing else does.
+ *  - Per-step torques: one call per step (the cotangent chains through q_bar, v_bar). */
+int rbd_simulate_vjp(rbd_ws_t* ws, int32_t B, void* q, void* v, const void* tau, const void* fext, double dt, int32_t nsteps,
+                     void* q_bar, void* v_bar, void* tau_bar, void* fext_bar, const rbd_opts_t* opts);
 
 /* ---- diagnostics ------------------------------------------------------------ */
 const char* rbd_status_string(int status);
@@ -473,7 +486,7 @@ const char* rbd_workspace_last_kernel(const rbd_ws_t* ws);
  * 500: rbd_mass_matrix_solve_packed, rbd_gatherv.  600: rbd_jit_check_walk_object; no size limit left on any entry point; program family 11; family 1 in fp64.
  * 700: forward-mode derivatives — rbd_inverse_dynamics_jvp, rbd_dynamics_jvp, rbd_inverse_dynamics_derivatives, rbd_dynamics_derivatives;
  *      added to 700 without a new version: rbd_simulate_jvp, rbd_simulate_step_derivatives (derivatives of simulate steps);
- *      rbd_inverse_dynamics_vjp, rbd_dynamics_vjp (reverse mode). */
+ *      rbd_inverse_dynamics_vjp, rbd_dynamics_vjp (reverse mode); rbd_simulate_vjp (reverse mode through simulate steps). */
 #define RBD_HIP_H_VERSION 700
 int rbd_version(void);
 /* Run-time specialisation.  The one-lane-per-state kernels (mass_matrix! and mass_matrix! + Cholesky at large batches) exist in a second form

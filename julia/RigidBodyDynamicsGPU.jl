@@ -30,7 +30,7 @@ using LinearAlgebra
 
 export BatchedMechanismState, BatchedDynamicsResult, DeviceMatrix, RbdComm, gather!, gatherv!, mass_matrix_solve_packed!, synchronize, librbd_hip, TorqueTable, PDControl,
     inverse_dynamics_jvp!, dynamics_jvp!, inverse_dynamics_derivatives!, dynamics_derivatives!, simulate_jvp!, simulate_step_derivatives!,
-    inverse_dynamics_vjp!, dynamics_vjp!
+    inverse_dynamics_vjp!, dynamics_vjp!, simulate_vjp!
 
 const librbd_hip = Ref("librbd_hip.so")   # set to <repo>/rigidbodydynamics.jl_amd/csrc/librbd_hip.so
 const libhip = Ref("libamdhip64.so")
@@ -565,6 +565,26 @@ function dynamics_vjp!(q̄, v̄, τ̄, state::BatchedMechanismState{T}, v̇̄::B
         (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
         state.ws, B, state.q, state.v, nullable(torques), nullable(densewrenches(state, externalwrenches)), v̇̄, nullable(v̇out), nullable(q̄), nullable(v̄),
         nullable(τ̄), nullable(f̄ext), opts(state)), "rbd_dynamics_vjp")
+    finish(state)
+    q̄, v̄, τ̄
+end
+
+"""`simulate_vjp!(q̄, v̄, state, Δt; nsteps = 1, torques, externalwrenches, τ̄, f̄ext)` — `nsteps` Munthe-Kaas RK4 steps of `simulate` pulled back
+(`state` advanced in place, as `simulate_jvp!`): q̄ (nq × B), v̄ (nv × B) hold the cotangent of the final state on entry and that of the initial state on
+return; τ̄, f̄ext (each may be `nothing`) are overwritten with the gradient in the held torques / wrenches over every stage (`rbd_simulate_vjp`)."""
+function simulate_vjp!(q̄::Buffer{T}, v̄::Buffer{T}, state::BatchedMechanismState{T}, Δt::Real; nsteps::Integer = 1, torques = nothing,
+        externalwrenches = nothing, τ̄ = nothing, f̄ext = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, B = state.model.nq, state.model.nv, batchsize(state)
+    Δt > 0 || throw(ArgumentError("Δt must be positive"))
+    nsteps >= 0 || throw(ArgumentError("nsteps must be non-negative"))
+    for (x, n) in ((q̄, nq), (v̄, nv), (τ̄, nv))
+        x === nothing || size(x) == (n, B) || throw(DimensionMismatch("cotangent buffer has wrong size"))
+    end
+    check(ccall((:rbd_simulate_vjp, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Cdouble, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, state.q, state.v, nullable(torques), nullable(densewrenches(state, externalwrenches)), Float64(Δt), Int32(nsteps), q̄, v̄,
+        nullable(τ̄), nullable(f̄ext), opts(state)), "rbd_simulate_vjp")
     finish(state)
     q̄, v̄, τ̄
 end

@@ -27,6 +27,7 @@ SYMBOLS = (
     "rbd_inverse_dynamics_jvp", "rbd_dynamics_jvp", "rbd_inverse_dynamics_derivatives", "rbd_dynamics_derivatives",
     "rbd_simulate_jvp", "rbd_simulate_step_derivatives",
     "rbd_inverse_dynamics_vjp", "rbd_dynamics_vjp",
+    "rbd_simulate_vjp",
 )
 
 
@@ -91,6 +92,7 @@ def lib():
         L.rbd_simulate_step_derivatives.argtypes = [vp, i32, vp, vp, vp, vp, ctypes.c_double, vp, vp, ctypes.POINTER(Opts)]
         L.rbd_inverse_dynamics_vjp.argtypes = [vp, i32] + [vp] * 10 + [ctypes.POINTER(Opts)]
         L.rbd_dynamics_vjp.argtypes = [vp, i32] + [vp] * 10 + [ctypes.POINTER(Opts)]
+        L.rbd_simulate_vjp.argtypes = [vp, i32, vp, vp, vp, vp, ctypes.c_double, i32, vp, vp, vp, vp, ctypes.POINTER(Opts)]
         L.rbd_model_chain_plan.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), i32]
         L.rbd_model_track_plan.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(ctypes.c_double), i32]
         L.rbd_comm_unique_id.argtypes = [vp]

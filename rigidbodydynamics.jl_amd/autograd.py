@@ -1,12 +1,12 @@
-"""torch.autograd through the library: `tau = inverse_dynamics(state, q, v, vd, fext)` and `vd = dynamics(state, q, v, tau, fext)` are differentiable
-functions of their tensor arguments, so `loss.backward()` (reverse mode) and `torch.func.jvp` / `torch.autograd.forward_ad` (forward mode) work through
+"""torch.autograd through the library: `tau = inverse_dynamics(state, q, v, vd, fext)`, `vd = dynamics(state, q, v, tau, fext)` and
+`q1, v1 = simulate(state, q, v, tau, fext, dt=, nsteps=)` are differentiable functions of their tensor arguments, so `loss.backward()` (reverse mode) and `torch.func.jvp` / `torch.autograd.forward_ad` (forward mode) work through
 them.
 
   - `state` (a MechanismState) supplies the workspace, the batch, the dtype and the layout; q, v, … are tensors of that layout ((B, n) with "aos",
     (n, B) with "soa"); `state.q` / `state.v` are neither read nor written.
   - The forward pass is the library's normal call (rbd_inverse_dynamics / rbd_dynamics), so the value stays on the fast routes.
-  - backward is one vector-Jacobian product per call (rbd_inverse_dynamics_vjp / rbd_dynamics_vjp) on the current torch stream; forward-mode AD is one
-    JVP with one direction (rbd_inverse_dynamics_jvp / rbd_dynamics_jvp).
+  - backward is one vector-Jacobian product per call (rbd_inverse_dynamics_vjp / rbd_dynamics_vjp / rbd_simulate_vjp) on the current torch stream;
+    forward-mode AD is one JVP with one direction (rbd_inverse_dynamics_jvp / rbd_dynamics_jvp / rbd_simulate_jvp).
   - The derivatives are those of the raw coordinates q (a quaternion joint's unnormalised rotation formula; a SinCosRevolute's (s, c) as two
     coordinates), as every derivative entry point of the library.
   - Double backward is not supported (once_differentiable)."""
@@ -19,7 +19,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _capi
-from .state import MechanismState, _ptr, _raise, dynamics_vjp_, inverse_dynamics_vjp_
+from .state import MechanismState, _ptr, _raise, dynamics_vjp_, inverse_dynamics_vjp_, simulate_vjp_
 
 
 def _prep(state: MechanismState, t: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
@@ -120,6 +120,54 @@ class _Dynamics(torch.autograd.Function):
         return dvd
 
 
+class _Simulate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, state, q, v, tau, fext, dt, nsteps):
+        f = state.flat
+        q, v, tau = _prep(state, q, f.nq, "q"), _prep(state, v, f.nv, "v"), _prep(state, tau, f.nv, "torques")
+        fext = _prep(state, fext, 6 * f.n_bodies, "externalwrenches")
+        q1, v1 = q.clone(), v.clone()
+        state.ws.use_current_stream()
+        opts = state._opts()
+        _raise(_capi.lib().rbd_simulate(state.ws.handle, state.batch, _ptr(q1), _ptr(v1), _ptr(tau), _ptr(fext), ctypes.c_double(dt), int(nsteps),
+                                        ctypes.byref(opts)), "rbd_simulate")
+        ctx.state, ctx.dt, ctx.nsteps = state, float(dt), int(nsteps)
+        ctx.save_for_backward(q, v, tau, fext)
+        ctx.save_for_forward(q, v, tau, fext)
+        return q1, v1
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, q1_bar, v1_bar):
+        state, f = ctx.state, ctx.state.flat
+        q, v, tau, fext = ctx.saved_tensors
+        _, nq_, nv_, nt_, nf_, _, _ = ctx.needs_input_grad
+        if not (nq_ or nv_ or nt_ or nf_):
+            return (None,) * 7
+        # (the steps run again from the saved inputs, on copies: the library advances q, v in place)
+        qs, vs = q.clone(), v.clone()
+        qb = _prep(state, q1_bar, f.nq, "q_bar").clone() if q1_bar is not None else torch.zeros_like(q)
+        vb = _prep(state, v1_bar, f.nv, "v_bar").clone() if v1_bar is not None else torch.zeros_like(v)
+        tb, fb = _empty(state, f.nv, nt_ and tau is not None), _empty(state, 6 * f.n_bodies, nf_ and fext is not None)
+        simulate_vjp_(qb, vb, state, ctx.dt, ctx.nsteps, torques=tau, externalwrenches=fext, tau_bar=tb, fext_bar=fb, q=qs, v=vs)
+        return None, qb if nq_ else None, vb if nv_ else None, tb, fb, None, None
+
+    @staticmethod
+    def jvp(ctx, _dstate, dq, dv, dtau, dfext, _ddt, _dnsteps):
+        state, f = ctx.state, ctx.state.flat
+        q, v, tau, fext = ctx.saved_tensors
+        qs, vs = q.clone(), v.clone()
+        dq = _prep(state, dq, f.nq, "dq").clone() if dq is not None else torch.zeros_like(q)
+        dv = _prep(state, dv, f.nv, "dv").clone() if dv is not None else torch.zeros_like(v)
+        dtau = _prep(state, dtau, f.nv, "dτ") if tau is not None else None
+        dfext = _prep(state, dfext, 6 * f.n_bodies, "dexternalwrenches") if fext is not None else None
+        state.ws.use_current_stream()
+        opts = state._opts()
+        _raise(_capi.lib().rbd_simulate_jvp(state.ws.handle, state.batch, 1, _ptr(qs), _ptr(vs), _ptr(tau), _ptr(fext), ctypes.c_double(ctx.dt), ctx.nsteps,
+                                            _ptr(dq), _ptr(dv), _ptr(dtau), _ptr(dfext), ctypes.byref(opts)), "rbd_simulate_jvp")
+        return dq, dv
+
+
 def inverse_dynamics(state: MechanismState, q: torch.Tensor, v: torch.Tensor, vd: torch.Tensor, fext: Optional[torch.Tensor] = None) -> torch.Tensor:
     """τ = inverse_dynamics!(q, v, v̇, f_ext), differentiable in q, v, vd and fext (None: no external wrenches)."""
     return _InverseDynamics.apply(state, q, v, vd, fext)
@@ -133,3 +181,18 @@ def dynamics(state: MechanismState, q: torch.Tensor, v: torch.Tensor, tau: Optio
     In the raw coordinates OFF the unit sphere of a quaternion (or circle of a SinCosRevolute's (s, c)) the two routes are different functions of q; the
     derivatives there are the CRBA route's, so finite differences of raw q off the sphere match algorithm="crba"."""
     return _Dynamics.apply(state, q, v, tau, fext, algorithm)
+
+
+def simulate(state: MechanismState, q: torch.Tensor, v: torch.Tensor, tau: Optional[torch.Tensor] = None, fext: Optional[torch.Tensor] = None,
+             dt: float = 1e-4, nsteps: int = 1):
+    """(q⁺, v⁺) after `nsteps` Munthe-Kaas RK4 steps of `simulate` with the torques `tau` and wrenches `fext` held (None: zero / none), differentiable
+    in q, v, tau and fext.  The value is rbd_simulate's (on copies: q and v are not modified); backward runs the steps again from the saved inputs
+    through rbd_simulate_vjp, forward-mode AD is one rbd_simulate_jvp direction.  The derivatives are those of the steps with dynamics! on the CRBA +
+    Cholesky route at every stage (as `dynamics(..., algorithm="crba")`), which equal the articulated-body value's to rounding on the unit sphere of
+    each quaternion; off it, the two routes are different functions of the raw q and finite differences match the CRBA route.
+    Per-step controls (backpropagation through time): call this once per step with that step's tau; torch's saved tensors are then the checkpoints."""
+    if not float(dt) > 0:
+        raise ValueError("dt must be positive")
+    if int(nsteps) < 0:
+        raise ValueError("nsteps must be non-negative")
+    return _Simulate.apply(state, q, v, tau, fext, float(dt), int(nsteps))

@@ -29,6 +29,8 @@ template <typename T> struct AdjArgs {
   T* tau;                            // value of τ (nullable)
   T *qbar, *vbar, *vdbar, *fbar;     // pullbacks times `sign` (each nullable), layouts Lq, Lv, Lv, Lf; overwritten
   T sign;                            // dynamics!: −1 (the implicit-function identity)
+  int accum;                         // 1: ADD to qbar, vbar, vdbar, fbar instead of overwriting them (rbd_simulate_vjp sums over stages)
+  T* lbar;                           // nullable: λ is added here (Lv; rbd_simulate_vjp's τ̄)
 };
 
 // ---- adjoints of the spatial primitives (rbd_device.hpp): given the output's adjoint ō, ADD the inputs' adjoints ----------------------------------------
@@ -281,6 +283,8 @@ template <typename T> RBD_HD void adjoint_rnea_state(const BigModel& M, const Ad
     const int nvi = joint_nv(b.jtype);
     T lj[6], m[6], K[24], W[6], Wb[6], Kb[24];
     load_v(A.lam, A.Llam, b.voff, nvi, lj);
+    if (A.lbar)
+      for (int k = 0; k < nvi; ++k) A.lbar[(long)(b.voff + k) * A.Lv.sk + layout_base(A.Lv, st)] += lj[k];
     local_joint_motion(b, rb, lj, m);
 #pragma unroll
     for (int k = 0; k < 24; ++k) { K[k] = at(ADJ_K + k, i); Kb[k] = T(0); }
@@ -294,7 +298,10 @@ template <typename T> RBD_HD void adjoint_rnea_state(const BigModel& M, const Ad
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
       at(ADJ_WB + k, i) = Wb[k];
-      if (A.fbar) A.fbar[(long)(6 * i + k) * A.Lf.sk + layout_base(A.Lf, st)] = -A.sign * Wb[k];
+      if (A.fbar) {
+        T& o = A.fbar[(long)(6 * i + k) * A.Lf.sk + layout_base(A.Lf, st)];
+        o = A.accum ? o - A.sign * Wb[k] : -A.sign * Wb[k];
+      }
     }
     xmotion_adj(K, K + 9, m, W, Kb, Kb + 9, (T*)nullptr);
     newton_euler_adj(rb, K, Wb, Kb);
@@ -362,7 +369,10 @@ template <typename T> RBD_HD void adjoint_rnea_state(const BigModel& M, const Ad
       }
 #pragma unroll
       for (int k = 0; k < 7; ++k)
-        if (k < nqi) A.qbar[(long)(b.qoff + k) * A.Lq.sk + layout_base(A.Lq, st)] = A.sign * qb[k];
+        if (k < nqi) {
+          T& o = A.qbar[(long)(b.qoff + k) * A.Lq.sk + layout_base(A.Lq, st)];
+          o = A.accum ? o + A.sign * qb[k] : A.sign * qb[k];
+        }
     }
     if (A.vbar || A.vdbar) {
       const T ax[3] = {rb[RB_AXIS], rb[RB_AXIS + 1], rb[RB_AXIS + 2]}, ay[3] = {rb[RB_AXIS2], rb[RB_AXIS2 + 1], rb[RB_AXIS2 + 2]};
@@ -370,8 +380,8 @@ template <typename T> RBD_HD void adjoint_rnea_state(const BigModel& M, const Ad
         T sl[6];
         subspace_col(b.jtype, ax, ay, k, sl);
         const long o = (long)(b.voff + k) * A.Lv.sk + layout_base(A.Lv, st);
-        if (A.vbar) A.vbar[o] = A.sign * dot6(sl, tlb);
-        if (A.vdbar) A.vdbar[o] = A.sign * dot6(sl, alb);
+        if (A.vbar) A.vbar[o] = A.accum ? A.vbar[o] + A.sign * dot6(sl, tlb) : A.sign * dot6(sl, tlb);
+        if (A.vdbar) A.vdbar[o] = A.accum ? A.vdbar[o] + A.sign * dot6(sl, alb) : A.sign * dot6(sl, alb);
       }
     }
   }

@@ -27,6 +27,7 @@
 #include "rbd_tangent.hpp"
 #include "rbd_tangent_mk.hpp"
 #include "rbd_adjoint.hpp"
+#include "rbd_adjoint_mk.hpp"
 enum { BANK_LDS_PAIRS_HOST = 30 };  // = BANK_LDS_PAIRS of rbd_bank.hpp (16 parked + 14 exchange pairs per lane; checked in rbd_bank_kernels.hip)
 
 using namespace rbd;
@@ -199,6 +200,10 @@ struct rbd_ws {
   bool adj_ready = false; long adj_states = 0;
   void* d_adj_scratch = nullptr; void* d_adj_rhs = nullptr; void* d_adj_lam = nullptr; void* d_adj_x = nullptr;
   size_t d_adj_scratch_bytes = 0, d_adj_rhs_bytes = 0, d_adj_lam_bytes = 0, d_adj_x_bytes = 0;
+  // rbd_simulate_vjp: the joints by class (1-coordinate / the rest, (jtype, qoff, voff) each), the stage states of one step and the cotangents of the
+  // backward pass (d_sav), and the step starts kept (d_sav_ckpt, sav_ckpt_bytes)
+  bool sav_ready = false; int sav_nn = 0, sav_nw = 0;
+  void* d_sav_joints = nullptr; void* d_sav = nullptr; void* d_sav_ckpt = nullptr; size_t d_sav_bytes = 0, d_sav_ckpt_bytes = 0;
 };
 
 // RBD_TUNE="key=value,key=value,...": the developer knobs of the tests and sweep scripts in ONE environment variable (batch thresholds between the lane
@@ -1091,7 +1096,7 @@ int rbd_workspace_destroy(rbd_ws_t* w) {
   (void)hipSetDevice(w->device);
   void* ptrs[] = {w->d_big_L, w->d_big_tbl, w->d_big_rb, w->d_big_scratch, w->d_fused_i, w->d_tauwork, w->d_rr_chain_i, w->d_rr_chain_r, w->d_rrtrack_ri, w->d_rrtrack_rr, w->d_rrwalk_wk, w->d_cp_body, w->d_cp_r, w->d_hs_r, w->d_tw, w->d_cw, w->d_s0, w->d_sacc, w->d_sdot, w->d_rows, w->d_walk_wk, w->d_state_ops, w->d_state_cols, w->d_state_sr, w->d_Msoa, w->d_track_ri, w->d_track_rr, w->d_bank_ib[0], w->d_bank_ib[1], w->d_bank_rb[0], w->d_bank_rb[1], w->d_ib, w->d_rb, w->d_nslots, w->d_dof_body, w->d_anc, w->d_row_mask, w->d_M, w->d_c, w->d_K, w->d_k, (void*)w->d_notpd, w->d_body, w->d_scratch, w->d_loop_i, w->d_loop_r, w->d_loop_path, w->d_jt_ref, w->d_voff_ref, w->d_axis_ref, w->d_axis2_ref,
                   w->d_tan_tbl, w->d_tan_rb, w->d_tan_scratch, w->d_tan_M, w->d_tan_L, w->d_tan_c, w->d_tan_vd, w->d_tan_rhs, w->d_tan_x,
-                  w->d_sim_val, w->d_sim_tan, w->d_adj_scratch, w->d_adj_rhs, w->d_adj_lam, w->d_adj_x};
+                  w->d_sim_val, w->d_sim_tan, w->d_adj_scratch, w->d_adj_rhs, w->d_adj_lam, w->d_adj_x, w->d_sav_joints, w->d_sav, w->d_sav_ckpt};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (void* p : w->stage) if (p) (void)hipFree(p);
   {
@@ -2641,6 +2646,7 @@ template <typename T> hipError_t launch_tangent_mk_stage(const MkTanArgs<T>& A, 
 size_t adjoint_scratch_elems_per_state(const BigModel& M);
 template <typename T> hipError_t launch_adjoint_rnea(const BigModel& M, const AdjArgs<T>& A, void* scratch, long max_states, hipStream_t s);
 template <typename T> hipError_t launch_stage_rows(int n, long B, const void* x, Layout L, void* out, hipStream_t s);
+template <typename T> hipError_t launch_mk_stage_classes(MkAdjArgs<T> A, const int32_t* jn, int nn, const int32_t* jw, int nw, int adjoint, hipStream_t s);
 template <typename T>
 hipError_t launch_tangent_mk_load(long B, int ncol, int nq, int nv, int col0, int unit, const ColOut<T>& sq, const ColOut<T>& sv, const ColOut<T>& sd,
                                   const ColOut<T>& dq, const ColOut<T>& dv, const ColOut<T>& dd, hipStream_t s);
@@ -2995,6 +3001,159 @@ int adj_dyn_vjp(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, 
   HIP_TRY(launch_adjoint_rnea<T>(w->tan, A, w->d_adj_scratch, w->adj_states, w->stream));
   return RBD_OK;
 }
+
+// ---- reverse mode through simulate steps (header 700 addition): rbd_simulate_vjp ----------------------------------------------------------------------
+enum : long { SAV_CKPT_CAP = 1L << 30 };  // bytes of step starts kept while every step's fits; beyond that two-level (√n) checkpointing
+
+// the first call of a workspace allocates the joint lists, one step's stage states and the backward pass's cotangents (for max_batch states)
+int sav_ensure(rbd_ws* w) {
+  const rbd_model* m = w->model;
+  const size_t es = esize(w), B = (size_t)w->max_batch;
+  int st;
+  if ((st = adj_ensure(w))) return st;
+  if (w->sav_ready) return RBD_OK;
+  std::vector<int32_t> jl;  // the 1-coordinate joints first (adjoint_mk_stage_kernel<T, false>), then the rest
+  int nn = 0, nw = 0;
+  for (int wide = 0; wide < 2; ++wide)
+    for (int i = 0; i < m->nb; ++i) {
+      const int jt = m->jt_ref[i];
+      if (jt == RBD_JOINT_FIXED || mk_narrow_joint(jt) == (wide == 1)) continue;
+      jl.insert(jl.end(), {jt, m->qoff_ref[i], m->voff_ref[i]});
+      ++(wide ? nw : nn);
+    }
+  if ((st = upload(&w->d_sav_joints, jl.data(), jl.size() * sizeof(int32_t)))) return st;
+  // stage states 1-3 (q, v), the running sums (2 nv), the base point's cotangent (nq + nv), v̇̄ and the sums' cotangents (3 nv)
+  if ((st = ensure(&w->d_sav, &w->d_sav_bytes, es * B * (4 * (size_t)m->nq + 9 * (size_t)m->nv)))) return st;
+  w->sav_nn = nn; w->sav_nw = nw;
+  w->sav_ready = true;
+  return RBD_OK;
+}
+
+// which step starts are kept: all (S = 1, K = nsteps slots), or every S-th in slots 0 … K − 1 and one segment's others, recomputed, in K … K + S − 2.
+// RBD_TUNE sim_vjp_ckpt_steps=<k>: room for k starts instead of the byte cap (tests reach the recompute path at small sizes).
+struct SavPlan { int S, K, slots; };
+SavPlan sav_plan(size_t slot_bytes, int nsteps) {
+  bool has;
+  const long knob = tune("sim_vjp_ckpt_steps", 0, &has);
+  const long room = has ? std::max(1L, knob) : std::max<long>(1, (long)(SAV_CKPT_CAP / std::max<size_t>(1, slot_bytes)));
+  if (nsteps <= room) return {1, nsteps, nsteps};
+  const int S = (int)std::ceil(std::sqrt((double)nsteps)), K = (nsteps + S - 1) / S;
+  return {S, K, K + S - 1};
+}
+
+template <typename T> struct SavBufs {
+  T *qs[3], *vs[3], *accp, *accv, *q0b, *v0b, *vdb, *apb, *avb;
+};
+template <typename T> SavBufs<T> sav_bufs(rbd_ws* w) {
+  const long nq = w->model->nq, nv = w->model->nv, Bm = w->max_batch;
+  T* p = (T*)w->d_sav;
+  SavBufs<T> b;
+  for (int i = 0; i < 3; ++i) { b.qs[i] = p; p += nq * Bm; b.vs[i] = p; p += nv * Bm; }
+  b.accp = p; p += nv * Bm; b.accv = p; p += nv * Bm;
+  b.q0b = p; p += nq * Bm; b.v0b = p; p += nv * Bm;
+  b.vdb = p; p += nv * Bm; b.apb = p; p += nv * Bm; b.avb = p;
+  return b;
+}
+
+template <typename T> MkAdjArgs<T> sav_args(rbd_ws* w, int32_t B, int layout, double dt, int stage) {
+  MkAdjArgs<T> A{};
+  A.B = B; A.stage = stage; A.dt = (T)dt;
+  A.Lq = layout_of(layout, w->model->nq, B); A.Lv = layout_of(layout, w->model->nv, B);
+  A.Lqb = A.Lq; A.Lvb = A.Lv;
+  return A;
+}
+
+// stages 0 … last of one step from (q0, v0), values only (the route of sim_tan_run: dynamics! by CRBA + Cholesky at every stage state, then the stage
+// map): the stage states 1-3 and the running sums into the workspace, the state after the step (last = 3) into (qout, vout), which may be (q0, v0).
+template <typename T>
+int sav_value_step(rbd_ws* w, int32_t B, int layout, const T* q0, const T* v0, const void* tau, const void* fext, double dt, int last, T* qout, T* vout) {
+  const SavBufs<T> b = sav_bufs<T>(w);
+  const int32_t* jl = (const int32_t*)w->d_sav_joints;
+  for (int stage = 0; stage <= last; ++stage) {
+    const T* qs = stage == 0 ? q0 : b.qs[stage - 1];
+    const T* vs = stage == 0 ? v0 : b.vs[stage - 1];
+    int st;
+    if ((st = tan_dynamics_value<T>(w, B, layout, qs, vs, tau, fext, w->d_tan_vd))) return st;
+    MkAdjArgs<T> A = sav_args<T>(w, B, layout, dt, stage);
+    A.q0 = q0; A.v0 = v0; A.qs = qs; A.vs = vs; A.vd = (const T*)w->d_tan_vd; A.accp = b.accp; A.accv = b.accv;
+    A.qn = stage == 3 ? qout : b.qs[stage]; A.vn = stage == 3 ? vout : b.vs[stage];
+    HIP_TRY(launch_mk_stage_classes<T>(A, jl, w->sav_nn, jl + 3 * w->sav_nn, w->sav_nw, 0, w->stream));
+  }
+  return RBD_OK;
+}
+
+// One step pulled back: (q_bar, v_bar) hold the cotangent of the state after the step on entry and that of (q0, v0) on return; τ̄ and f̄ext accumulate.
+// Stages 3 … 0: the stage map's pullback (v̇̄_i, the stage state's cotangent, the base point's), λ_i = M_i⁻¹ v̇̄_i, then the adjoint RNEA at the stage state
+// with sign −1 ADDING −(∂ID)ᵀλ_i to the stage state's cotangent and f̄ext, and λ_i to τ̄.  `fresh`: the stage states, the sums and stage 3's factor and v̇
+// are this step's already (the forward pass's last step).
+template <typename T>
+int sav_backward_step(rbd_ws* w, int32_t B, int layout, const T* q0, const T* v0, const void* tau, const void* fext, double dt, bool fresh, void* q_bar,
+                      void* v_bar, void* tau_bar, void* fext_bar) {
+  const rbd_model* m = w->model;
+  const SavBufs<T> b = sav_bufs<T>(w);
+  const int32_t* jl = (const int32_t*)w->d_sav_joints;
+  const Layout Li{B, 1};
+  int st;
+  if (!fresh && (st = sav_value_step<T>(w, B, layout, q0, v0, tau, fext, dt, 2, nullptr, nullptr))) return st;
+  for (int stage = 3; stage >= 0; --stage) {
+    const T* qs = stage == 0 ? q0 : b.qs[stage - 1];
+    const T* vs = stage == 0 ? v0 : b.vs[stage - 1];
+    if (!(fresh && stage == 3) && (st = tan_dynamics_value<T>(w, B, layout, qs, vs, tau, fext, w->d_tan_vd))) return st;
+    MkAdjArgs<T> S = sav_args<T>(w, B, layout, dt, stage);
+    S.q0 = q0; S.qs = qs; S.vs = vs; S.accp = b.accp;
+    S.qsb = (T*)q_bar; S.vsb = (T*)v_bar; S.q0b = b.q0b; S.v0b = b.v0b; S.vdb = b.vdb; S.apb = b.apb; S.avb = b.avb;
+    HIP_TRY(launch_mk_stage_classes<T>(S, jl, w->sav_nn, jl + 3 * w->sav_nn, w->sav_nw, 1, w->stream));
+    const ColOut<T> lam{(T*)w->d_adj_lam, Li, nullptr, Layout{0, 0}, INT32_MAX, m->nv};
+    HIP_TRY(launch_tangent_solve<T>(m->nv, B, 0, 1, w->d_tan_L, Li, b.vdb, 0, lam, w->d_adj_x, w->stream));
+    AdjArgs<T> A = adj_args<T>(w, B, layout, qs, vs, w->d_tan_vd, fext);
+    A.lam = lam.a; A.Llam = Li;
+    A.qbar = (T*)q_bar; A.vbar = (T*)v_bar; A.fbar = (T*)fext_bar; A.lbar = (T*)tau_bar;
+    A.sign = T(-1); A.accum = 1;
+    HIP_TRY(launch_adjoint_rnea<T>(w->tan, A, w->d_adj_scratch, w->adj_states, w->stream));
+  }
+  return RBD_OK;
+}
+
+// nsteps steps forward (the step starts kept as `P` says; q, v advanced in place), then backward from the last step to the first
+template <typename T>
+int sav_run(rbd_ws* w, int32_t B, int layout, void* q, void* v, const void* tau, const void* fext, double dt, int nsteps, SavPlan P, void* q_bar, void* v_bar,
+            void* tau_bar, void* fext_bar) {
+  const rbd_model* m = w->model;
+  const long nq = m->nq, nv = m->nv, slot = (nq + nv) * B;
+  const size_t es = sizeof(T);
+  T* ck = (T*)w->d_sav_ckpt;
+  auto cq = [&](int i) { return ck + i * slot; };
+  auto cv = [&](int i) { return ck + i * slot + nq * B; };
+  auto keep = [&](int i, const void* qf, const void* vf) -> hipError_t {
+    hipError_t e = hipMemcpyAsync(cq(i), qf, es * nq * B, hipMemcpyDeviceToDevice, w->stream);
+    return e != hipSuccess ? e : hipMemcpyAsync(cv(i), vf, es * nv * B, hipMemcpyDeviceToDevice, w->stream);
+  };
+  int st;
+  if (P.S == 1) {  // every start kept: step s from slot s into slot s + 1 (the last into (q, v))
+    HIP_TRY(keep(0, q, v));
+    for (int s = 0; s < nsteps; ++s) {
+      const bool last = s == nsteps - 1;
+      if ((st = sav_value_step<T>(w, B, layout, cq(s), cv(s), tau, fext, dt, 3, last ? (T*)q : cq(s + 1), last ? (T*)v : cv(s + 1)))) return st;
+    }
+  } else {  // every S-th start kept, (q, v) stepped in place
+    for (int s = 0; s < nsteps; ++s) {
+      if (s % P.S == 0) HIP_TRY(keep(s / P.S, q, v));
+      if ((st = sav_value_step<T>(w, B, layout, (T*)q, (T*)v, tau, fext, dt, 3, (T*)q, (T*)v))) return st;
+    }
+  }
+  bool fresh = P.S == 1;  // (the forward pass's last step left its stage states, sums and stage-3 factor)
+  for (int g = P.K - 1; g >= 0; --g) {
+    const int s0 = g * P.S, n = std::min(P.S, nsteps - s0);
+    auto start = [&](int j) { return j == 0 ? g : P.K + j - 1; };  // (the slot of step s0 + j's start)
+    for (int j = 1; j < n; ++j)  // the segment's starts recomputed from its kept one
+      if ((st = sav_value_step<T>(w, B, layout, cq(start(j - 1)), cv(start(j - 1)), tau, fext, dt, 3, cq(start(j)), cv(start(j))))) return st;
+    for (int j = n - 1; j >= 0; --j) {
+      if ((st = sav_backward_step<T>(w, B, layout, cq(start(j)), cv(start(j)), tau, fext, dt, fresh, q_bar, v_bar, tau_bar, fext_bar))) return st;
+      fresh = false;
+    }
+  }
+  return RBD_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -3124,6 +3283,29 @@ int rbd_dynamics_vjp(rbd_ws_t* w, int32_t B, const void* q, const void* v, const
   Timed t(w);
   w->last_kernel = "tangent_solve_kernel + adjoint_rnea_kernel";
   return by_dtype(w->dtype, [&](auto t) { return adj_dyn_vjp<decltype(t)>(w, B, o.layout, q, v, tau, fext, vdot_bar, vdot_out, q_bar, v_bar, tau_bar, fext_bar); });
+}
+
+int rbd_simulate_vjp(rbd_ws_t* w, int32_t B, void* q, void* v, const void* tau, const void* fext, double dt, int32_t nsteps, void* q_bar, void* v_bar,
+                     void* tau_bar, void* fext_bar, const rbd_opts_t* opts) {
+  Opts o;
+  int st = tan_check(w, B, opts, &o);
+  if (st != RBD_OK) return st;
+  if (!(dt > 0) || nsteps < 0 || !q || !v || !q_bar || !v_bar) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0) return RBD_OK;
+  const rbd_model* m = w->model;
+  const size_t es = esize(w);
+  HIP_TRY(hipSetDevice(w->device));
+  // τ̄ and f̄ext are sums over every stage of every step: zero first (all of them when nothing moves)
+  if (tau_bar) HIP_TRY(hipMemsetAsync(tau_bar, 0, es * m->nv * B, w->stream));
+  if (fext_bar) HIP_TRY(hipMemsetAsync(fext_bar, 0, es * 6 * m->nb * B, w->stream));
+  if (nsteps == 0 || m->nv == 0) return RBD_OK;
+  if ((st = sav_ensure(w))) return st;
+  const size_t slot_bytes = es * (size_t)(m->nq + m->nv) * B;
+  const SavPlan P = sav_plan(slot_bytes, nsteps);
+  if ((st = ensure(&w->d_sav_ckpt, &w->d_sav_ckpt_bytes, slot_bytes * P.slots))) return st;  // (only a call that needs more room than any before)
+  Timed t(w);
+  w->last_kernel = "value_mk_stage_kernel + adjoint_mk_stage_kernel + tangent_solve_kernel + adjoint_rnea_kernel";
+  return by_dtype(w->dtype, [&](auto t) { return sav_run<decltype(t)>(w, B, o.layout, q, v, tau, fext, dt, nsteps, P, q_bar, v_bar, tau_bar, fext_bar); });
 }
 
 }  // extern "C"

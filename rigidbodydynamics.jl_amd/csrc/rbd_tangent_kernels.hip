@@ -1,12 +1,14 @@
 // rbd_tangent_kernels.hip — the kernels of the derivative entry points (rbd_inverse_dynamics_jvp, rbd_dynamics_jvp, rbd_inverse_dynamics_derivatives,
-// rbd_dynamics_derivatives, rbd_simulate_jvp, rbd_simulate_step_derivatives, rbd_inverse_dynamics_vjp, rbd_dynamics_vjp): the tangent RNEA (rbd_tangent.hpp)
-// with one thread per (state, chunk of TAN_CHUNK directions), the multi-right-hand-side triangular solve of dynamics! tangents against the Cholesky factor of
-// M, the tangent of the integrator's stage map (rbd_tangent_mk.hpp) with one thread per (state, joint, chunk), and the adjoint RNEA (rbd_adjoint.hpp) with
-// one thread per state.  Compiled with -ffinite-math-only -fno-signed-zeros (build.sh): the zero
+// rbd_dynamics_derivatives, rbd_simulate_jvp, rbd_simulate_step_derivatives, rbd_inverse_dynamics_vjp, rbd_dynamics_vjp, rbd_simulate_vjp): the tangent RNEA
+// (rbd_tangent.hpp) with one thread per (state, chunk of TAN_CHUNK directions), the multi-right-hand-side triangular solve of dynamics! tangents against the
+// Cholesky factor of M, the tangent of the integrator's stage map (rbd_tangent_mk.hpp) with one thread per (state, joint, chunk), the adjoint RNEA
+// (rbd_adjoint.hpp) with one thread per state, and the stage map's values and pullback (rbd_adjoint_mk.hpp) with one thread per (state, joint) of a
+// joint class.  Compiled with -ffinite-math-only -fno-signed-zeros (build.sh): the zero
 // tangents of the mechanism's constants fold out of the products.
 #include "rbd_tangent.hpp"
 #include "rbd_adjoint.hpp"
 #include "rbd_tangent_mk.hpp"
+#include "rbd_adjoint_mk.hpp"
 #include "rbd_internal.hpp"
 
 namespace rbd {
@@ -225,6 +227,127 @@ template <typename T> hipError_t launch_stage_rows(int n, long B, const void* x,
   return hipGetLastError();
 }
 
+// ---- simulate VJPs: the stage map's values and its pullback, one thread per (joint of a class, state), thread = j · B + state ---------------------------
+// Two instantiations per kernel: WIDE = false for the 1-coordinate joints (no Dual code: the registers of a revolute joint), WIDE = true for the planar and
+// quaternion joints.  Values are read in the call's layout, the cotangents of the stage state in the caller's (Lqb, Lvb), the rest batch-innermost.
+template <typename T, bool WIDE>
+__global__ __launch_bounds__(64) void value_mk_stage_kernel(MkAdjArgs<T> A) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)A.nj * A.B) return;
+  const long st = t % A.B;
+  const int j = (int)(t / A.B);
+  const int jt = A.jl[3 * j], qoff = A.jl[3 * j + 1], voff = A.jl[3 * j + 2];
+  constexpr int KQ = WIDE ? 7 : 2, KV = WIDE ? 6 : 1;
+  const int nqi = joint_nq<T>(jt), nvi = joint_nv(jt);
+  auto at = [&](T* p, Layout L, int row) -> T& { return p[(long)row * L.sk + layout_base(L, st)]; };
+  T q0[7], qs[7], qn[7], v0[6], vs[6], vd[6], ap[6], av[6], vn[6];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    const bool in = k < KQ && k < nqi;
+    q0[k] = in ? at((T*)A.q0, A.Lq, qoff + k) : T(0);
+    qs[k] = in ? at((T*)A.qs, A.Lq, qoff + k) : T(0);
+    qn[k] = T(0);
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const bool in = k < KV && k < nvi;
+    v0[k] = in ? at((T*)A.v0, A.Lv, voff + k) : T(0);
+    vs[k] = in ? at((T*)A.vs, A.Lv, voff + k) : T(0);
+    vd[k] = in ? at((T*)A.vd, A.Lv, voff + k) : T(0);
+    ap[k] = in && A.stage > 0 ? at(A.accp, A.Lv, voff + k) : T(0);
+    av[k] = in && A.stage > 0 ? at(A.accv, A.Lv, voff + k) : T(0);
+    vn[k] = T(0);
+  }
+  mk_stage_value_joint<T, WIDE>(jt, A.stage, A.dt, q0, v0, qs, vs, vd, ap, av, qn, vn);
+#pragma unroll
+  for (int k = 0; k < KQ; ++k)
+    if (k < nqi) at(A.qn, A.Lq, qoff + k) = qn[k];
+#pragma unroll
+  for (int k = 0; k < KV; ++k)
+    if (k < nvi) {
+      at(A.vn, A.Lv, voff + k) = vn[k];
+      if (A.stage < 3) { at(A.accp, A.Lv, voff + k) = ap[k]; at(A.accv, A.Lv, voff + k) = av[k]; }
+    }
+}
+
+template <typename T, bool WIDE>
+__global__ __launch_bounds__(64) void adjoint_mk_stage_kernel(MkAdjArgs<T> A) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)A.nj * A.B) return;
+  const long st = t % A.B;
+  const int j = (int)(t / A.B);
+  const int jt = A.jl[3 * j], qoff = A.jl[3 * j + 1], voff = A.jl[3 * j + 2];
+  constexpr int KQ = WIDE ? 7 : 2, KV = WIDE ? 6 : 1;
+  const int nqi = joint_nq<T>(jt), nvi = joint_nv(jt), stage = A.stage;
+  auto at = [&](T* p, Layout L, int row) -> T& { return p[(long)row * L.sk + layout_base(L, st)]; };
+  auto li = [&](T* p, int row) -> T& { return p[(long)row * A.B + st]; };
+  T q0[7], qs[7], qnb[7], q0b[7], qsb[7], vs[6], ap[6], vnb[6], apb[6], avb[6], v0b[6], vsb[6], vdb[6];
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    const bool in = k < KQ && k < nqi;
+    q0[k] = in ? at((T*)A.q0, A.Lq, qoff + k) : T(0);
+    qs[k] = in ? at((T*)A.qs, A.Lq, qoff + k) : T(0);
+    qnb[k] = in ? at(A.qsb, A.Lqb, qoff + k) : T(0);
+    q0b[k] = in && stage < 3 ? li(A.q0b, qoff + k) : T(0);
+    qsb[k] = T(0);
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const bool in = k < KV && k < nvi;
+    vs[k] = in ? at((T*)A.vs, A.Lv, voff + k) : T(0);
+    ap[k] = in && stage == 3 ? at(A.accp, A.Lv, voff + k) : T(0);
+    vnb[k] = in ? at(A.vsb, A.Lvb, voff + k) : T(0);
+    apb[k] = in && stage < 3 ? li(A.apb, voff + k) : T(0);
+    avb[k] = in && stage < 3 ? li(A.avb, voff + k) : T(0);
+    v0b[k] = in && stage < 3 ? li(A.v0b, voff + k) : T(0);
+    vsb[k] = T(0); vdb[k] = T(0);
+  }
+  adj_mk_stage_joint<T, WIDE>(jt, stage, A.dt, q0, qs, vs, ap, qnb, vnb, apb, avb, q0b, v0b, qsb, vsb, vdb);
+#pragma unroll
+  for (int k = 0; k < KQ; ++k)
+    if (k < nqi) {
+      if (stage > 0) {
+        at(A.qsb, A.Lqb, qoff + k) = qsb[k];
+        li(A.q0b, qoff + k) = q0b[k];
+      } else {  // (the stage-0 state is the base point itself)
+        at(A.qsb, A.Lqb, qoff + k) = q0b[k] + qsb[k];
+      }
+    }
+#pragma unroll
+  for (int k = 0; k < KV; ++k)
+    if (k < nvi) {
+      li(A.vdb, voff + k) = vdb[k];
+      if (stage > 0) {
+        at(A.vsb, A.Lvb, voff + k) = vsb[k];
+        li(A.v0b, voff + k) = v0b[k];
+      } else {
+        at(A.vsb, A.Lvb, voff + k) = v0b[k] + vsb[k];
+      }
+      if (stage == 3) { li(A.apb, voff + k) = apb[k]; li(A.avb, voff + k) = avb[k]; }
+    }
+}
+
+// one stage for both joint classes (narrow: nn joints at jn, wide: nw at jw); `adjoint` picks the pullback, else the value map
+template <typename T> hipError_t launch_mk_stage_classes(MkAdjArgs<T> A, const int32_t* jn, int nn, const int32_t* jw, int nw, int adjoint, hipStream_t s) {
+  for (int c = 0; c < 2; ++c) {
+    A.jl = c ? jw : jn;
+    A.nj = c ? nw : nn;
+    const long total = (long)A.nj * A.B;
+    if (total == 0) continue;
+    const dim3 grid((unsigned)((total + 63) / 64));
+    if (adjoint) {
+      if (c) hipLaunchKernelGGL((adjoint_mk_stage_kernel<T, true>), grid, dim3(64), 0, s, A);
+      else hipLaunchKernelGGL((adjoint_mk_stage_kernel<T, false>), grid, dim3(64), 0, s, A);
+    } else {
+      if (c) hipLaunchKernelGGL((value_mk_stage_kernel<T, true>), grid, dim3(64), 0, s, A);
+      else hipLaunchKernelGGL((value_mk_stage_kernel<T, false>), grid, dim3(64), 0, s, A);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 #define RBD_TAN_INST(T)                                                                                                                                    \
   template hipError_t launch_tangent_rnea<T>(const BigModel&, const TanArgs<T>&, void*, long, hipStream_t);                                              \
   template hipError_t launch_tangent_solve<T>(int, long, int, int, const void*, Layout, const void*, int, const ColOut<T>&, void*, hipStream_t);          \
@@ -233,7 +356,8 @@ template <typename T> hipError_t launch_stage_rows(int n, long B, const void* x,
   template hipError_t launch_tangent_mk_load<T>(long, int, int, int, int, int, const ColOut<T>&, const ColOut<T>&, const ColOut<T>&, const ColOut<T>&,   \
                                                 const ColOut<T>&, const ColOut<T>&, hipStream_t);                                                        \
   template hipError_t launch_adjoint_rnea<T>(const BigModel&, const AdjArgs<T>&, void*, long, hipStream_t);                                              \
-  template hipError_t launch_stage_rows<T>(int, long, const void*, Layout, void*, hipStream_t);
+  template hipError_t launch_stage_rows<T>(int, long, const void*, Layout, void*, hipStream_t);                                                        \
+  template hipError_t launch_mk_stage_classes<T>(MkAdjArgs<T>, const int32_t*, int, const int32_t*, int, int, hipStream_t);
 RBD_TAN_INST(double)
 RBD_TAN_INST(float)
 
