@@ -5,8 +5,15 @@ Default workload (BASELINE.json configs[1], `--config 2`): Atlas v5 URDF with fl
 perf/runbenchmarks.jl:14-19 mechanism, from the vendored test/urdf/atlas.urdf), batch = 4096 states per GPU, fp64, random (q, v, τ)
 drawn with the reference's distributions.  One *step* = one `dynamics!` over the whole batch (one ABA kernel launch); inputs are
 resident in HBM before the timed region (and, being re-evaluated every step, in L2 / Infinity Cache: the HBM-axis figure is a cache
-figure — irrelevant while the kernel is ALU/latency bound, but said here).  The same line also carries the run WITH a random external
-wrench on every body (what the reference's published 9.874 µs is measured with, perf/runbenchmarks.jl:59-67).
+figure — irrelevant while the kernel is ALU/latency bound, but said here).
+
+A plain run (`--gpus 1 --steps K --warmup W`) does what that figure needs and no more: set-up, W warm-up steps, the K timed steps,
+`--dump-outputs`, the line — with `roofline` and `alu`, which are arithmetic on the timed steps' own HIP events.  `--full` adds everything
+else the benchmark measures or checks: the whole-batch comparison with the oracle (`parity_check`; null on a plain line), the same steps
+WITH a random external wrench on every body (what the reference's published 9.874 µs is measured with, perf/runbenchmarks.jl:59-67),
+replayed from a hipGraph and as two batches on two streams, `cpu_baseline`, the RCCL gather timings of N > 1, and the blocks of the
+other configs, sizes and entry points that ride on the headline's line (main()).  `--no-extra-legs`, `--no-pipelined`, `--no-cpu-baseline`
+and `--no-other-configs` take single parts of `--full` away again.
 
 Other BASELINE configs: `--config 3` (65 536 states fp32, mass_matrix! + Cholesky solve), `--config 4` (65 536 states per GPU fp32 ABA,
 v̇ gathered over RCCL: both the compute-only rate and the rate with the all-gather inside every step), `--config 5` (four-bar linkage
@@ -17,11 +24,11 @@ under torch.distributed.run it reads RANK / WORLD_SIZE from the environment.  Th
 fixed), no data-path collective; `n_gpus` is the world size RCCL reports.  It refuses to run when fewer GPUs are visible than asked for.
 With N > 1 and no `--config`, the line's `value` is the SHARDED config — BASELINE configs[3], 65 536 fp32 states per GPU, the one the north star
 shards over 8 GPUs — not the 22 µs launches of configs[1]; `per_rank` lists every rank's own rate (there is no data-path collective, so a rank's rate
-IS the one-GPU rate of the same run), and the N = 1 point of the same workload is the `config4_shard` block of the one-GPU line.
+IS the one-GPU rate of the same run), and the N = 1 point of the same workload is the `config4_shard` block of the one-GPU `--full` line.
 
 Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel against HBM with the ALGORITHMIC bytes (sizeof(T)·(nq + 3·nv)
-per evaluation + q̇, SURVEY.md §8 d); `alu` gives the binding roof (vector ALU).  The result of the timed launches is compared with
-the oracle over the WHOLE batch.  `cpu_baseline` times the oracle's restatement of the reference route on the host cores (N = 1 only).
+per evaluation + q̇, SURVEY.md §8 d); `alu` gives the binding roof (vector ALU).  With `--full` the result of the timed launches is compared
+with the oracle over the WHOLE batch, and `cpu_baseline` times the oracle's restatement of the reference route on the host cores (N = 1 only).
 
 `--dump-outputs DIR` writes what the timed leg's last step computed (v̇ and q̇ for dynamics!, τ for inverse_dynamics!, x and the lower triangle of M for
 the solve; the final q, v of --op-sim; the by-products of --op-kin) as DIR/<name>.npy, state-major, at most 64 MB in all (beyond that a seeded sample of
@@ -106,6 +113,8 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the one timed leg: parity against the oracle, the extra legs, the other configs' blocks, cpu_baseline (see the module docstring)")
     ap.add_argument("--config", type=int, default=None, choices=sorted(CONFIGS),
                     help="BASELINE.json config (default: 2 = the headline, configs[1], on one GPU; 4 = the sharded configs[3] with --gpus N > 1)")
     ap.add_argument("--op", default=None, choices=["dynamics", "inverse_dynamics", "mass_matrix_solve"],
@@ -146,6 +155,8 @@ def parse_args():
     args.batch = args.batch or cfg["batch"]
     args.dtype = args.dtype or cfg["dtype"]
     args.op = args.op or cfg["op"]
+    if not args.full:  # a plain run: the one timed leg and its line
+        args.no_cpu_baseline = args.no_other_configs = args.no_extra_legs = True
     if args.no_extra_legs:
         args.no_pipelined = True
     args.solve_only_leg = not args.no_extra_legs
@@ -213,7 +224,9 @@ def setup(args):
     device = torch.device("cuda", local_rank if world > 1 and not one_device else 0)
     import rbd_amd as rbd
     from rigidbodydynamics_jl_amd import _capi
-    import oracle
+    oracle = None
+    if args.full:  # (a plain run compares nothing: it does not load the oracle)
+        import oracle
     return dict(np=np, torch=torch, world=world, rank=rank, dist=dist, device=device, rbd=rbd, _capi=_capi, oracle=oracle)
 
 
@@ -375,74 +388,76 @@ def run(args, env):
         dist.all_gather(allr, mine)
         per_rank = [float(t.item()) for t in allr]
 
-    # ---- parity of the timed work against the oracle over the WHOLE batch (outside the timed region) ----
-    qf, vf, tf = [a.astype(ndt).astype(np.float64) for a in (q, v, tau)]
-    ff = fext_all.astype(ndt).astype(np.float64) if headline_fext else None
-    ncores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-    check = {}
-    if args.op == "mass_matrix_solve":
-        n = min(B, 4096)  # M is nv x nv per state: the full 65 536-state comparison would need 0.7 GB of host doubles
-        Mref = oracle.mass_matrix(model, qf[:n], nthreads=ncores)
-        Mref = np.tril(Mref) + np.transpose(np.tril(Mref, -1), (0, 2, 1))
-        xref = np.linalg.solve(Mref, tf[:n, :, None])[:, :, 0]
-        if packed_M:
-            got_M = rbd.unpack_lower((d_packed if args.layout == "aos" else d_packed.t())[:n].double(), model.nv)
-        else:
-            got_M = result.massmatrix if args.layout == "aos" else result.massmatrix.t()
-            got_M = got_M[:n].double().cpu().numpy().reshape(n, model.nv, model.nv).transpose(0, 2, 1)
-        got_x = (x_out if args.layout == "aos" else x_out.t())[:n].double().cpu().numpy()
-        il = np.tril_indices(model.nv)
-        err_M = None if args.no_emit_M else float(np.abs(got_M[:, il[0], il[1]] - Mref[:, il[0], il[1]]).max() / np.abs(Mref).max())  # (None: M was not produced)
-        res = np.einsum("bij,bj->bi", Mref, got_x) - tf[:n]
-        # normwise backward error of the solve (Rigal–Gaches): ||M x − r|| / (||M|| ||x|| + ||r||) with the ORACLE's M
-        berr = float((np.linalg.norm(res, axis=1) / (np.linalg.norm(Mref, axis=(1, 2)) * np.linalg.norm(got_x, axis=1) + np.linalg.norm(tf[:n], axis=1))).max())
-        check = {"states_compared": n, "mass_matrix_rel_err": err_M, "solve_backward_err": berr,
-                 "forward_err_rel_max": float(np.abs(got_x - xref).max() / np.abs(xref).max())}
-        err = berr if err_M is None else max(err_M, berr)
-        tol = 1e-10 if args.dtype == "f64" else 2e-5
-    elif args.op == "inverse_dynamics":
-        ref = oracle.inverse_dynamics(model, qf, vf, tf, ff, nthreads=ncores)
-        got = (x_out if args.layout == "aos" else x_out.t()).double().cpu().numpy()
-        err = float(np.abs(got - ref).max() / max(1.0, np.abs(ref).max()))
-        check = {"states_compared": B}
-        if bodies:  # the per-body outputs on a sample (the oracle's per-body entry point is one state per call)
-            n = min(B, 4096)
-            _, jw_ref, acc_ref = oracle.inverse_dynamics_bodies(model, qf[:n], vf[:n], tf[:n], ff[:n] if ff is not None else None)
-            for name_, dev_, ref_ in (("jointwrenches", d_jw, jw_ref), ("accelerations", d_acc, acc_ref)):
-                g = (dev_ if args.layout == "aos" else dev_.t())[:n].double().cpu().numpy()
-                e = float(np.abs(g - ref_.reshape(n, -1)).max() / max(1.0, np.abs(ref_).max()))
-                check[name_ + "_rel_err"] = e
-                err = max(err, e)
-            check["per_body_states_compared"] = n
-        tol = 1e-10 if args.dtype == "f64" else 2e-4
-    elif model.nc > 0:
-        n = B  # the whole batch (the loop-joint oracle is one state per call: ~1 s for 4096 four-bar states)
-        ref = oracle.dynamics_loops(model, qf[:n], vf[:n], tf[:n], ff[:n] if ff is not None else None)["vdot"]
-        got = (result.vd if args.layout == "aos" else result.vd.t())[:n].double().cpu().numpy()
-        err = float(np.abs(got - ref).max() / max(1.0, np.abs(ref).max()))
-        check = {"states_compared": n}
-        tol = 1e-9
-    else:
-        ref = oracle.dynamics(model, qf, vf, tf, ff, nthreads=ncores)
-        got = (result.vd if args.layout == "aos" else result.vd.t()).double().cpu().numpy()
-        if args.dtype == "f64":
-            err = float(np.abs(got - ref).max() / max(1.0, np.abs(ref).max()))
-            tol = 1e-10
-        else:  # fp32: backward error against the fp64 oracle's M, c on a sample (cond(M) ~ 5e5: the forward error is not the criterion)
-            n = min(B, 4096)
+    # ---- --full: parity of the timed work against the oracle over the WHOLE batch (outside the timed region) ----
+    err = check = None
+    if args.full:
+        qf, vf, tf = [a.astype(ndt).astype(np.float64) for a in (q, v, tau)]
+        ff = fext_all.astype(ndt).astype(np.float64) if headline_fext else None
+        ncores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+        check = {}
+        if args.op == "mass_matrix_solve":
+            n = min(B, 4096)  # M is nv x nv per state: the full 65 536-state comparison would need 0.7 GB of host doubles
             Mref = oracle.mass_matrix(model, qf[:n], nthreads=ncores)
             Mref = np.tril(Mref) + np.transpose(np.tril(Mref, -1), (0, 2, 1))
-            c = oracle.dynamics_bias(model, qf[:n], vf[:n], ff[:n] if ff is not None else None)
-            r = tf[:n] - c
-            err = float((np.linalg.norm(np.einsum("bij,bj->bi", Mref, got[:n]) - r, axis=1) / np.linalg.norm(r, axis=1)).max())
-            check = {"backward_err_states": n, "forward_err_rel_max_whole_batch": float(np.abs(got - ref).max() / max(1.0, np.abs(ref).max()))}
-            tol = 2e-5
-        check["states_compared"] = B
-    assert err < tol or "spec_variant" in os.environ.get("RBD_TUNE", ""), f"parity lost in bench: {err} (tolerance {tol})"
+            xref = np.linalg.solve(Mref, tf[:n, :, None])[:, :, 0]
+            if packed_M:
+                got_M = rbd.unpack_lower((d_packed if args.layout == "aos" else d_packed.t())[:n].double(), model.nv)
+            else:
+                got_M = result.massmatrix if args.layout == "aos" else result.massmatrix.t()
+                got_M = got_M[:n].double().cpu().numpy().reshape(n, model.nv, model.nv).transpose(0, 2, 1)
+            got_x = (x_out if args.layout == "aos" else x_out.t())[:n].double().cpu().numpy()
+            il = np.tril_indices(model.nv)
+            err_M = None if args.no_emit_M else float(np.abs(got_M[:, il[0], il[1]] - Mref[:, il[0], il[1]]).max() / np.abs(Mref).max())  # (None: M was not produced)
+            res = np.einsum("bij,bj->bi", Mref, got_x) - tf[:n]
+            # normwise backward error of the solve (Rigal–Gaches): ||M x − r|| / (||M|| ||x|| + ||r||) with the ORACLE's M
+            berr = float((np.linalg.norm(res, axis=1) / (np.linalg.norm(Mref, axis=(1, 2)) * np.linalg.norm(got_x, axis=1) + np.linalg.norm(tf[:n], axis=1))).max())
+            check = {"states_compared": n, "mass_matrix_rel_err": err_M, "solve_backward_err": berr,
+                     "forward_err_rel_max": float(np.abs(got_x - xref).max() / np.abs(xref).max())}
+            err = berr if err_M is None else max(err_M, berr)
+            tol = 1e-10 if args.dtype == "f64" else 2e-5
+        elif args.op == "inverse_dynamics":
+            ref = oracle.inverse_dynamics(model, qf, vf, tf, ff, nthreads=ncores)
+            got = (x_out if args.layout == "aos" else x_out.t()).double().cpu().numpy()
+            err = float(np.abs(got - ref).max() / max(1.0, np.abs(ref).max()))
+            check = {"states_compared": B}
+            if bodies:  # the per-body outputs on a sample (the oracle's per-body entry point is one state per call)
+                n = min(B, 4096)
+                _, jw_ref, acc_ref = oracle.inverse_dynamics_bodies(model, qf[:n], vf[:n], tf[:n], ff[:n] if ff is not None else None)
+                for name_, dev_, ref_ in (("jointwrenches", d_jw, jw_ref), ("accelerations", d_acc, acc_ref)):
+                    g = (dev_ if args.layout == "aos" else dev_.t())[:n].double().cpu().numpy()
+                    e = float(np.abs(g - ref_.reshape(n, -1)).max() / max(1.0, np.abs(ref_).max()))
+                    check[name_ + "_rel_err"] = e
+                    err = max(err, e)
+                check["per_body_states_compared"] = n
+            tol = 1e-10 if args.dtype == "f64" else 2e-4
+        elif model.nc > 0:
+            n = B  # the whole batch (the loop-joint oracle is one state per call: ~1 s for 4096 four-bar states)
+            ref = oracle.dynamics_loops(model, qf[:n], vf[:n], tf[:n], ff[:n] if ff is not None else None)["vdot"]
+            got = (result.vd if args.layout == "aos" else result.vd.t())[:n].double().cpu().numpy()
+            err = float(np.abs(got - ref).max() / max(1.0, np.abs(ref).max()))
+            check = {"states_compared": n}
+            tol = 1e-9
+        else:
+            ref = oracle.dynamics(model, qf, vf, tf, ff, nthreads=ncores)
+            got = (result.vd if args.layout == "aos" else result.vd.t()).double().cpu().numpy()
+            if args.dtype == "f64":
+                err = float(np.abs(got - ref).max() / max(1.0, np.abs(ref).max()))
+                tol = 1e-10
+            else:  # fp32: backward error against the fp64 oracle's M, c on a sample (cond(M) ~ 5e5: the forward error is not the criterion)
+                n = min(B, 4096)
+                Mref = oracle.mass_matrix(model, qf[:n], nthreads=ncores)
+                Mref = np.tril(Mref) + np.transpose(np.tril(Mref, -1), (0, 2, 1))
+                c = oracle.dynamics_bias(model, qf[:n], vf[:n], ff[:n] if ff is not None else None)
+                r = tf[:n] - c
+                err = float((np.linalg.norm(np.einsum("bij,bj->bi", Mref, got[:n]) - r, axis=1) / np.linalg.norm(r, axis=1)).max())
+                check = {"backward_err_states": n, "forward_err_rel_max_whole_batch": float(np.abs(got - ref).max() / max(1.0, np.abs(ref).max()))}
+                tol = 2e-5
+            check["states_compared"] = B
+        assert err < tol or "spec_variant" in os.environ.get("RBD_TUNE", ""), f"parity lost in bench: {err} (tolerance {tol})"
 
     extra = {}
     gather_ms = None
-    if dist is not None and args.op == "dynamics":
+    if dist is not None and args.op == "dynamics" and args.full:
         torch.cuda.synchronize(device)
         try:
             dist.all_gather_into_tensor(gathered, result.vd)  # warm-up (RCCL channel setup)
@@ -612,14 +627,13 @@ def run(args, env):
     return out
 
 
-def sim_leg(env, B, dtype, steps=12, warm=2, dt=1e-3, dump=None):
+def sim_leg(env, B, dtype, steps=12, warm=2, dt=1e-3, dump=None, full=True):
     """One RK4 step of the batched `simulate` (src/simulate.jl:36-55, MuntheKaasIntegrator.step src/ode_integrators.jl:233-299; rbd_simulate, the stage folded
     into the dynamics kernel): K steps between HIP events on Atlas at B states, then — from the same initial state — two steps of EVERY state compared with the
     numpy restatement of the integrator (oracle/simulate_np.py, its batch-vectorised form).  One step = four dynamics! evaluations: `alu` prices 4 x 27 kflop,
-    `roofline` the step's compulsory bytes (q, v in and out, tau in)."""
+    `roofline` the step's compulsory bytes (q, v in and out, tau in).  full = False: the timed steps alone, nothing compared."""
     np, torch, device = env["np"], env["torch"], env["device"]
     rbd, _capi = env["rbd"], env["_capi"]
-    import simulate_np
     model = rbd.load_flat_model(os.path.join(ROOT, "tests", "golden", "models", "atlas_floating.json"))
     tdt = torch.float64 if dtype == "f64" else torch.float32
     es = 8 if dtype == "f64" else 4
@@ -658,21 +672,24 @@ def sim_leg(env, B, dtype, steps=12, warm=2, dt=1e-3, dump=None):
         dump_outputs(dump, {"q": state.q, "v": state.v}, B)
     kernel = (L.rbd_workspace_last_kernel(state.ws.handle) or b"").decode()
     # parity: two steps from the initial state, EVERY state against the integrator's numpy restatement (fp64)
-    reset()
-    advance(2)
-    torch.cuda.synchronize(device)
-    ndt = np.float64 if dtype == "f64" else np.float32
-    ncores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-    qs, vs, ts_ = [a.astype(ndt).astype(np.float64) for a in (q0, v0, tau)]
-    q_ref, v_ref = simulate_np.simulate_batch(model, qs, vs, 2, dt, ts_, nthreads=ncores)
-    qg, vg = state.q.double().cpu().numpy(), state.v.double().cpu().numpy()
-    for o in range(0, 1):  # Atlas: one quaternion, at q[0:4] — compared up to sign
-        sg = np.sign(qg[:, o:o + 1] * q_ref[:, o:o + 1]); sg[sg == 0] = 1
-        qg[:, o:o + 4] *= sg
-    eq = float(np.abs(qg - q_ref).max() / max(1.0, np.abs(q_ref).max()))
-    ev = float(np.abs(vg - v_ref).max() / max(1.0, np.abs(v_ref).max()))
-    tq, tv = (1e-10, 1e-9) if dtype == "f64" else (2e-5, 2e-3)
-    assert eq < tq and ev < tv, f"simulate parity lost in bench: q {eq} v {ev}"
+    eq = ev = None
+    if full:
+        import simulate_np
+        reset()
+        advance(2)
+        torch.cuda.synchronize(device)
+        ndt = np.float64 if dtype == "f64" else np.float32
+        ncores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+        qs, vs, ts_ = [a.astype(ndt).astype(np.float64) for a in (q0, v0, tau)]
+        q_ref, v_ref = simulate_np.simulate_batch(model, qs, vs, 2, dt, ts_, nthreads=ncores)
+        qg, vg = state.q.double().cpu().numpy(), state.v.double().cpu().numpy()
+        for o in range(0, 1):  # Atlas: one quaternion, at q[0:4] — compared up to sign
+            sg = np.sign(qg[:, o:o + 1] * q_ref[:, o:o + 1]); sg[sg == 0] = 1
+            qg[:, o:o + 4] *= sg
+        eq = float(np.abs(qg - q_ref).max() / max(1.0, np.abs(q_ref).max()))
+        ev = float(np.abs(vg - v_ref).max() / max(1.0, np.abs(v_ref).max()))
+        tq, tv = (1e-10, 1e-9) if dtype == "f64" else (2e-5, 2e-3)
+        assert eq < tq and ev < tv, f"simulate parity lost in bench: q {eq} v {ev}"
     us = ev0.elapsed_time(ev1) / steps * 1e3
     alg_bytes = es * (2 * model.nq + 3 * model.nv)
     gbs = alg_bytes * B / (us * 1e-6) / 1e9
@@ -686,8 +703,8 @@ def sim_leg(env, B, dtype, steps=12, warm=2, dt=1e-3, dump=None):
                          "kernel": kernel, "kernel_ms": us * 1e-3, "algorithmic_bytes_per_eval": alg_bytes},
             "alu": {"bound": "fp64 vector ALU" if dtype == "f64" else "fp32 vector ALU", "achieved": tf, "peak": peak_tf, "unit": "TFLOP/s", "frac": tf / peak_tf,
                     "flops_per_eval": 4 * ABA_FLOPS_PER_EVAL},
-            "parity_rel_err_vs_oracle": max(eq, ev),
-            "parity_check": {"states_compared": B, "steps": 2, "q_rel_err": eq, "v_rel_err": ev, "against": "oracle/simulate_np.py (Munthe-Kaas RK4 restated in numpy, fp64)"}}
+            "parity_rel_err_vs_oracle": max(eq, ev) if full else None,
+            "parity_check": {"states_compared": B, "steps": 2, "q_rel_err": eq, "v_rel_err": ev, "against": "oracle/simulate_np.py (Munthe-Kaas RK4 restated in numpy, fp64)"} if full else None}
 
 
 def pmc_traffic(key):
@@ -710,11 +727,11 @@ def sim_traffic(dtype, B):
     return pmc_traffic(f"atlas_floating_{dtype}_B{B}_simulate")[0]
 
 
-def kin_leg(env, B, dtype, steps=40, warm=8, model_name="atlas_floating", dump=None):
+def kin_leg(env, B, dtype, steps=40, warm=8, model_name="atlas_floating", dump=None, full=True):
     """The kinematics by-products the reference benchmarks beside the dynamics (perf/runbenchmarks.jl:69-110: momentum_matrix!, geometric_jacobian!, momentum,
     kinetic_energy, center_of_mass — SURVEY.md §8 f3): one step = rbd_kinematics (momentum matrix + centre of mass + both energies) + rbd_geometric_jacobian (world ->
     the last body: a hand) + rbd_momentum (momentum, momentum_rate_bias) over the batch, each also timed on its own by HIP events; parity of every output against
-    the oracle.  Algorithmic bytes: the inputs each call reads plus the outputs it writes."""
+    the oracle.  Algorithmic bytes: the inputs each call reads plus the outputs it writes.  full = False: the timed sets alone (`kernel` = the last call's)."""
     np, torch, device = env["np"], env["torch"], env["device"]
     rbd, _capi, oracle = env["rbd"], env["_capi"], env["oracle"]
     if model_name.startswith("randmech"):  # the reference's own test mechanism, seed = the suffix (as in run())
@@ -771,29 +788,32 @@ def kin_leg(env, B, dtype, steps=40, warm=8, model_name="atlas_floating", dump=N
     wall, us = time_of(list(calls))
     if dump:
         dump_outputs(dump, {"momentum_matrix": A, "center_of_mass": com, "energies": en, "geometric_jacobian": J, "momentum": mom}, B)
-    each, kernels = {}, []
-    for n_ in calls:
-        each[n_] = time_of([n_])[1]
-        kernels.append((L.rbd_workspace_last_kernel(h) or b"").decode().split(" (")[0])
+    each, kernels = {}, [(L.rbd_workspace_last_kernel(h) or b"").decode().split(" (")[0]]
+    err = errs = n = None
+    if full:  # each call in a timed run of its own, then parity
+        kernels = []
+        for n_ in calls:
+            each[n_] = time_of([n_])[1]
+            kernels.append((L.rbd_workspace_last_kernel(h) or b"").decode().split(" (")[0])
     # parity (the per-state oracle entry points are one ctypes call per state: a sample of 4096 states)
-    n = min(B, 4096)
-    ndt = np.float64 if dtype == "f64" else np.float32
-    qf, vf = q[:n].astype(ndt).astype(np.float64), v[:n].astype(ndt).astype(np.float64)
-    A_ref, _, com_ref = oracle.momentum_matrix(model, qf, vf)
-    ke_ref, pe_ref = oracle.energy(model, qf, vf)
-    J_ref, _ = oracle.geometric_jacobian(model, qf, -1, target)
-    h_ref, hb_ref = oracle.momentum(model, qf, vf)
+        n = min(B, 4096)
+        ndt = np.float64 if dtype == "f64" else np.float32
+        qf, vf = q[:n].astype(ndt).astype(np.float64), v[:n].astype(ndt).astype(np.float64)
+        A_ref, _, com_ref = oracle.momentum_matrix(model, qf, vf)
+        ke_ref, pe_ref = oracle.energy(model, qf, vf)
+        J_ref, _ = oracle.geometric_jacobian(model, qf, -1, target)
+        h_ref, hb_ref = oracle.momentum(model, qf, vf)
 
-    def rel(got, ref):
-        return float(np.abs(got - ref).max() / max(1.0, np.abs(ref).max()))
-    errs = {"momentum_matrix": rel(A[:n].double().cpu().numpy().reshape(n, nv, 6).transpose(0, 2, 1), A_ref),
-            "center_of_mass": rel(com[:n].double().cpu().numpy(), com_ref),
-            "energies": rel(en[:n].double().cpu().numpy(), np.stack([ke_ref, pe_ref], axis=1)),
-            "geometric_jacobian": rel(J[:n].double().cpu().numpy().reshape(n, nv, 6).transpose(0, 2, 1), J_ref),
-            "momentum": rel(mom[:n].double().cpu().numpy(), np.concatenate([h_ref, hb_ref], axis=1))}
-    err = max(errs.values())
-    tol = 1e-10 if dtype == "f64" else 2e-4
-    assert err < tol, f"kinematics parity lost in bench: {errs}"
+        def rel(got, ref):
+            return float(np.abs(got - ref).max() / max(1.0, np.abs(ref).max()))
+        errs = {"momentum_matrix": rel(A[:n].double().cpu().numpy().reshape(n, nv, 6).transpose(0, 2, 1), A_ref),
+                "center_of_mass": rel(com[:n].double().cpu().numpy(), com_ref),
+                "energies": rel(en[:n].double().cpu().numpy(), np.stack([ke_ref, pe_ref], axis=1)),
+                "geometric_jacobian": rel(J[:n].double().cpu().numpy().reshape(n, nv, 6).transpose(0, 2, 1), J_ref),
+                "momentum": rel(mom[:n].double().cpu().numpy(), np.concatenate([h_ref, hb_ref], axis=1))}
+        err = max(errs.values())
+        tol = 1e-10 if dtype == "f64" else 2e-4
+        assert err < tol, f"kinematics parity lost in bench: {errs}"
     alg_bytes = sum(c[1] for c in calls.values())
     gbs = alg_bytes * B / (us * 1e-6) / 1e9
     return {"metric": "kinematics by-products sets/sec (momentum_matrix! + center_of_mass + energies, geometric_jacobian!, momentum + momentum_rate_bias)",
@@ -803,8 +823,8 @@ def kin_leg(env, B, dtype, steps=40, warm=8, model_name="atlas_floating", dump=N
                          "traffic": pmc_traffic(f"{model_name}_{dtype}_B{B}_kinematics")[0], "kernel": " + ".join(kernels), "kernel_ms": us * 1e-3,
                          "algorithmic_bytes_per_eval": alg_bytes,
                          "each": {n_: {"us": round(each[n_], 2), "bytes_per_state": calls[n_][1], "hbm_frac": round(calls[n_][1] * B / (each[n_] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}
-                                  for n_ in calls}},
-            "parity_rel_err_vs_oracle": err, "parity_check": dict(errs, states_compared=n)}
+                                  for n_ in each}},
+            "parity_rel_err_vs_oracle": err, "parity_check": dict(errs, states_compared=n) if full else None}
 
 
 def sub_args(args, config, **over):
@@ -892,8 +912,8 @@ def main():
         return selftest_launch(args)
     env = setup(args)
     if args.op_sim or args.op_kin:  # one leg of its own for a profiler run
-        d = sim_leg(env, args.batch, args.dtype, steps=args.steps, warm=args.warmup, dump=args.dump_outputs) if args.op_sim else \
-            kin_leg(env, args.batch, args.dtype, steps=args.steps, warm=args.warmup, model_name=args.model, dump=args.dump_outputs)
+        d = sim_leg(env, args.batch, args.dtype, steps=args.steps, warm=args.warmup, dump=args.dump_outputs, full=args.full) if args.op_sim else \
+            kin_leg(env, args.batch, args.dtype, steps=args.steps, warm=args.warmup, model_name=args.model, dump=args.dump_outputs, full=args.full)
         print(json.dumps(d))
         return
     out = run(args, env)

@@ -7,7 +7,7 @@ for B in ${BATCHES:-256 512 1024 2048 4096 8192 16384}; do
     export RBD_TUNE="mass_min_batch=$T"
     for V in "" "--no-emit-M" "--packed-M"; do
       [ "$DT" = f64 ] && [ -n "$V" ] && continue
-      python bench.py --config 3 --dtype $DT --batch $B $V --no-cpu-baseline --no-extra-legs --no-other-configs --steps 100 --warmup 10 2>/dev/null | tail -1 | python -c "
+      python bench.py --config 3 --dtype $DT --batch $B $V --full --no-cpu-baseline --no-extra-legs --no-other-configs --steps 100 --warmup 10 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('$DT B', $B, 'mass_min_batch', '$T'[:6], '$V', 'us', round(d['ms_per_step']*1e3,2), d['roofline'].get('kernel'), 'err', d.get('parity_rel_err_vs_oracle'))"

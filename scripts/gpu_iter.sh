@@ -17,7 +17,7 @@ leg_args() {
 }
 cd /tmp
 for LEG in $LEGS; do
-  SHORT="$(leg_args $LEG) --no-cpu-baseline --no-extra-legs --no-other-configs --steps 60 --warmup 10"
+  SHORT="$(leg_args $LEG) --full --no-cpu-baseline --no-extra-legs --no-other-configs --steps 60 --warmup 10"
   python $R/bench.py $SHORT > $OUT/bench_$LEG.json 2> $OUT/bench_$LEG.err
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$LEG -- python $R/bench.py $SHORT > $OUT/stats_$LEG.log 2>&1
   rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS --output-format csv -d $OUT/pmc_sq1_$LEG -- python $R/bench.py $SHORT > /dev/null 2>&1

@@ -33,7 +33,7 @@ leg_args() {
 }
 cd /tmp
 for LEG in $LEGS; do
-  SHORT="$(leg_args $LEG) --no-cpu-baseline --no-extra-legs --no-other-configs --steps 60 --warmup 10"
+  SHORT="$(leg_args $LEG) --full --no-cpu-baseline --no-extra-legs --no-other-configs --steps 60 --warmup 10"
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$LEG -- python $R/bench.py $SHORT > $OUT/stats_$LEG.log 2>&1
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_$LEG -- python $R/bench.py $SHORT > /dev/null 2>&1
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_$LEG -- python $R/bench.py $SHORT > /dev/null 2>&1
@@ -42,8 +42,8 @@ for LEG in $LEGS; do
 done
 cd $R
 python scripts/summarize_measure.py $LEGS
-python bench.py --full-out profiles/r06_bench_full.json > profiles/r06_bench.json 2> $OUT/bench.err
-python bench.py --steps 20 --warmup 5 --full-out profiles/r06_bench_driver_steps_full.json > profiles/r06_bench_driver_steps.json 2>> $OUT/bench.err
+python bench.py --full --full-out profiles/r06_bench_full.json > profiles/r06_bench.json 2> $OUT/bench.err
+python bench.py --full --steps 20 --warmup 5 --full-out profiles/r06_bench_driver_steps_full.json > profiles/r06_bench_driver_steps.json 2>> $OUT/bench.err
 wc -c profiles/r06_bench.json profiles/r06_bench_driver_steps.json
 python - <<PY
 import json

@@ -1,11 +1,13 @@
-"""Condenses the rocprofv3 outputs of scripts/gpu_check.sh (gpurun_out/prof, gpurun_out/pmc*) into one text summary."""
-import collections, csv, glob, json
-for f in glob.glob("gpurun_out/prof/**/*kernel_stats.csv", recursive=True):
+"""Condenses the rocprofv3 outputs of scripts/gpu_check.sh (<output directory>/prof, <output directory>/pmc*) into one text summary.
+usage: python scripts/summarize_prof.py <output directory>"""
+import collections, csv, glob, json, sys
+OUT = sys.argv[1]
+for f in glob.glob(OUT + "/prof/**/*kernel_stats.csv", recursive=True):
     print("== kernel stats (rocprofv3 --kernel-trace --stats):", f)
     for r in csv.DictReader(open(f)):
         print(f"  {r['Name'][:90]:90s} calls={r['Calls']} avg_ns={float(r['AverageNs']):.0f} min={r['MinNs']} max={r['MaxNs']} pct={r['Percentage']}")
 tot = {}
-for d in sorted(glob.glob("gpurun_out/pmc*/")):
+for d in sorted(glob.glob(OUT + "/pmc*/")):
     for f in glob.glob(d + "**/*counter_collection.csv", recursive=True):
         acc = collections.defaultdict(list)
         for r in csv.DictReader(open(f)):
@@ -25,4 +27,4 @@ if "FETCH_SIZE" in tot:
     # the x2 correction is applied as an upper bound; narrow 8-byte accesses are uncalibrated.
     fetch, write = tot["FETCH_SIZE"] * 1024, tot.get("WRITE_SIZE", 0) * 1024
     print(f"  HBM traffic per launch: FETCH {fetch:.0f} B (x2 corrected: {2*fetch:.0f} B), WRITE {write:.0f} B")
-    json.dump({"fetch_bytes_raw": fetch, "fetch_bytes_x2": 2 * fetch, "write_bytes": write}, open("gpurun_out/pmc_traffic.json", "w"))
+    json.dump({"fetch_bytes_raw": fetch, "fetch_bytes_x2": 2 * fetch, "write_bytes": write}, open(OUT + "/pmc_traffic.json", "w"))

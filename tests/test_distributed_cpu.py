@@ -83,3 +83,26 @@ def test_bench_refuses_more_gpus_than_visible():
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "64"], capture_output=True, text=True, env=env, timeout=300)
     assert out.returncode == 2
     assert "refusing" in json.loads(out.stdout.strip().splitlines()[-1])["error"]
+
+
+def test_bench_full_option_gates_everything_beyond_the_timed_leg():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` is the timed leg alone; `--full` brings back parity, cpu_baseline, the extra legs and the other
+    configs' blocks, and the --no-* options still take single parts of it away.  (In a child process: importing bench.py sets environment defaults.)"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import json, sys; sys.path.insert(0, %r); import bench; a = bench.parse_args(); "
+            "print(json.dumps({k: getattr(a, k) for k in ('full', 'no_cpu_baseline', 'no_other_configs', 'no_extra_legs', 'no_pipelined', 'steps', 'warmup')}))") % root
+
+    def parse(*argv):
+        out = subprocess.run([sys.executable, "-c", code, *argv], capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return json.loads(out.stdout.strip().splitlines()[-1])
+    off = ("no_cpu_baseline", "no_other_configs", "no_extra_legs", "no_pipelined")
+    plain = parse("--gpus", "1", "--steps", "20", "--warmup", "5")
+    assert not plain["full"] and all(plain[k] for k in off) and (plain["steps"], plain["warmup"]) == (20, 5)
+    full = parse("--gpus", "1", "--steps", "20", "--warmup", "5", "--full")
+    assert full["full"] and not any(full[k] for k in off) and (full["steps"], full["warmup"]) == (20, 5)
+    part = parse("--full", "--no-cpu-baseline")
+    assert part["full"] and part["no_cpu_baseline"] and not part["no_other_configs"]
