@@ -12,6 +12,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
+_LIBQ = None
 
 WHAT_DYNAMICS, WHAT_INVERSE_DYNAMICS, WHAT_DYNAMICS_BIAS, WHAT_MASS_MATRIX, WHAT_ABA = range(5)
 
@@ -21,6 +22,7 @@ def build(force: bool = False) -> str:
     srcs = [os.path.join(_HERE, f) for f in ("rbd_oracle.c", "rbd_oracle_impl.h")] + [os.path.join(_HERE, "..", "include", "rbd_hip.h")]
     if force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
         subprocess.check_call(["make", "-C", _HERE, "-B", "librbd_oracle.so"], stdout=subprocess.DEVNULL)
+    build_quad(force)
     return so
 
 
@@ -32,6 +34,29 @@ def lib():
             build()
         _LIB = ctypes.CDLL(so)
     return _LIB
+
+
+def build_quad(force: bool = False) -> str:
+    """oracle/librbd_oracle_q.so: the oracle in IEEE binary128 with its derivative drivers (rbd_oracle_q.c).  A failure raises with the compiler's message."""
+    so = os.path.join(_HERE, "librbd_oracle_q.so")
+    srcs = [os.path.join(_HERE, f) for f in ("rbd_oracle_q.c", "rbd_oracle_impl.h", "Makefile")] + [os.path.join(_HERE, "..", "include", "rbd_hip.h")]
+    if force or not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+        p = subprocess.run(["make", "-C", _HERE, "-B", "librbd_oracle_q.so"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if p.returncode != 0:
+            raise RuntimeError("the quad-precision oracle failed to build:\n" + p.stdout)
+    return so
+
+
+def libq():
+    """The quad-precision oracle.  It is never optional: a tree where it cannot be built or loaded raises here (no skip)."""
+    global _LIBQ
+    if _LIBQ is None:
+        so = build_quad()
+        try:
+            _LIBQ = ctypes.CDLL(so)
+        except OSError as e:
+            raise RuntimeError(f"the quad-precision oracle {so} failed to load: {e}") from e
+    return _LIBQ
 
 
 def _sfx(dtype):
@@ -241,3 +266,69 @@ def dynamics_contact(model, q, v, s, tau=None, fext=None, dtype=np.float64):
     s2, sd, cw = contact_dynamics(model, q, v, s, dtype)
     tw = cw if fext is None else cw + np.asarray(fext, dtype)
     return dynamics(model, q, v, tau, tw, dtype=dtype), s2, sd, cw, tw
+
+
+# ---- the quad-precision oracle (oracle/rbd_oracle_q.c): values and derivatives evaluated in IEEE binary128, doubles in and out -------------------------
+# The reference of every derivative kernel.  A central difference of the oracle evaluated in quad is exact to the final rounding to double (the argument and
+# its proof by test: rbd_oracle_q.c, tests/test_oracle_quad.py), and it differentiates the SAME function of raw coordinates as the fp64 oracle.
+QUAD_H = 1e-11       # 2-point quotient: truncation ~ h^2 f'''/6 ~ 1e-23, rounding ~ cond 2^-113 / h ~ 1e-23 cond
+QUAD_THREADS = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 1, int(os.environ.get("OMP_NUM_THREADS") or 16)))
+_D = ctypes.c_double
+
+
+def _prepq(a, shape):
+    return _prep(a, np.float64, shape)
+
+
+def quad_values(model, what, q, v=None, x=None, fext=None, nthreads=None):
+    """batch(...) evaluated in quad and rounded to double once (WHAT_MASS_MATRIX: [b, i, j] = M[i, j], lower triangle, as mass_matrix)."""
+    B, nq, nv, nb = q.shape[0], model.nq, model.nv, model.n_bodies
+    q, v, x, fext = _prepq(q, (B, nq)), _prepq(v, (B, nv)), _prepq(x, (B, nv)), _prepq(fext, (B, 6 * nb))
+    out = np.zeros((B, nv * nv) if what == WHAT_MASS_MATRIX else (B, nv))
+    f = libq().rbdo_q_values
+    f.restype = ctypes.c_int
+    st = f(ctypes.byref(model.c_struct()), ctypes.c_int(what), ctypes.c_int(B), ctypes.c_int(nthreads or QUAD_THREADS), _ptr(q, _D), _ptr(v, _D), _ptr(x, _D),
+           _ptr(fext, _D), _ptr(out, _D))
+    if st != 0:
+        raise RuntimeError(f"quad oracle status {st}")
+    return out.reshape(B, nv, nv).transpose(0, 2, 1) if what == WHAT_MASS_MATRIX else out
+
+
+def jvp(model, what, q, v, x=None, fext=None, dq=None, dv=None, dx=None, dfext=None, h=QUAD_H, points=2, nthreads=None, want_value=False):
+    """Directional derivative of WHAT_INVERSE_DYNAMICS (x = v̇), WHAT_DYNAMICS or WHAT_ABA (x = τ) or WHAT_DYNAMICS_BIAS along (dq, dv, dx, dfext), any of them
+    None (a zero direction), in raw coordinates.  Directions (B, n) give (B, nv); (B, ntan, n) give (B, ntan, nv).  points: 2 or 4, the central quotient."""
+    B, nq, nv, nb = q.shape[0], model.nq, model.nv, model.n_bodies
+    dirs = [None if d is None else np.asarray(d, dtype=np.float64) for d in (dq, dv, dx, dfext)]
+    given = [d for d in dirs if d is not None]
+    assert given, "no direction"
+    single = given[0].ndim == 2
+    assert all((d.ndim == 2) == single for d in given)
+    ntan = 1 if single else given[0].shape[1]
+    dirs = [_prepq(d if d is None or not single else d[:, None], (B, ntan, n)) for d, n in zip(dirs, (nq, nv, nv, 6 * nb))]
+    q, v, x, fext = _prepq(q, (B, nq)), _prepq(v, (B, nv)), _prepq(x, (B, nv)), _prepq(fext, (B, 6 * nb))
+    val, out = np.zeros((B, nv)), np.zeros((B, ntan, nv))
+    f = libq().rbdo_q_jvp
+    f.restype = ctypes.c_int
+    st = f(ctypes.byref(model.c_struct()), ctypes.c_int(what), ctypes.c_int(B), ctypes.c_int(ntan), ctypes.c_int(nthreads or QUAD_THREADS), _ptr(q, _D), _ptr(v, _D),
+           _ptr(x, _D), _ptr(fext, _D), *[_ptr(d, _D) for d in dirs], _D(h), ctypes.c_int(points), _ptr(val, _D), _ptr(out, _D))
+    if st != 0:
+        raise RuntimeError(f"quad oracle status {st}")
+    out = out[:, 0] if single else out
+    return (val, out) if want_value else out
+
+
+def jacobians(model, what, q, v, x=None, fext=None, h=QUAD_H, points=2, nthreads=None, wrt="qvx"):
+    """Full Jacobians by unit directions in raw coordinates: dict(val [B, nv], q [B, nv, nq], v [B, nv, nv], x [B, nv, nv]) with [b, i, j] = ∂out_i/∂coordinate_j;
+    x is v̇ for inverse dynamics (the mass matrix) and τ for dynamics and ABA (its inverse).  wrt: which of them to compute."""
+    B, nq, nv, nb = q.shape[0], model.nq, model.nv, model.n_bodies
+    q, v, x, fext = _prepq(q, (B, nq)), _prepq(v, (B, nv)), _prepq(x, (B, nv)), _prepq(fext, (B, 6 * nb))
+    out = dict(val=np.zeros((B, nv)))
+    for key, n in (("q", nq), ("v", nv), ("x", nv)):
+        out[key] = np.zeros((B, nv, n)) if key in wrt else None
+    f = libq().rbdo_q_jacobians
+    f.restype = ctypes.c_int
+    st = f(ctypes.byref(model.c_struct()), ctypes.c_int(what), ctypes.c_int(B), ctypes.c_int(nthreads or QUAD_THREADS), _ptr(q, _D), _ptr(v, _D), _ptr(x, _D),
+           _ptr(fext, _D), _D(h), ctypes.c_int(points), _ptr(out["val"], _D), _ptr(out["q"], _D), _ptr(out["v"], _D), _ptr(out["x"], _D))
+    if st != 0:
+        raise RuntimeError(f"quad oracle status {st}")
+    return out

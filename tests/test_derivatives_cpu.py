@@ -1,6 +1,7 @@
 """Forward-mode derivatives of inverse_dynamics! without a GPU (header 700): the four entry points are declared and exported, and the per-state tangent
-routine of the derivative kernels (csrc/rbd_tangent.hpp tangent_rnea_state), compiled as plain C++ for the host like tests/emu/spec_emu.py does, matches a
-4th-order central difference of the oracle — every joint type, random directions, quaternion directions off the unit sphere included."""
+routine of the derivative kernels (csrc/rbd_tangent.hpp tangent_rnea_state), compiled as plain C++ for the host like tests/emu/spec_emu.py does, matches the
+directional derivative of the quad-precision oracle (oracle.jvp: exact to double rounding) at the project's fp64 parity number 1e-10 — every joint type, random
+directions, quaternion directions off the unit sphere included."""
 import ctypes
 import hashlib
 import os
@@ -85,10 +86,9 @@ def emu_jvp(lib, flat, q, v, vd, fext, dq, dv, dvd, dfext, ntan):
     return tau, dtau
 
 
-def fd_jvp(oracle, flat, q, v, vd, fext, dq, dv, dvd, dfext, h=1e-3):
-    """4th-order central difference of the oracle's inverse_dynamics along one direction per state."""
-    f = lambda s: oracle.inverse_dynamics(flat, q + s * dq, v + s * dv, vd + s * dvd, fext + s * dfext)
-    return (8 * (f(h) - f(-h)) - (f(2 * h) - f(-2 * h))) / (12 * h)
+def quad_jvp(oracle, flat, q, v, vd, fext, dq, dv, dvd, dfext):
+    """The directional derivative of the oracle's inverse_dynamics in raw coordinates, evaluated in quad precision: one direction per state."""
+    return oracle.jvp(flat, oracle.WHAT_INVERSE_DYNAMICS, q, v, vd, fext, dq, dv, dvd, dfext)
 
 
 @pytest.fixture(scope="module")
@@ -129,9 +129,9 @@ def test_tangent_routine_matches_central_difference(harness, models, oracle, rbd
     assert np.abs(tau - ref_tau).max() <= 1e-10 * (1 + np.abs(ref_tau).max())
     got = dtau.reshape(B, ntan, flat.nv)
     for d in range(ntan):
-        ref = fd_jvp(oracle, flat, q, v, vd, fext, dq[:, d], dv[:, d], dvd[:, d], dfe[:, d])
+        ref = quad_jvp(oracle, flat, q, v, vd, fext, dq[:, d], dv[:, d], dvd[:, d], dfe[:, d])
         err = np.abs(got[:, d] - ref).max()
-        assert err <= 1e-7 * (1 + np.abs(ref).max()), (name, d, err)
+        assert err <= 1e-10 * (1 + np.abs(ref).max()), (name, d, err)  # (no solve in τ: the fp64 parity number; it was 1e-7 against an fp64 difference)
 
 
 def test_tangent_routine_pure_q_directions(harness, models, oracle, rbd):
@@ -150,5 +150,5 @@ def test_tangent_routine_pure_q_directions(harness, models, oracle, rbd):
     _, dtau = emu_jvp(harness, flat, q, v, vd, None, dq.reshape(B, -1), None, None, None, ntan)
     got = dtau.reshape(B, ntan, flat.nv)
     for d in range(ntan):
-        ref = fd_jvp(oracle, flat, q, v, vd, fext, dq[:, d], np.zeros_like(v), np.zeros_like(vd), fext)
-        assert np.abs(got[:, d] - ref).max() <= 1e-7 * (1 + np.abs(ref).max())
+        ref = quad_jvp(oracle, flat, q, v, vd, None, dq[:, d], None, None, None)
+        assert np.abs(got[:, d] - ref).max() <= 1e-10 * (1 + np.abs(ref).max())

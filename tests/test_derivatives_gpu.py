@@ -1,24 +1,16 @@
 """Forward-mode derivatives of inverse_dynamics! and dynamics! on the GPU (header 700: rbd_inverse_dynamics_jvp, rbd_dynamics_jvp,
-rbd_inverse_dynamics_derivatives, rbd_dynamics_derivatives): tangents against a 4th-order central difference of the oracle, the reference's own autodiff
-identities (test/test_mechanism_algorithms.jl:600-652), Jacobian columns against JVPs, fp32 against fp64, and the edge cases."""
+rbd_inverse_dynamics_derivatives, rbd_dynamics_derivatives): tangents and full Jacobians against the quad-precision oracle (oracle.jvp, oracle.jacobians: exact
+to double rounding, in raw coordinates; the bounds: tests/derivative_parity.py), the reference's own autodiff identities (test/test_mechanism_algorithms.jl:600-652), Jacobian columns against JVPs, fp32 against fp64, and the edge cases."""
 import numpy as np
 import pytest
 import torch
 
-from conftest import rand_inputs
+from conftest import LIMBS, rand_inputs
+from derivative_parity import assert_no_solve, assert_solve_forward, cond_M, jvp_directions
 
 pytestmark = pytest.mark.gpu
 
 FD_MODELS = ["atlas_floating", "atlas_fixed", "valkyrie_floating", "double_pendulum", "randmech1", "randmech2", "randmech3", "inner_floating", "mixed20", "chain70"]
-H = 1e-3
-
-
-def central_difference(f):
-    """f'(0) from 4th-order central differences at h = 1e-3 and h / 2, Richardson-combined (6th order): dynamics! of a humanoid (cond(M) ~ 5e5) has large
-    higher derivatives, and the plain 4th-order difference at 1e-3 is itself off by ~3e-6 of the column scale there."""
-    d = lambda h: (8 * (f(h) - f(-h)) - (f(2 * h) - f(-2 * h))) / (12 * h)
-    return (16 * d(H / 2) - d(H)) / 15
-
 
 def model(rbd, models, name):
     if name == "chain70":  # a tree of more than 64 bodies: the any-size tables
@@ -53,30 +45,28 @@ def close(got, ref, tol, what=""):
 @pytest.mark.parametrize("layout", ["aos", "soa"])
 @pytest.mark.parametrize("name", FD_MODELS)
 def test_jvp_against_central_difference(rbd, oracle, models, name, layout):
+    """Against the central difference of the oracle evaluated in QUAD precision (exact to double rounding; it was an fp64 difference, good to 1e-7): inverse
+    dynamics at the fp64 parity number 1e-10, dynamics state by state at C · cond₂(M_b) · eps64 with the model's measured C (profiles/derivative_parity.txt)."""
     flat = model(rbd, models, name)
     B, ntan = (4096, 1) if name == "atlas_floating" else (16, 2)
-    rng = np.random.default_rng(3)
     q, v, tau, fext = rand_inputs(rbd, flat, B, 11, fext=True)
-    vd = rng.standard_normal((B, flat.nv))
-    dq = rng.standard_normal((B, ntan, flat.nq))  # (not projected on any quaternion's unit sphere: raw-coordinate derivatives)
-    dv = rng.standard_normal((B, ntan, flat.nv))
-    dvd = rng.standard_normal((B, ntan, flat.nv))
-    dtau = rng.standard_normal((B, ntan, flat.nv))
-    dfe = rng.standard_normal((B, ntan, 6 * flat.n_bodies))
+    vd = np.random.default_rng(13).standard_normal((B, flat.nv))
+    d = jvp_directions(flat, B, ntan)  # (dq not projected on any quaternion's unit sphere: raw-coordinate derivatives)
     s = make_state(rbd, flat, q, v, layout=layout)
     flat2 = lambda a: dev(a.reshape(B, -1), s)
-    out = torch.full_like(flat2(dv), float("nan"))
-    rbd.inverse_dynamics_jvp_(out, s, dev(vd, s), ntan, dq=flat2(dq), dv=flat2(dv), dvd=flat2(dvd), externalwrenches=dev(fext, s), dexternalwrenches=flat2(dfe))
+    out = torch.full_like(flat2(d["v"]), float("nan"))
+    rbd.inverse_dynamics_jvp_(out, s, dev(vd, s), ntan, dq=flat2(d["q"]), dv=flat2(d["v"]), dvd=flat2(d["vd"]), externalwrenches=dev(fext, s), dexternalwrenches=flat2(d["f"]))
     got = host(out, s).reshape(B, ntan, flat.nv)
-    for d in range(ntan):
-        ref = central_difference(lambda h: oracle.inverse_dynamics(flat, q + h * dq[:, d], v + h * dv[:, d], vd + h * dvd[:, d], fext + h * dfe[:, d]))
-        close(got[:, d], ref, 1e-7, ("inverse_dynamics", name, d))
-    out = torch.full_like(flat2(dv), float("nan"))
-    rbd.dynamics_jvp_(out, s, ntan, torques=dev(tau, s), dq=flat2(dq), dv=flat2(dv), dtorques=flat2(dtau), externalwrenches=dev(fext, s), dexternalwrenches=flat2(dfe))
+    ref = oracle.jvp(flat, oracle.WHAT_INVERSE_DYNAMICS, q, v, vd, fext, d["q"], d["v"], d["vd"], d["f"])
+    for k in range(ntan):
+        assert_no_solve(got[:, k], ref[:, k], name, "jvp inverse_dynamics %s %d" % (layout, k))
+    out = torch.full_like(flat2(d["v"]), float("nan"))
+    rbd.dynamics_jvp_(out, s, ntan, torques=dev(tau, s), dq=flat2(d["q"]), dv=flat2(d["v"]), dtorques=flat2(d["tau"]), externalwrenches=dev(fext, s), dexternalwrenches=flat2(d["f"]))
     got = host(out, s).reshape(B, ntan, flat.nv)
-    for d in range(ntan):
-        ref = central_difference(lambda h: oracle.dynamics(flat, q + h * dq[:, d], v + h * dv[:, d], tau + h * dtau[:, d], fext + h * dfe[:, d]))
-        close(got[:, d], ref, 1e-6, ("dynamics", name, d))  # (the difference itself: two Richardson pairs of randmech2 differ by 1e-7 of the scale)
+    ref = oracle.jvp(flat, oracle.WHAT_DYNAMICS, q, v, tau, fext, d["q"], d["v"], d["tau"], d["f"])
+    kappa = cond_M(oracle, flat, q)
+    for k in range(ntan):
+        assert_solve_forward(got[:, k], ref[:, k], kappa, name, "jvp dynamics %s %d" % (layout, k))
     assert "tangent" in rbd.last_kernel(s)
 
 
@@ -89,6 +79,27 @@ def jacobians(rbd, s, flat, vd, tau, fext=None):
     rbd.dynamics_derivatives_(s, tau, Aq, Av, Ainv, externalwrenches=fext, vdout=vd_out)
     v3 = lambda t, cols: rbd.jacobian_view(t, s, nv, cols).double().cpu().numpy()
     return dict(tq=v3(Tq, nq), tv=v3(Tv, nv), M=v3(M, nv), tau=host(tau_out, s), aq=v3(Aq, nq), av=v3(Av, nv), Minv=v3(Ainv, nv), vd=host(vd_out, s))
+
+
+@pytest.mark.parametrize("layout", ["aos", "soa"])
+@pytest.mark.parametrize("name", FD_MODELS + LIMBS)
+def test_jacobians_against_the_quad_oracle(rbd, oracle, models, name, layout):
+    """The full Jacobians of both entry points, external wrenches present, against unit-direction derivatives of the quad-precision oracle in raw coordinates:
+    ∂τ/∂(q, v, v̇) at 1e-10, ∂v̇/∂(q, v, τ) state by state at the model's C · cond₂(M_b) · eps64.  8 states: a full Jacobian costs ~2 (nq + 2 nv) quad evaluations."""
+    flat = model(rbd, models, name)
+    B = 8
+    q, v, tau, fext = rand_inputs(rbd, flat, B, 11, fext=True)
+    vd = np.random.default_rng(13).standard_normal((B, flat.nv))
+    s = make_state(rbd, flat, q, v, layout=layout)
+    J = jacobians(rbd, s, flat, dev(vd, s), dev(tau, s), fext=dev(fext, s))
+    T = oracle.jacobians(flat, oracle.WHAT_INVERSE_DYNAMICS, q, v, vd, fext)
+    A = oracle.jacobians(flat, oracle.WHAT_DYNAMICS, q, v, tau, fext)
+    for key, ref in (("tq", T["q"]), ("tv", T["v"]), ("M", T["x"]), ("tau", T["val"])):
+        assert_no_solve(J[key], ref, name, "jacobian %s %s" % (key, layout))
+    kappa = cond_M(oracle, flat, q)
+    for key, ref in (("aq", A["q"]), ("av", A["v"]), ("Minv", A["x"])):
+        assert_solve_forward(J[key], ref, kappa, name, "jacobian %s %s" % (key, layout))
+    close(J["vd"], A["val"], 1e-10, "vdot")
 
 
 @pytest.mark.parametrize("layout", ["aos", "soa"])
@@ -170,15 +181,16 @@ def test_fp32_against_fp64(rbd, oracle, models, name):
     rng = np.random.default_rng(6)
     vd = rng.standard_normal((B, flat.nv))
     dq, dv, dt = (rng.standard_normal((B, ntan * n)) for n in (flat.nq, flat.nv, flat.nv))
-    res = {}
-    for dtype in (torch.float64, torch.float32):
-        s = make_state(rbd, flat, q, v, dtype=dtype)
-        a = torch.zeros((B, flat.nv * ntan), dtype=dtype, device="cuda")
-        b = torch.zeros_like(a)
-        rbd.inverse_dynamics_jvp_(a, s, dev(vd, s), ntan, dq=dev(dq, s), dv=dev(dv, s))
-        rbd.dynamics_jvp_(b, s, ntan, torques=dev(tau, s), dq=dev(dq, s), dv=dev(dv, s), dtorques=dev(dt, s))
-        res[dtype] = (a.double().cpu().numpy().reshape(B, ntan, -1), b.double().cpu().numpy().reshape(B, ntan, -1))
-    (a64, b64), (a32, b32) = res[torch.float64], res[torch.float32]
+    # the fp64 side is the quad-precision oracle, not the library's fp64 kernels: an error shared by both GPU precisions does not cancel
+    D = lambda a, n: a.reshape(B, ntan, n)
+    a64 = oracle.jvp(flat, oracle.WHAT_INVERSE_DYNAMICS, q, v, vd, None, D(dq, flat.nq), D(dv, flat.nv))
+    b64 = oracle.jvp(flat, oracle.WHAT_DYNAMICS, q, v, tau, None, D(dq, flat.nq), D(dv, flat.nv), D(dt, flat.nv))
+    s = make_state(rbd, flat, q, v, dtype=torch.float32)
+    a = torch.zeros((B, flat.nv * ntan), dtype=torch.float32, device="cuda")
+    b = torch.zeros_like(a)
+    rbd.inverse_dynamics_jvp_(a, s, dev(vd, s), ntan, dq=dev(dq, s), dv=dev(dv, s))
+    rbd.dynamics_jvp_(b, s, ntan, torques=dev(tau, s), dq=dev(dq, s), dv=dev(dv, s), dtorques=dev(dt, s))
+    a32, b32 = a.double().cpu().numpy().reshape(B, ntan, -1), b.double().cpu().numpy().reshape(B, ntan, -1)
     for d in range(ntan):
         assert np.abs(a32[:, d] - a64[:, d]).max() <= 1e-4 * np.abs(a64[:, d]).max()
     # the dynamics! tangents: the cond-scaled forward-error criterion of tests/test_gpu_parity.py:26-35 (a solve with M), state by state

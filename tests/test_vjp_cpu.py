@@ -1,8 +1,8 @@
 """Reverse-mode derivatives of inverse_dynamics! without a GPU (header 700 additions): rbd_inverse_dynamics_vjp and rbd_dynamics_vjp are declared and
 exported, and the per-state adjoint routine of their kernel (csrc/rbd_adjoint.hpp adjoint_rnea_state), compiled as plain C++ for the host beside the
 tangent routine (csrc/rbd_tangent.hpp tangent_rnea_state), is exactly its transpose: ⟨λ, J d⟩ = ⟨Jᵀλ, d⟩ for random cotangents and directions over
-(q, v, v̇, f_ext), quaternion directions off the unit sphere included.  q̄, v̄ are also checked against a central difference of the oracle's λᵀτ, and
-v̇̄ against Mλ."""
+(q, v, v̇, f_ext), quaternion directions off the unit sphere included.  q̄, v̄, v̇̄ are also checked against Jᵀλ from the quad-precision oracle's Jacobians
+(oracle.jacobians), f̄ext against its derivative along every wrench coordinate, and v̇̄ against Mλ."""
 import ctypes
 import hashlib
 import os
@@ -158,24 +158,19 @@ def test_adjoint_is_the_transpose_of_the_tangent(harness, models, oracle, rbd, n
 
 @pytest.mark.parametrize("name", MODELS)
 def test_adjoint_against_the_oracle(harness, models, oracle, rbd, name):
-    """q̄, v̄ against a central difference of the oracle's λᵀτ along every coordinate; v̇̄ = Mλ with M from the oracle; f̄ext = −(subtree sums of Sλ)
-    is checked by the dot-product test above."""
+    """q̄, v̄, v̇̄ against Jᵀλ with the Jacobians of the quad-precision oracle, f̄ext against λᵀ ∂τ/∂f_ext from its derivative along every wrench coordinate, at the
+    fp64 parity number 1e-10 (no solve in τ); v̇̄ = Mλ with M from the oracle."""
     flat = models[name]
     B = 3
     rng, q, v, vd, fext = inputs(rbd, flat, B, 23, True)
     lam = rng.standard_normal((B, flat.nv))
-    _, qb, vb, vdb, _ = emu_vjp(harness, flat, q, v, vd, fext, lam)
-    f = lambda qq, vv: np.sum(lam * oracle.inverse_dynamics(flat, qq, vv, vd, fext), axis=1)
-    h = 1e-4
-    for x, xb, n in ((q, qb, flat.nq), (v, vb, flat.nv)):
-        fd = np.zeros((B, n))
-        for k in range(n):
-            def at(s):
-                xx = x.copy()
-                xx[:, k] += s
-                return f(xx, v) if x is q else f(q, xx)
-            fd[:, k] = (8 * (at(h) - at(-h)) - (at(2 * h) - at(-2 * h))) / (12 * h)
-        assert np.abs(xb - fd).max() <= 1e-7 * (1 + np.abs(fd).max()), (name, np.abs(xb - fd).max())
+    _, qb, vb, vdb, fb = emu_vjp(harness, flat, q, v, vd, fext, lam)
+    J = oracle.jacobians(flat, oracle.WHAT_INVERSE_DYNAMICS, q, v, vd, fext)
+    nf = 6 * flat.n_bodies
+    Jf = oracle.jvp(flat, oracle.WHAT_INVERSE_DYNAMICS, q, v, vd, fext, dfext=np.tile(np.eye(nf)[None], (B, 1, 1)))  # [b, wrench coordinate, i]
+    for got, ref in ((qb, np.einsum("bij,bi->bj", J["q"], lam)), (vb, np.einsum("bij,bi->bj", J["v"], lam)), (vdb, np.einsum("bij,bi->bj", J["x"], lam)),
+                     (fb, np.einsum("bji,bi->bj", Jf, lam))):
+        assert np.abs(got - ref).max() <= 1e-10 * (1 + np.abs(ref).max()), (name, np.abs(got - ref).max())
     Mo = oracle.mass_matrix(flat, q)
     Ms = np.tril(Mo) + np.transpose(np.tril(Mo, -1), (0, 2, 1))
     ref = np.einsum("bij,bj->bi", Ms, lam)

@@ -1,5 +1,6 @@
 """Reverse-mode derivatives of inverse_dynamics! and dynamics! on the GPU (header 700 additions: rbd_inverse_dynamics_vjp, rbd_dynamics_vjp, and the
-torch.autograd functions of rigidbodydynamics.jl_amd/autograd.py): VJPs against Jᵀλ from the full Jacobians, the external-wrench pullback against JVPs,
+torch.autograd functions of rigidbodydynamics.jl_amd/autograd.py): VJPs and backward() against Jᵀλ from the Jacobians of the quad-precision oracle (exact to
+double rounding; the bounds: tests/derivative_parity.py), VJPs against Jᵀλ from the library's full Jacobians, the external-wrench pullback against JVPs,
 values against the library's own calls, fp32 against fp64, the edge cases, allocation, gradcheck (reverse and forward mode) and loss.backward()."""
 import ctypes
 
@@ -8,6 +9,7 @@ import pytest
 import torch
 
 from conftest import rand_inputs
+from derivative_parity import assert_no_solve, assert_solve_forward, cond_M
 from test_derivatives_gpu import close, dev, host, jacobians, make_state, model
 
 pytestmark = pytest.mark.gpu
@@ -59,6 +61,66 @@ def test_vjp_equals_transposed_jacobians(rbd, models, name, layout):
     close(vdb, host(r.vd, s), 1e-12, "vdot")
 
 
+Tr = lambda X, y: np.einsum("bij,bi->bj", X, y)  # Xᵀ y per state
+
+
+def quad_transposed(oracle, flat, q, v, vd, tau, fext, lam, w, wrench=False):
+    """Jᵀλ of inverse dynamics and Jᵀw of dynamics formed in numpy from the quad-precision oracle's Jacobians: (q̄, v̄, v̇̄[, f̄ext]), (q̄, v̄, τ̄[, f̄ext]); the
+    wrench part from its directional derivative along every wrench coordinate."""
+    T = oracle.jacobians(flat, oracle.WHAT_INVERSE_DYNAMICS, q, v, vd, fext)
+    A = oracle.jacobians(flat, oracle.WHAT_DYNAMICS, q, v, tau, fext)
+    a, b = [Tr(T[k], lam) for k in "qvx"], [Tr(A[k], w) for k in "qvx"]
+    if wrench:
+        E = np.tile(np.eye(6 * flat.n_bodies)[None], (q.shape[0], 1, 1))  # [b, wrench coordinate, :]
+        a.append(np.einsum("bji,bi->bj", oracle.jvp(flat, oracle.WHAT_INVERSE_DYNAMICS, q, v, vd, fext, dfext=E), lam))
+        b.append(np.einsum("bji,bi->bj", oracle.jvp(flat, oracle.WHAT_DYNAMICS, q, v, tau, fext, dfext=E), w))
+    return a, b
+
+
+@pytest.mark.parametrize("layout", ["aos", "soa"])
+@pytest.mark.parametrize("name", MODELS)
+def test_vjp_against_the_quad_oracle(rbd, oracle, models, name, layout):
+    """(q̄, v̄, v̇̄ / τ̄, f̄ext) against Jᵀλ from the QUAD Jacobians, external wrenches present: inverse dynamics at 1e-10, dynamics state by state at the model's
+    C · cond₂(M_b) · eps64 (profiles/derivative_parity.txt).  f̄ext on the small models (6 n_bodies more directions)."""
+    flat = model(rbd, models, name)
+    B = 8
+    q, v, tau, fext = rand_inputs(rbd, flat, B, 11, fext=True)
+    rng = np.random.default_rng(8)
+    vd = rng.standard_normal((B, flat.nv))
+    lam, w = rng.standard_normal((B, flat.nv)), rng.standard_normal((B, flat.nv))
+    wrench = name in ("mixed20", "inner_floating")
+    s = make_state(rbd, flat, q, v, layout=layout)
+    (qa, va, vda, fa, _), (qb, vb, tb, fb, _) = vjps(rbd, s, flat, dev(vd, s), dev(tau, s), lam, w, fext=dev(fext, s))
+    ra, rb = quad_transposed(oracle, flat, q, v, vd, tau, fext, lam, w, wrench)
+    kappa = cond_M(oracle, flat, q)
+    for key, got, ref in zip(("q̄", "v̄", "v̇̄", "f̄ext"), (qa, va, vda, fa), ra):
+        assert_no_solve(got, ref, name, "vjp inverse_dynamics %s %s" % (key, layout))
+    for key, got, ref in zip(("q̄", "v̄", "τ̄", "f̄ext"), (qb, vb, tb, fb), rb):
+        assert_solve_forward(got, ref, kappa, name, "vjp dynamics %s %s" % (key, layout))
+
+
+def test_loss_backward_against_the_quad_oracle(rbd, oracle, models):
+    """loss.backward() through both autograd functions, external wrenches among the leaves, against Jᵀw from the quad Jacobians."""
+    name = "mixed20"
+    flat = models[name]
+    B = 8
+    q, v, tau, fext = rand_inputs(rbd, flat, B, 11, fext=True)
+    rng = np.random.default_rng(14)
+    vd, w = rng.standard_normal((B, flat.nv)), rng.standard_normal((B, flat.nv))
+    s = make_state(rbd, flat, q, v)
+    ra, rb = quad_transposed(oracle, flat, q, v, vd, tau, fext, w, w, True)
+    leaf = lambda a: dev(a, s).requires_grad_(True)
+    Q, V, A, F, W = leaf(q), leaf(v), leaf(vd), leaf(fext), dev(w, s)
+    (W * rbd.autograd.inverse_dynamics(s, Q, V, A, F)).sum().backward()
+    for key, t, ref in zip(("q", "v", "v̇", "f_ext"), (Q, V, A, F), ra):
+        assert_no_solve(host(t.grad, s), ref, name, "backward inverse_dynamics " + key)
+    Q, V, T, F = leaf(q), leaf(v), leaf(tau), leaf(fext)
+    (W * rbd.autograd.dynamics(s, Q, V, T, F, algorithm="crba")).sum().backward()
+    kappa = cond_M(oracle, flat, q)
+    for key, t, ref in zip(("q", "v", "τ", "f_ext"), (Q, V, T, F), rb):
+        assert_solve_forward(host(t.grad, s), ref, kappa, name, "backward dynamics " + key)
+
+
 @pytest.mark.parametrize("layout", ["aos", "soa"])
 @pytest.mark.parametrize("name", ["atlas_floating", "mixed20", "chain70"])
 def test_wrench_pullback_against_jvp(rbd, models, name, layout):
@@ -95,11 +157,10 @@ def test_fp32_against_fp64(rbd, oracle, models, name):
     rng = np.random.default_rng(10)
     vd = rng.standard_normal((B, flat.nv))
     lam, w = rng.standard_normal((B, flat.nv)), rng.standard_normal((B, flat.nv))
-    res = {}
-    for dtype in (torch.float64, torch.float32):
-        s = make_state(rbd, flat, q, v, dtype=dtype)
-        res[dtype] = vjps(rbd, s, flat, dev(vd, s), dev(tau, s), lam, w)
-    (a64, b64), (a32, b32) = res[torch.float64], res[torch.float32]
+    # the fp64 side is Jᵀλ from the quad-precision oracle's Jacobians, not the library's fp64 kernels: an error shared by both GPU precisions does not cancel
+    a64, b64 = quad_transposed(oracle, flat, q, v, vd, tau, None, lam, w)
+    s = make_state(rbd, flat, q, v, dtype=torch.float32)
+    a32, b32 = vjps(rbd, s, flat, dev(vd, s), dev(tau, s), lam, w)
     for k in range(3):  # q̄, v̄, v̇̄ of inverse dynamics
         assert np.abs(a32[k] - a64[k]).max() <= 1e-4 * np.abs(a64[k]).max(), k
     # dynamics: a solve with M — the cond-scaled forward-error criterion of tests/test_gpu_parity.py:26-35, state by state
