@@ -471,6 +471,30 @@ int rbd_dynamics_vjp(rbd_ws_t* ws, int32_t B, const void* q, const void* v, cons
 int rbd_simulate_vjp(rbd_ws_t* ws, int32_t B, void* q, void* v, const void* tau, const void* fext, double dt, int32_t nsteps,
                      void* q_bar, void* v_bar, void* tau_bar, void* fext_bar, const rbd_opts_t* opts);
 
+/* Point kinematics (700 addition): positions, velocities, accelerations and Jacobians of P points fixed to bodies, and the pullback of positions and
+ * velocities.  Points are expressed in the ROOT frame and paths run from the world: the reference's transform(state, point, world), point_velocity,
+ * point_acceleration and point_jacobian! of path(world → body).  Tree mechanisms only (RBD_ERR_HAS_LOOPS: loop joints are out of scope here, and so
+ * is relative_acceleration between two bodies); fp32 and fp64, both layouts, trees of any size, every tree joint type.
+ * rbd_workspace_set_points: P points from HOST arrays, point k fixed to body body[k] (a flat-model body index, 0 … n_bodies − 1; several points may share
+ * a body) at r[3k … 3k + 2] in that body's frame — the frame whose transform to root the per-body outputs return.  The call copies the points and builds
+ * the path tables; it may allocate and synchronise.  npoints == 0 clears the points; a body index out of range is RBD_ERR_INVALID_ARGUMENT. */
+int rbd_workspace_set_points(rbd_ws_t* ws, int32_t npoints, const int32_t* body, const double* r);
+/* Every output is nullable; batch buffers in the layout of opts, RBD_MEM_HOST as rbd_geometric_jacobian.  Per state:
+ *  - pos (3P) = R_b r + p_b;  vel (3P) = ω_b × pos + v_b with (ω_b; v_b) the body's twist with respect to the world (needs v);
+ *  - acc (3P) = α_b × pos + a_b + ω_b × vel with (α_b; a_b) the body's spatial acceleration relative to the world, without gravity (needs v; a NULL
+ *    vdot means v̇ = 0: acc is then the bias term J̇v of task-space control);
+ *  - jac (3·nv·P): for point k a 3×nv column-major block whose column of a velocity coordinate of a joint on path(world → body[k]) is
+ *    ang(S) × pos + lin(S), S that coordinate's motion subspace column in the root frame; the other columns are written as zeros.
+ * No points set, a NULL q, or vel / acc without v: RBD_ERR_INVALID_ARGUMENT; B == 0 is a successful no-op.  The call neither allocates nor synchronises
+ * (device memory).  rbd_workspace_last_kernel names the kernel afterwards. */
+int rbd_point_kinematics(rbd_ws_t* ws, int32_t B, const void* q, const void* v, const void* vdot, void* pos, void* vel, void* acc, void* jac,
+                         const rbd_opts_t* opts);
+/* The pullback of (pos, vel): one cotangent per output and state, pos_bar and vel_bar of 3P values each, either nullable (zero) but not both.
+ * q_bar (nq) and v_bar (nv) are nullable and OVERWRITTEN; the pullback is in the RAW coordinates q, exactly as rbd_inverse_dynamics_vjp defines them.
+ * Device pointers only; errors as the other VJPs.  The first call of a workspace allocates the adjoint scratch (unless a reverse-mode call did). */
+int rbd_point_kinematics_vjp(rbd_ws_t* ws, int32_t B, const void* q, const void* v, const void* pos_bar, const void* vel_bar, void* q_bar, void* v_bar,
+                             const rbd_opts_t* opts);
+
 /* ---- diagnostics ------------------------------------------------------------ */
 const char* rbd_status_string(int status);
 const char* rbd_last_hip_error(void);   /* thread-local text of the last HIP failure     */
@@ -486,7 +510,8 @@ const char* rbd_workspace_last_kernel(const rbd_ws_t* ws);
  * 500: rbd_mass_matrix_solve_packed, rbd_gatherv.  600: rbd_jit_check_walk_object; no size limit left on any entry point; program family 11; family 1 in fp64.
  * 700: forward-mode derivatives — rbd_inverse_dynamics_jvp, rbd_dynamics_jvp, rbd_inverse_dynamics_derivatives, rbd_dynamics_derivatives;
  *      added to 700 without a new version: rbd_simulate_jvp, rbd_simulate_step_derivatives (derivatives of simulate steps);
- *      rbd_inverse_dynamics_vjp, rbd_dynamics_vjp (reverse mode); rbd_simulate_vjp (reverse mode through simulate steps). */
+ *      rbd_inverse_dynamics_vjp, rbd_dynamics_vjp (reverse mode); rbd_simulate_vjp (reverse mode through simulate steps);
+ *      rbd_workspace_set_points, rbd_point_kinematics, rbd_point_kinematics_vjp (point kinematics). */
 #define RBD_HIP_H_VERSION 700
 int rbd_version(void);
 /* Run-time specialisation.  The one-lane-per-state kernels (mass_matrix! and mass_matrix! + Cholesky at large batches) exist in a second form

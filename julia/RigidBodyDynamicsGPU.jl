@@ -30,7 +30,7 @@ using LinearAlgebra
 
 export BatchedMechanismState, BatchedDynamicsResult, DeviceMatrix, RbdComm, gather!, gatherv!, mass_matrix_solve_packed!, synchronize, librbd_hip, TorqueTable, PDControl,
     inverse_dynamics_jvp!, dynamics_jvp!, inverse_dynamics_derivatives!, dynamics_derivatives!, simulate_jvp!, simulate_step_derivatives!,
-    inverse_dynamics_vjp!, dynamics_vjp!, simulate_vjp!
+    inverse_dynamics_vjp!, dynamics_vjp!, simulate_vjp!, set_points!, point_kinematics!, point_jacobian!, point_velocity!, point_kinematics_vjp!
 
 const librbd_hip = Ref("librbd_hip.so")   # set to <repo>/rigidbodydynamics.jl_amd/csrc/librbd_hip.so
 const libhip = Ref("libamdhip64.so")
@@ -762,6 +762,49 @@ function geometric_jacobian!(out::Buffer{T}, state::BatchedMechanismState{T}, ba
         state.ws, B, state.q, state.model.bodyindex[base], state.model.bodyindex[body], out, opts(state)), "rbd_geometric_jacobian")
     finish(state)
     out
+end
+
+# ---- point kinematics (700 addition): P points fixed to bodies, expressed in the root frame, paths from the world — transform(state, point, world),
+# point_velocity, point_acceleration and point_jacobian! (src/mechanism_algorithms.jl:168-189) over a batch.  Tree mechanisms only.
+
+"""`set_points!(state, bodies, r)` — point k is fixed to `bodies[k]` at `r[:, k]` (3 × P, in that body's frame); the library copies them. An empty list clears them."""
+function set_points!(state::BatchedMechanismState, bodies::AbstractVector{<:RigidBody}, r::AbstractMatrix{<:Real})
+    checkmodcount(state)
+    P = length(bodies)
+    size(r) == (3, P) || throw(DimensionMismatch("r must be 3 × P"))
+    idx = Int32[state.model.bodyindex[b] for b in bodies]
+    rr = Vector{Float64}(vec(r))
+    check(ccall((:rbd_workspace_set_points, librbd_hip[]), Cint, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float64}), state.ws, P, idx, rr), "rbd_workspace_set_points")
+    state
+end
+
+"""`point_kinematics!(state; pos, vel, acc, jac, v̇)` — every output optional: `pos`, `vel`, `acc` 3P × B, `jac` (3·nv·P) × B (per point a 3 × nv column-major
+block, zero off the point's path); without `v̇` the acceleration is the bias term J̇v (`rbd_point_kinematics`)."""
+function point_kinematics!(state::BatchedMechanismState{T}; pos = nothing, vel = nothing, acc = nothing, jac = nothing, v̇ = nothing) where {T}
+    checkmodcount(state)
+    B = batchsize(state)
+    check(ccall((:rbd_point_kinematics, librbd_hip[]), Cint, (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, state.q, state.v, nullable(v̇), nullable(pos), nullable(vel), nullable(acc), nullable(jac), opts(state)), "rbd_point_kinematics")
+    finish(state)
+    nothing
+end
+"`point_jacobian!(out, state)` — the point Jacobians of the points of `set_points!`, (3·nv·P) × B"
+point_jacobian!(out::Buffer, state::BatchedMechanismState) = (point_kinematics!(state; jac = out); out)
+"`point_velocity!(out, state)` — the velocities of the points of `set_points!` in the root frame, 3P × B"
+point_velocity!(out::Buffer, state::BatchedMechanismState) = (point_kinematics!(state; vel = out); out)
+
+"""`point_kinematics_vjp!(q̄, v̄, state; pos̄, vel̄)` — positions and velocities pulled back to the raw coordinates: q̄ (nq × B) and v̄ (nv × B) are
+overwritten; one of the cotangents `pos̄`, `vel̄` (3P × B) may be `nothing` (`rbd_point_kinematics_vjp`)."""
+function point_kinematics_vjp!(q̄, v̄, state::BatchedMechanismState{T}; pos̄ = nothing, vel̄ = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, B = state.model.nq, state.model.nv, batchsize(state)
+    for (x, n) in ((q̄, nq), (v̄, nv))
+        x === nothing || size(x) == (n, B) || throw(DimensionMismatch("cotangent buffer has wrong size"))
+    end
+    check(ccall((:rbd_point_kinematics_vjp, librbd_hip[]), Cint, (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, state.q, state.v, nullable(pos̄), nullable(vel̄), nullable(q̄), nullable(v̄), opts(state)), "rbd_point_kinematics_vjp")
+    finish(state)
+    q̄, v̄
 end
 
 # ---- multi-GPU: one process per GPU, the batch sharded by state, v̇ gathered over RCCL (SURVEY.md §8 e) ------------------------------

@@ -28,6 +28,7 @@ SYMBOLS = (
     "rbd_simulate_jvp", "rbd_simulate_step_derivatives",
     "rbd_inverse_dynamics_vjp", "rbd_dynamics_vjp",
     "rbd_simulate_vjp",
+    "rbd_workspace_set_points", "rbd_point_kinematics", "rbd_point_kinematics_vjp",
 )
 
 
@@ -93,6 +94,9 @@ def lib():
         L.rbd_inverse_dynamics_vjp.argtypes = [vp, i32] + [vp] * 10 + [ctypes.POINTER(Opts)]
         L.rbd_dynamics_vjp.argtypes = [vp, i32] + [vp] * 10 + [ctypes.POINTER(Opts)]
         L.rbd_simulate_vjp.argtypes = [vp, i32, vp, vp, vp, vp, ctypes.c_double, i32, vp, vp, vp, vp, ctypes.POINTER(Opts)]
+        L.rbd_workspace_set_points.argtypes = [vp, i32, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_double)]
+        L.rbd_point_kinematics.argtypes = [vp, i32] + [vp] * 7 + [ctypes.POINTER(Opts)]
+        L.rbd_point_kinematics_vjp.argtypes = [vp, i32] + [vp] * 6 + [ctypes.POINTER(Opts)]
         L.rbd_model_chain_plan.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), i32]
         L.rbd_model_track_plan.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(ctypes.c_double), i32]
         L.rbd_comm_unique_id.argtypes = [vp]

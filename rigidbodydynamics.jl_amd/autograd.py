@@ -1,5 +1,5 @@
 """torch.autograd through the library: `tau = inverse_dynamics(state, q, v, vd, fext)`, `vd = dynamics(state, q, v, tau, fext)` and
-`q1, v1 = simulate(state, q, v, tau, fext, dt=, nsteps=)` are differentiable functions of their tensor arguments, so `loss.backward()` (reverse mode) and `torch.func.jvp` / `torch.autograd.forward_ad` (forward mode) work through
+`q1, v1 = simulate(state, q, v, tau, fext, dt=, nsteps=)` and `pos, vel = point_kinematics(state, q, v)` (reverse mode only) are differentiable functions of their tensor arguments, so `loss.backward()` (reverse mode) and `torch.func.jvp` / `torch.autograd.forward_ad` (forward mode) work through
 them.
 
   - `state` (a MechanismState) supplies the workspace, the batch, the dtype and the layout; q, v, … are tensors of that layout ((B, n) with "aos",
@@ -19,7 +19,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _capi
-from .state import MechanismState, _ptr, _raise, dynamics_vjp_, inverse_dynamics_vjp_, simulate_vjp_
+from .state import MechanismState, _ptr, _raise, dynamics_vjp_, inverse_dynamics_vjp_, point_kinematics_, point_kinematics_vjp_, simulate_vjp_
 
 
 def _prep(state: MechanismState, t: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
@@ -166,6 +166,39 @@ class _Simulate(torch.autograd.Function):
         _raise(_capi.lib().rbd_simulate_jvp(state.ws.handle, state.batch, 1, _ptr(qs), _ptr(vs), _ptr(tau), _ptr(fext), ctypes.c_double(ctx.dt), ctx.nsteps,
                                             _ptr(dq), _ptr(dv), _ptr(dtau), _ptr(dfext), ctypes.byref(opts)), "rbd_simulate_jvp")
         return dq, dv
+
+
+class _PointKinematics(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, state, q, v):
+        f, P = state.flat, getattr(state, "npoints", 0)
+        q, v = _prep(state, q, f.nq, "q"), _prep(state, v, f.nv, "v")
+        pos, vel = _empty(state, 3 * P), _empty(state, 3 * P)
+        point_kinematics_(state, pos, vel, q=q, v=v)
+        ctx.state = state
+        ctx.save_for_backward(q, v)
+        return pos, vel
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, pos_bar, vel_bar):
+        state, f, P = ctx.state, ctx.state.flat, ctx.state.npoints
+        q, v = ctx.saved_tensors
+        _, nq_, nv_ = ctx.needs_input_grad
+        out = (_empty(state, f.nq, nq_), _empty(state, f.nv, nv_))
+        if any(o is not None for o in out):
+            point_kinematics_vjp_(state, _prep(state, pos_bar, 3 * P, "pos_bar"), _prep(state, vel_bar, 3 * P, "vel_bar"), out[0], out[1], q=q, v=v)
+        return (None,) + out
+
+    @staticmethod
+    def jvp(ctx, *tangents):
+        raise NotImplementedError("point_kinematics: forward-mode AD is not implemented (use the Jacobian output of point_kinematics_)")
+
+
+def point_kinematics(state: MechanismState, q: torch.Tensor, v: torch.Tensor):
+    """(pos, vel) of the points fixed with `set_points_(state, …)`, each (B, 3P) in the root frame, differentiable in q and v (reverse mode: one
+    rbd_point_kinematics_vjp per backward; the points must not be replaced between forward and backward)."""
+    return _PointKinematics.apply(state, q, v)
 
 
 def inverse_dynamics(state: MechanismState, q: torch.Tensor, v: torch.Tensor, vd: torch.Tensor, fext: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -182,23 +182,108 @@ template <typename T, int N> RBD_HD void local_transform_pullback(int jt, const 
   }
 }
 
+// what the sweeps share: the world's entry (identity, at rest, a = −g) and a joint's coordinates of state `st` (zero past the joint's own, or without the buffer)
+template <typename T> RBD_HD void adj_root_k(const BigModel& M, T* pk) {
+#pragma unroll
+  for (int k = 0; k < 24; ++k) pk[k] = (k < 9 && k % 4 == 0) ? T(1) : T(0);
+  pk[21] = T(-M.gravity[0]); pk[22] = T(-M.gravity[1]); pk[23] = T(-M.gravity[2]);
+}
+template <typename T> RBD_HD void adj_load_q(const AdjArgs<T>& A, long st, int qoff, int nqi, T* qj) {
+#pragma unroll
+  for (int k = 0; k < 7; ++k) qj[k] = k < nqi ? A.q[(long)(qoff + k) * A.Lq.sk + layout_base(A.Lq, st)] : T(0);
+}
+template <typename T> RBD_HD void adj_load_v(const T* x, Layout L, long st, int voff, int nvi, T* xj) {
+#pragma unroll
+  for (int k = 0; k < 6; ++k) xj[k] = (x && k < nvi) ? x[(long)(voff + k) * L.sk + layout_base(L, st)] : T(0);
+}
+
+// Sweep 4's step for body i (K̄_i complete): the kinematic step pulled back to q̄_i, v̄_i, v̇̄_i, and its share added to K̄_parent.  `at(field, body)`: the scratch.
+// Reads K_i, K_parent and K̄_i; of K only (R, p, twist) — the accelerations enter through K̄ alone.  Shared with point_adjoint_state (rbd_point.hpp).
+template <typename T, typename At> RBD_HD void adjoint_kinematic_step(const BigModel& M, const AdjArgs<T>& A, long st, int i, At& at) {
+  const T* rbase = reinterpret_cast<const T*>(M.rb);
+  Body<T> b{};
+  b.parent = M.tbl[4 * i]; b.jtype = M.tbl[4 * i + 1]; b.qoff = M.tbl[4 * i + 2]; b.voff = M.tbl[4 * i + 3];
+  b.state = st; b.valid = true; b.orig = i;
+  const T* rb = rbase + (long)i * RB_STRIDE;
+  const int nqi = joint_nq<T>(b.jtype), nvi = joint_nv(b.jtype);
+  T qj[7], vj[6], aj[6];
+  adj_load_q(A, st, b.qoff, nqi, qj);
+  adj_load_v(A.v, A.Lv, st, b.voff, nvi, vj);
+  adj_load_v(A.vdot, A.Lv, st, b.voff, nvi, aj);
+  T XR[9], Xp[3], tl[6], al[6], pk[24], K[24], Kb[24], pkb[24];
+  local_transform(b, rb, qj, XR, Xp);
+  local_joint_motion(b, rb, vj, tl);
+  local_joint_motion(b, rb, aj, al);
+  if (b.parent >= 0) {
+#pragma unroll
+    for (int k = 0; k < 24; ++k) pk[k] = at(ADJ_K + k, b.parent);
+  } else {
+    adj_root_k(M, pk);
+  }
+#pragma unroll
+  for (int k = 0; k < 24; ++k) { K[k] = at(ADJ_K + k, i); Kb[k] = at(ADJ_KB + k, i); pkb[k] = T(0); }
+  T tlb[6] = {T(0), T(0), T(0), T(0), T(0), T(0)}, alb[6] = {T(0), T(0), T(0), T(0), T(0), T(0)}, nT[6], nTb[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
+  // a = a_parent + se3_comm(−T, T_parent) + xmotion(R, p, a_local)
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { pkb[18 + k] = Kb[18 + k]; nT[k] = -K[12 + k]; }
+  xmotion_adj(K, K + 9, al, Kb + 18, Kb, Kb + 9, alb);
+  se3_comm_adj(nT, pk + 12, Kb + 18, nTb, pkb + 12);
+  // T = T_parent + xmotion(R, p, t_local)
+#pragma unroll
+  for (int k = 0; k < 6; ++k) { Kb[12 + k] -= nTb[k]; pkb[12 + k] += Kb[12 + k]; }
+  xmotion_adj(K, K + 9, tl, Kb + 12, Kb, Kb + 9, tlb);
+  // p = R_parent Xp + p_parent, R = R_parent XR
+  T XRb[9] = {T(0), T(0), T(0), T(0), T(0), T(0), T(0), T(0), T(0)}, Xpb[3] = {T(0), T(0), T(0)};
+#pragma unroll
+  for (int k = 0; k < 3; ++k) pkb[9 + k] = Kb[9 + k];
+  matvec3_adj(pk, Xp, Kb + 9, pkb, Xpb);
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      pkb[3 * r + c] += Kb[3 * r] * XR[3 * c] + Kb[3 * r + 1] * XR[3 * c + 1] + Kb[3 * r + 2] * XR[3 * c + 2];  // R̄ XRᵀ
+      XRb[3 * r + c] += pk[r] * Kb[c] + pk[3 + r] * Kb[3 + c] + pk[6 + r] * Kb[6 + c];    // R_parentᵀ R̄
+    }
+  if (b.parent >= 0) {
+#pragma unroll
+    for (int k = 0; k < 24; ++k) at(ADJ_KB + k, b.parent) += pkb[k];
+  }
+  // the joint's coordinates: q̄ through the local transform, v̄ and v̇̄ through the (constant) local motion subspace
+  if (A.qbar && nqi > 0) {
+    T qb[7];
+    if (nqi == 1) {
+      local_transform_pullback<T, 1>(b.jtype, rb, qj, nqi, XRb, Xpb, qb);
+    } else {
+      local_transform_pullback<T, 4>(b.jtype, rb, qj, nqi, XRb, Xpb, qb);
+      // (a floating joint's translation enters linearly, Xp = X_pred,R q[4:7] + X_pred,p: its three coordinates by hand, the Duals stay 4 wide)
+      if (b.jtype == RBD_JOINT_QUAT_FLOATING) matTvec3(rb + RB_XPR, Xpb, qb + 4);
+    }
+#pragma unroll
+    for (int k = 0; k < 7; ++k)
+      if (k < nqi) {
+        T& o = A.qbar[(long)(b.qoff + k) * A.Lq.sk + layout_base(A.Lq, st)];
+        o = A.accum ? o + A.sign * qb[k] : A.sign * qb[k];
+      }
+  }
+  if (A.vbar || A.vdbar) {
+    const T ax[3] = {rb[RB_AXIS], rb[RB_AXIS + 1], rb[RB_AXIS + 2]}, ay[3] = {rb[RB_AXIS2], rb[RB_AXIS2 + 1], rb[RB_AXIS2 + 2]};
+    for (int k = 0; k < nvi; ++k) {
+      T sl[6];
+      subspace_col(b.jtype, ax, ay, k, sl);
+      const long o = (long)(b.voff + k) * A.Lv.sk + layout_base(A.Lv, st);
+      if (A.vbar) A.vbar[o] = A.accum ? A.vbar[o] + A.sign * dot6(sl, tlb) : A.sign * dot6(sl, tlb);
+      if (A.vdbar) A.vdbar[o] = A.accum ? A.vdbar[o] + A.sign * dot6(sl, alb) : A.sign * dot6(sl, alb);
+    }
+  }
+}
+
 // inverse_dynamics! and its pullback for state `st`.  sc: scratch, element (field, body) at (field nb + body) ld + slot
 template <typename T> RBD_HD void adjoint_rnea_state(const BigModel& M, const AdjArgs<T>& A, long st, T* sc, long ld, long slot) {
   auto at = [&](int f, int i) -> T& { return sc[((long)f * M.nb + i) * ld + slot]; };
   const T* rbase = reinterpret_cast<const T*>(M.rb);
-  auto root_k = [&](T* pk) {  // the world: identity, at rest, a = −g
-#pragma unroll
-    for (int k = 0; k < 24; ++k) pk[k] = (k < 9 && k % 4 == 0) ? T(1) : T(0);
-    pk[21] = T(-M.gravity[0]); pk[22] = T(-M.gravity[1]); pk[23] = T(-M.gravity[2]);
-  };
-  auto load_q = [&](int qoff, int nqi, T* qj) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) qj[k] = k < nqi ? A.q[(long)(qoff + k) * A.Lq.sk + layout_base(A.Lq, st)] : T(0);
-  };
-  auto load_v = [&](const T* x, Layout L, int voff, int nvi, T* xj) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) xj[k] = (x && k < nvi) ? x[(long)(voff + k) * L.sk + layout_base(L, st)] : T(0);
-  };
+  auto root_k = [&](T* pk) { adj_root_k(M, pk); };
+  auto load_q = [&](int qoff, int nqi, T* qj) { adj_load_q(A, st, qoff, nqi, qj); };
+  auto load_v = [&](const T* x, Layout L, int voff, int nvi, T* xj) { adj_load_v(x, L, st, voff, nvi, xj); };
   // 1. forward kinematics and newton_euler! (as tangent_rnea_state)
   for (int i = 0; i < M.nb; ++i) {
     Body<T> b{};
@@ -310,80 +395,7 @@ template <typename T> RBD_HD void adjoint_rnea_state(const BigModel& M, const Ad
   }
   // 4. the kinematic step, children first: K̄_i → q̄_i, v̄_i, v̇̄_i and K̄_parent
   for (int i = M.nb - 1; i >= 0; --i) {
-    Body<T> b{};
-    b.parent = M.tbl[4 * i]; b.jtype = M.tbl[4 * i + 1]; b.qoff = M.tbl[4 * i + 2]; b.voff = M.tbl[4 * i + 3];
-    b.state = st; b.valid = true; b.orig = i;
-    const T* rb = rbase + (long)i * RB_STRIDE;
-    const int nqi = joint_nq<T>(b.jtype), nvi = joint_nv(b.jtype);
-    T qj[7], vj[6], aj[6];
-    load_q(b.qoff, nqi, qj);
-    load_v(A.v, A.Lv, b.voff, nvi, vj);
-    load_v(A.vdot, A.Lv, b.voff, nvi, aj);
-    T XR[9], Xp[3], tl[6], al[6], pk[24], K[24], Kb[24], pkb[24];
-    local_transform(b, rb, qj, XR, Xp);
-    local_joint_motion(b, rb, vj, tl);
-    local_joint_motion(b, rb, aj, al);
-    if (b.parent >= 0) {
-#pragma unroll
-      for (int k = 0; k < 24; ++k) pk[k] = at(ADJ_K + k, b.parent);
-    } else {
-      root_k(pk);
-    }
-#pragma unroll
-    for (int k = 0; k < 24; ++k) { K[k] = at(ADJ_K + k, i); Kb[k] = at(ADJ_KB + k, i); pkb[k] = T(0); }
-    T tlb[6] = {T(0), T(0), T(0), T(0), T(0), T(0)}, alb[6] = {T(0), T(0), T(0), T(0), T(0), T(0)}, nT[6], nTb[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
-    // a = a_parent + se3_comm(−T, T_parent) + xmotion(R, p, a_local)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) { pkb[18 + k] = Kb[18 + k]; nT[k] = -K[12 + k]; }
-    xmotion_adj(K, K + 9, al, Kb + 18, Kb, Kb + 9, alb);
-    se3_comm_adj(nT, pk + 12, Kb + 18, nTb, pkb + 12);
-    // T = T_parent + xmotion(R, p, t_local)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) { Kb[12 + k] -= nTb[k]; pkb[12 + k] += Kb[12 + k]; }
-    xmotion_adj(K, K + 9, tl, Kb + 12, Kb, Kb + 9, tlb);
-    // p = R_parent Xp + p_parent, R = R_parent XR
-    T XRb[9] = {T(0), T(0), T(0), T(0), T(0), T(0), T(0), T(0), T(0)}, Xpb[3] = {T(0), T(0), T(0)};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) pkb[9 + k] = Kb[9 + k];
-    matvec3_adj(pk, Xp, Kb + 9, pkb, Xpb);
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        pkb[3 * r + c] += Kb[3 * r] * XR[3 * c] + Kb[3 * r + 1] * XR[3 * c + 1] + Kb[3 * r + 2] * XR[3 * c + 2];  // R̄ XRᵀ
-        XRb[3 * r + c] += pk[r] * Kb[c] + pk[3 + r] * Kb[3 + c] + pk[6 + r] * Kb[6 + c];    // R_parentᵀ R̄
-      }
-    if (b.parent >= 0) {
-#pragma unroll
-      for (int k = 0; k < 24; ++k) at(ADJ_KB + k, b.parent) += pkb[k];
-    }
-    // the joint's coordinates: q̄ through the local transform, v̄ and v̇̄ through the (constant) local motion subspace
-    if (A.qbar && nqi > 0) {
-      T qb[7];
-      if (nqi == 1) {
-        local_transform_pullback<T, 1>(b.jtype, rb, qj, nqi, XRb, Xpb, qb);
-      } else {
-        local_transform_pullback<T, 4>(b.jtype, rb, qj, nqi, XRb, Xpb, qb);
-        // (a floating joint's translation enters linearly, Xp = X_pred,R q[4:7] + X_pred,p: its three coordinates by hand, the Duals stay 4 wide)
-        if (b.jtype == RBD_JOINT_QUAT_FLOATING) matTvec3(rb + RB_XPR, Xpb, qb + 4);
-      }
-#pragma unroll
-      for (int k = 0; k < 7; ++k)
-        if (k < nqi) {
-          T& o = A.qbar[(long)(b.qoff + k) * A.Lq.sk + layout_base(A.Lq, st)];
-          o = A.accum ? o + A.sign * qb[k] : A.sign * qb[k];
-        }
-    }
-    if (A.vbar || A.vdbar) {
-      const T ax[3] = {rb[RB_AXIS], rb[RB_AXIS + 1], rb[RB_AXIS + 2]}, ay[3] = {rb[RB_AXIS2], rb[RB_AXIS2 + 1], rb[RB_AXIS2 + 2]};
-      for (int k = 0; k < nvi; ++k) {
-        T sl[6];
-        subspace_col(b.jtype, ax, ay, k, sl);
-        const long o = (long)(b.voff + k) * A.Lv.sk + layout_base(A.Lv, st);
-        if (A.vbar) A.vbar[o] = A.accum ? A.vbar[o] + A.sign * dot6(sl, tlb) : A.sign * dot6(sl, tlb);
-        if (A.vdbar) A.vdbar[o] = A.accum ? A.vdbar[o] + A.sign * dot6(sl, alb) : A.sign * dot6(sl, alb);
-      }
-    }
+    adjoint_kinematic_step<T>(M, A, st, i, at);
   }
 }
 

@@ -28,6 +28,8 @@
 #include "rbd_tangent_mk.hpp"
 #include "rbd_adjoint.hpp"
 #include "rbd_adjoint_mk.hpp"
+#include "rbd_point.hpp"
+#include "rbd_point_plan.hpp"
 enum { BANK_LDS_PAIRS_HOST = 30 };  // = BANK_LDS_PAIRS of rbd_bank.hpp (16 parked + 14 exchange pairs per lane; checked in rbd_bank_kernels.hip)
 
 using namespace rbd;
@@ -204,6 +206,9 @@ struct rbd_ws {
   // backward pass (d_sav), and the step starts kept (d_sav_ckpt, sav_ckpt_bytes)
   bool sav_ready = false; int sav_nn = 0, sav_nw = 0;
   void* d_sav_joints = nullptr; void* d_sav = nullptr; void* d_sav_ckpt = nullptr; size_t d_sav_bytes = 0, d_sav_ckpt_bytes = 0;
+  // rbd_workspace_set_points: the points' tables (rbd_point.hpp PointPlan; d_pt_i: poff, path, uni, ubeg, upts in one buffer, d_pt_r: the points); the tables of
+  // `tan` are built by then (tan_tbl_ready) without the dynamics! buffers of the derivative entry points
+  bool tan_tbl_ready = false; PointPlan pts{}; void* d_pt_i = nullptr; void* d_pt_r = nullptr;
 };
 
 // RBD_TUNE="key=value,key=value,...": the developer knobs of the tests and sweep scripts in ONE environment variable (batch thresholds between the lane
@@ -1096,7 +1101,7 @@ int rbd_workspace_destroy(rbd_ws_t* w) {
   (void)hipSetDevice(w->device);
   void* ptrs[] = {w->d_big_L, w->d_big_tbl, w->d_big_rb, w->d_big_scratch, w->d_fused_i, w->d_tauwork, w->d_rr_chain_i, w->d_rr_chain_r, w->d_rrtrack_ri, w->d_rrtrack_rr, w->d_rrwalk_wk, w->d_cp_body, w->d_cp_r, w->d_hs_r, w->d_tw, w->d_cw, w->d_s0, w->d_sacc, w->d_sdot, w->d_rows, w->d_walk_wk, w->d_state_ops, w->d_state_cols, w->d_state_sr, w->d_Msoa, w->d_track_ri, w->d_track_rr, w->d_bank_ib[0], w->d_bank_ib[1], w->d_bank_rb[0], w->d_bank_rb[1], w->d_ib, w->d_rb, w->d_nslots, w->d_dof_body, w->d_anc, w->d_row_mask, w->d_M, w->d_c, w->d_K, w->d_k, (void*)w->d_notpd, w->d_body, w->d_scratch, w->d_loop_i, w->d_loop_r, w->d_loop_path, w->d_jt_ref, w->d_voff_ref, w->d_axis_ref, w->d_axis2_ref,
                   w->d_tan_tbl, w->d_tan_rb, w->d_tan_scratch, w->d_tan_M, w->d_tan_L, w->d_tan_c, w->d_tan_vd, w->d_tan_rhs, w->d_tan_x,
-                  w->d_sim_val, w->d_sim_tan, w->d_adj_scratch, w->d_adj_rhs, w->d_adj_lam, w->d_adj_x, w->d_sav_joints, w->d_sav, w->d_sav_ckpt};
+                  w->d_sim_val, w->d_sim_tan, w->d_adj_scratch, w->d_adj_rhs, w->d_adj_lam, w->d_adj_x, w->d_sav_joints, w->d_sav, w->d_sav_ckpt, w->d_pt_i, w->d_pt_r};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (void* p : w->stage) if (p) (void)hipFree(p);
   {
@@ -2646,6 +2651,9 @@ template <typename T> hipError_t launch_tangent_mk_stage(const MkTanArgs<T>& A, 
 size_t adjoint_scratch_elems_per_state(const BigModel& M);
 template <typename T> hipError_t launch_adjoint_rnea(const BigModel& M, const AdjArgs<T>& A, void* scratch, long max_states, hipStream_t s);
 template <typename T> hipError_t launch_stage_rows(int n, long B, const void* x, Layout L, void* out, hipStream_t s);
+template <typename T> hipError_t launch_point_kin(const BigModel& M, const PointPlan& P, const PointArgs<T>& A, hipStream_t s);  // rbd_point_kernels.hip
+template <typename T>
+hipError_t launch_point_adjoint(const BigModel& M, const PointPlan& P, const AdjArgs<T>& A, const PointAdjArgs<T>& C, void* scratch, long max_states, hipStream_t s);
 template <typename T> hipError_t launch_mk_stage_classes(MkAdjArgs<T> A, const int32_t* jn, int nn, const int32_t* jw, int nw, int adjoint, hipStream_t s);
 template <typename T>
 hipError_t launch_tangent_mk_load(long B, int ncol, int nq, int nv, int col0, int unit, const ColOut<T>& sq, const ColOut<T>& sv, const ColOut<T>& sd,
@@ -2655,6 +2663,34 @@ hipError_t launch_tangent_mk_load(long B, int ncol, int nq, int nv, int col0, in
 namespace {
 enum : long { TAN_SCRATCH_CAP = 1L << 30 };  // bytes of tangent scratch at most: larger calls run in slabs of (state, chunk) threads
 
+// the tree in the reference's order (BigModel tables) for every mechanism: built by the first derivative call or by rbd_workspace_set_points
+int tan_tables(rbd_ws* w) {
+  const rbd_model* m = w->model;
+  int st;
+  if (w->tan_tbl_ready) return RBD_OK;
+  if (m->big) {
+    w->tan = w->big;
+  } else {  // the slot-ordered tables back in the reference's order (parents first: rbd_model_create checks it)
+    const int nb = m->nb;
+    std::vector<int32_t> tbl(4 * (size_t)nb);
+    std::vector<double> rb((size_t)nb * RB_STRIDE);
+    for (int i = 0; i < nb; ++i) {
+      const int s = m->slot_of[i];
+      const int32_t* ib = &m->ib[(size_t)s * IB_STRIDE];
+      tbl[4 * i] = ib[IB_PARENT] < 0 ? -1 : m->order[ib[IB_PARENT]];
+      tbl[4 * i + 1] = ib[IB_JTYPE]; tbl[4 * i + 2] = ib[IB_QOFF]; tbl[4 * i + 3] = ib[IB_VOFF];
+      memcpy(&rb[(size_t)i * RB_STRIDE], &m->rb[(size_t)s * RB_STRIDE], sizeof(double) * RB_STRIDE);
+    }
+    if ((st = upload_real(&w->d_tan_rb, rb, w->dtype))) return st;
+    w->tan.nb = nb; w->tan.nq = m->nq; w->tan.nv = m->nv; w->tan.rb = w->d_tan_rb;
+    memcpy(w->tan.gravity, m->gravity, sizeof w->tan.gravity);
+    if ((st = upload(&w->d_tan_tbl, tbl.data(), tbl.size() * sizeof(int32_t)))) return st;
+    w->tan.tbl = (const int32_t*)w->d_tan_tbl;
+  }
+  w->tan_tbl_ready = true;
+  return RBD_OK;
+}
+
 // what every derivative entry point shares, allocated by the first one: the tables in the reference's order, M, its factor, c and v̇
 int tan_base(rbd_ws* w) {
   const rbd_model* m = w->model;
@@ -2662,26 +2698,8 @@ int tan_base(rbd_ws* w) {
   const long B = w->max_batch;
   int st;
   if (!w->tan_ready) {
-    if (m->big) {
-      w->tan = w->big;
-      if ((st = big_scratch(w, w->max_batch))) return st;
-    } else {  // the slot-ordered tables back in the reference's order (parents first: rbd_model_create checks it)
-      const int nb = m->nb;
-      std::vector<int32_t> tbl(4 * (size_t)nb);
-      std::vector<double> rb((size_t)nb * RB_STRIDE);
-      for (int i = 0; i < nb; ++i) {
-        const int s = m->slot_of[i];
-        const int32_t* ib = &m->ib[(size_t)s * IB_STRIDE];
-        tbl[4 * i] = ib[IB_PARENT] < 0 ? -1 : m->order[ib[IB_PARENT]];
-        tbl[4 * i + 1] = ib[IB_JTYPE]; tbl[4 * i + 2] = ib[IB_QOFF]; tbl[4 * i + 3] = ib[IB_VOFF];
-        memcpy(&rb[(size_t)i * RB_STRIDE], &m->rb[(size_t)s * RB_STRIDE], sizeof(double) * RB_STRIDE);
-      }
-      if ((st = upload_real(&w->d_tan_rb, rb, w->dtype))) return st;
-      w->tan.nb = nb; w->tan.nq = m->nq; w->tan.nv = m->nv; w->tan.rb = w->d_tan_rb;
-      memcpy(w->tan.gravity, m->gravity, sizeof w->tan.gravity);
-      if ((st = upload(&w->d_tan_tbl, tbl.data(), tbl.size() * sizeof(int32_t)))) return st;
-      w->tan.tbl = (const int32_t*)w->d_tan_tbl;
-    }
+    if ((st = tan_tables(w))) return st;
+    if (m->big && (st = big_scratch(w, w->max_batch))) return st;
     const size_t nv = (size_t)m->nv;
     if ((st = ensure(&w->d_tan_M, &w->d_tan_M_bytes, es * nv * nv * B)) || (st = ensure(&w->d_tan_L, &w->d_tan_L_bytes, es * nv * nv * B)) ||
         (st = ensure(&w->d_tan_c, &w->d_tan_c_bytes, es * nv * B)) || (st = ensure(&w->d_tan_vd, &w->d_tan_vd_bytes, es * nv * B)))
@@ -2936,6 +2954,16 @@ int sim_tan_run(rbd_ws* w, int32_t B, int layout, void* q, void* v, const void* 
 // ---- reverse mode (header 700 additions): the adjoint RNEA, one thread per state -------------------------------------------------------------------------
 enum : long { ADJ_SCRATCH_CAP = TAN_SCRATCH_CAP };  // bytes of adjoint scratch at most: larger calls run in slabs of states
 
+// the adjoint scratch for max_batch states, in slabs beyond the cap (needs the tables of `tan`): also all that rbd_point_kinematics_vjp allocates
+int adj_scratch_ensure(rbd_ws* w) {
+  if (w->adj_states > 0) return RBD_OK;
+  const size_t per = std::max<size_t>(1, adjoint_scratch_elems_per_state(w->tan) * esize(w));
+  const long states = std::min<long>(w->max_batch, std::max<long>(64, (long)(ADJ_SCRATCH_CAP / per) / 64 * 64));
+  if (int st = ensure(&w->d_adj_scratch, &w->d_adj_scratch_bytes, per * std::max<long>(1, states))) return st;
+  w->adj_states = std::max<long>(1, states);
+  return RBD_OK;
+}
+
 // the first reverse-mode call of a workspace allocates (for max_batch states); every later call only launches
 int adj_ensure(rbd_ws* w) {
   const rbd_model* m = w->model;
@@ -2944,13 +2972,10 @@ int adj_ensure(rbd_ws* w) {
   int st;
   if ((st = tan_base(w))) return st;
   if (w->adj_ready) return RBD_OK;
-  const size_t per = std::max<size_t>(1, adjoint_scratch_elems_per_state(w->tan) * es);
-  const long states = std::min<long>(B, std::max<long>(64, (long)(ADJ_SCRATCH_CAP / per) / 64 * 64));
-  if ((st = ensure(&w->d_adj_scratch, &w->d_adj_scratch_bytes, per * states))) return st;
+  if ((st = adj_scratch_ensure(w))) return st;
   if ((st = ensure(&w->d_adj_rhs, &w->d_adj_rhs_bytes, es * std::max<size_t>(1, nv * B))) || (st = ensure(&w->d_adj_lam, &w->d_adj_lam_bytes, es * std::max<size_t>(1, nv * B))))
     return st;
   if (m->nv > 64 && (st = ensure(&w->d_adj_x, &w->d_adj_x_bytes, es * nv * B))) return st;
-  w->adj_states = states;
   w->adj_ready = true;
   return RBD_OK;
 }
@@ -3306,6 +3331,88 @@ int rbd_simulate_vjp(rbd_ws_t* w, int32_t B, void* q, void* v, const void* tau, 
   Timed t(w);
   w->last_kernel = "value_mk_stage_kernel + adjoint_mk_stage_kernel + tangent_solve_kernel + adjoint_rnea_kernel";
   return by_dtype(w->dtype, [&](auto t) { return sav_run<decltype(t)>(w, B, o.layout, q, v, tau, fext, dt, nsteps, P, q_bar, v_bar, tau_bar, fext_bar); });
+}
+
+// ---- point kinematics (rbd_point.hpp): rbd_workspace_set_points, rbd_point_kinematics, rbd_point_kinematics_vjp -------------------------------------------------
+int rbd_workspace_set_points(rbd_ws_t* w, int32_t npoints, const int32_t* body, const double* r) {
+  if (!w || npoints < 0 || (npoints > 0 && (!body || !r))) return RBD_ERR_INVALID_ARGUMENT;
+  const rbd_model* m = w->model;
+  if (m->nloops > 0) return RBD_ERR_HAS_LOOPS;
+  for (int k = 0; k < npoints; ++k)
+    if (body[k] < 0 || body[k] >= m->nb) return RBD_ERR_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(w->device));
+  HIP_TRY(hipStreamSynchronize(w->stream));  // (a call still running reads the tables replaced here)
+  if (w->d_pt_i) { HIP_TRY(hipFree(w->d_pt_i)); w->d_pt_i = nullptr; }
+  if (w->d_pt_r) { HIP_TRY(hipFree(w->d_pt_r)); w->d_pt_r = nullptr; }
+  w->pts = PointPlan{};
+  if (npoints == 0) return RBD_OK;
+  int st;
+  if ((st = tan_tables(w))) return st;
+  const PointPlanTables T = point_plan(m->nb, m->parent_ref.data(), npoints, body);
+  const std::vector<int32_t>&poff = T.poff, &path = T.path, &uni = T.uni, &ubeg = T.ubeg, &upts = T.upts;
+  std::vector<int32_t> all;
+  const size_t o_path = poff.size(), o_uni = o_path + path.size(), o_ubeg = o_uni + uni.size(), o_upts = o_ubeg + ubeg.size();
+  for (const std::vector<int32_t>* v : {&poff, &path, &uni, &ubeg, &upts}) all.insert(all.end(), v->begin(), v->end());
+  if ((st = upload(&w->d_pt_i, all.data(), all.size() * sizeof(int32_t)))) return st;
+  if ((st = upload_real(&w->d_pt_r, std::vector<double>(r, r + 3 * (size_t)npoints), w->dtype))) return st;
+  const int32_t* d = (const int32_t*)w->d_pt_i;
+  w->pts = PointPlan{npoints, (int32_t)uni.size(), d, d + o_path, d + o_uni, d + o_ubeg, d + o_upts, w->d_pt_r};
+  return RBD_OK;
+}
+
+int rbd_point_kinematics(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* vdot, void* pos, void* vel, void* acc, void* jac,
+                         const rbd_opts_t* opts) {
+  Opts o;
+  int st = begin_call(w, B, opts, kAnySize, &o);
+  if (st != RBD_OK) return st;
+  const rbd_model* m = w->model;
+  if (m->nloops > 0) return RBD_ERR_HAS_LOOPS;
+  if (w->pts.np == 0 || !q || ((vel || acc) && missing(v, m->nv))) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  const long P = w->pts.np;
+  const size_t row = esize(w) * B;
+  HostIO io(w, o.memory);
+  const void *dq, *dv, *dvd;
+  void *dpos, *dvel, *dacc, *djac;
+  if ((st = io.in(q, row * m->nq, &dq)) || (st = io.in(v, row * m->nv, &dv)) || (st = io.in(vdot, row * m->nv, &dvd)) || (st = io.out(pos, row * 3 * P, &dpos)) ||
+      (st = io.out(vel, row * 3 * P, &dvel)) || (st = io.out(acc, row * 3 * P, &dacc)) || (st = io.out(jac, row * 3 * P * m->nv, &djac)))
+    return st;
+  w->last_kernel = "point_kin_kernel";
+  {
+    Timed t(w);
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) {
+      using T = decltype(t);
+      PointArgs<T> A{};
+      A.B = B; A.q = (const T*)dq; A.v = (const T*)dv; A.vdot = (const T*)dvd;
+      A.Lq = layout_of(o.layout, m->nq, B); A.Lv = layout_of(o.layout, m->nv, B); A.L3 = layout_of(o.layout, 3 * P, B); A.Lj = layout_of(o.layout, 3 * P * m->nv, B);
+      A.pos = (T*)dpos; A.vel = (T*)dvel; A.acc = (T*)dacc; A.jac = (T*)djac;
+      return launch_point_kin<T>(w->tan, w->pts, A, w->stream);
+    }));
+  }
+  return io.finish();
+}
+
+int rbd_point_kinematics_vjp(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* pos_bar, const void* vel_bar, void* q_bar, void* v_bar,
+                             const rbd_opts_t* opts) {
+  Opts o;
+  int st = tan_check(w, B, opts, &o);
+  if (st != RBD_OK) return st;
+  const rbd_model* m = w->model;
+  if (w->pts.np == 0 || missing(q, m->nq) || missing(v, m->nv) || (!pos_bar && !vel_bar)) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0 || (!q_bar && !v_bar)) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  if ((st = adj_scratch_ensure(w))) return st;
+  Timed t(w);
+  w->last_kernel = "point_adjoint_kernel";
+  HIP_TRY(by_dtype(w->dtype, [&](auto t) {
+    using T = decltype(t);
+    AdjArgs<T> A = adj_args<T>(w, B, o.layout, q, v, nullptr, nullptr);
+    A.qbar = (T*)q_bar; A.vbar = (T*)v_bar;
+    PointAdjArgs<T> C{(const T*)pos_bar, (const T*)vel_bar, layout_of(o.layout, 3L * w->pts.np, B)};
+    return launch_point_adjoint<T>(w->tan, w->pts, A, C, w->d_adj_scratch, w->adj_states, w->stream);
+  }));
+  return RBD_OK;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // rbd_tangent_kernels.hip — the kernels of the derivative entry points (rbd_inverse_dynamics_jvp, rbd_dynamics_jvp, rbd_inverse_dynamics_derivatives,
-// rbd_dynamics_derivatives, rbd_simulate_jvp, rbd_simulate_step_derivatives, rbd_inverse_dynamics_vjp, rbd_dynamics_vjp, rbd_simulate_vjp): the tangent RNEA
+// rbd_dynamics_derivatives, rbd_simulate_jvp, rbd_simulate_step_derivatives, rbd_inverse_dynamics_vjp, rbd_dynamics_vjp, rbd_simulate_vjp, rbd_point_kinematics_vjp): the tangent RNEA
 // (rbd_tangent.hpp) with one thread per (state, chunk of TAN_CHUNK directions), the multi-right-hand-side triangular solve of dynamics! tangents against the
 // Cholesky factor of M, the tangent of the integrator's stage map (rbd_tangent_mk.hpp) with one thread per (state, joint, chunk), the adjoint RNEA
 // (rbd_adjoint.hpp) with one thread per state, and the stage map's values and pullback (rbd_adjoint_mk.hpp) with one thread per (state, joint) of a
@@ -9,6 +9,7 @@
 #include "rbd_adjoint.hpp"
 #include "rbd_tangent_mk.hpp"
 #include "rbd_adjoint_mk.hpp"
+#include "rbd_point.hpp"
 #include "rbd_internal.hpp"
 
 namespace rbd {
@@ -213,6 +214,25 @@ template <typename T> hipError_t launch_adjoint_rnea(const BigModel& M, const Ad
   return hipSuccess;
 }
 
+// the pullback of rbd_point_kinematics (rbd_point.hpp point_adjoint_state): one thread per state over the union of the points' paths, the same scratch and slabs
+template <typename T>
+__global__ __launch_bounds__(64) void point_adjoint_kernel(BigModel M, PointPlan P, AdjArgs<T> A, PointAdjArgs<T> C, long s0, long ns, T* __restrict__ scratch) {
+  const long slot = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= ns) return;
+  point_adjoint_state<T>(M, P, A, C, s0 + slot, scratch, ns, slot);
+}
+
+template <typename T>
+hipError_t launch_point_adjoint(const BigModel& M, const PointPlan& P, const AdjArgs<T>& A, const PointAdjArgs<T>& C, void* scratch, long max_states, hipStream_t s) {
+  for (long s0 = 0; s0 < A.B; s0 += max_states) {
+    const long ns = A.B - s0 < max_states ? A.B - s0 : max_states;
+    hipLaunchKernelGGL((point_adjoint_kernel<T>), dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, s, M, P, A, C, s0, ns, (T*)scratch);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 // an n × B batch buffer of layout L copied batch-innermost (row r of state b at r B + b: the right-hand side tri_solve_col reads)
 template <typename T> __global__ __launch_bounds__(256) void stage_rows_kernel(int n, long B, const T* __restrict__ x, Layout L, T* __restrict__ out) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -356,6 +376,7 @@ template <typename T> hipError_t launch_mk_stage_classes(MkAdjArgs<T> A, const i
   template hipError_t launch_tangent_mk_load<T>(long, int, int, int, int, int, const ColOut<T>&, const ColOut<T>&, const ColOut<T>&, const ColOut<T>&,   \
                                                 const ColOut<T>&, const ColOut<T>&, hipStream_t);                                                        \
   template hipError_t launch_adjoint_rnea<T>(const BigModel&, const AdjArgs<T>&, void*, long, hipStream_t);                                              \
+  template hipError_t launch_point_adjoint<T>(const BigModel&, const PointPlan&, const AdjArgs<T>&, const PointAdjArgs<T>&, void*, long, hipStream_t);         \
   template hipError_t launch_stage_rows<T>(int, long, const void*, Layout, void*, hipStream_t);                                                        \
   template hipError_t launch_mk_stage_classes<T>(MkAdjArgs<T>, const int32_t*, int, const int32_t*, int, int, hipStream_t);
 RBD_TAN_INST(double)

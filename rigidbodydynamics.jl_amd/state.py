@@ -702,6 +702,71 @@ def jacobian_view(t: torch.Tensor, state: MechanismState, rows: int, cols: int) 
     return per.reshape(per.shape[0], cols, rows).transpose(1, 2)
 
 
+# ---- point kinematics (rbd_workspace_set_points, rbd_point_kinematics, rbd_point_kinematics_vjp): points fixed to bodies, expressed in the root frame, paths
+# from the world — the reference's transform(state, point, world), point_velocity, point_acceleration and point_jacobian!.  Tree mechanisms only.
+
+def set_points_(state: MechanismState, bodies, r):
+    """Fix P points to bodies: point k to flat-model body `bodies[k]` (0 … n_bodies − 1; several points may share a body) at `r[k]` (P, 3) in that body's frame.
+    The library copies them; an empty list clears them.  May be called again with another P."""
+    bodies = np.ascontiguousarray(np.asarray(bodies, dtype=np.int32).reshape(-1))
+    r = np.ascontiguousarray(np.asarray(r, dtype=np.float64).reshape(-1, 3))
+    if r.shape[0] != bodies.shape[0]:
+        raise DimensionMismatch(f"r: expected shape ({bodies.shape[0]}, 3), got {tuple(r.shape)}")
+    state.ws.use_current_stream()
+    st = _capi.lib().rbd_workspace_set_points(state.ws.handle, int(bodies.shape[0]), bodies.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                              r.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    _raise(st, "rbd_workspace_set_points")
+    state.npoints = int(bodies.shape[0])
+
+
+def point_kinematics_(state: MechanismState, pos: Optional[torch.Tensor] = None, vel: Optional[torch.Tensor] = None, acc: Optional[torch.Tensor] = None,
+                      jac: Optional[torch.Tensor] = None, vd: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None):
+    """The points of `set_points_` in the root frame, every output optional: `pos`, `vel`, `acc` (B, 3P) and `jac` (B, 3·nv·P: per point a 3 × nv column-major
+    block, `point_jacobian_view`; columns off the point's path are zero).  `vd` None: v̇ = 0, and `acc` is the bias term J̇v.  `q` / `v` default to the state's."""
+    f, P = state.flat, getattr(state, "npoints", 0)
+    q = state.q if q is None else q
+    v = state.v if v is None else v
+    state._check(q, f.nq, "q")
+    state._check(v, f.nv, "v")
+    state._check(vd, f.nv, "v̇")
+    for t, what in ((pos, "pos"), (vel, "vel"), (acc, "acc")):
+        state._check(t, 3 * P, what)
+    state._check(jac, 3 * f.nv * P, "jac")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_point_kinematics(state.ws.handle, state.batch, _ptr(q), _ptr(v), _ptr(vd), _ptr(pos), _ptr(vel), _ptr(acc), _ptr(jac), ctypes.byref(opts))
+    _raise(st, "rbd_point_kinematics")
+    return pos, vel, acc, jac
+
+
+def point_kinematics_vjp_(state: MechanismState, pos_bar: Optional[torch.Tensor] = None, vel_bar: Optional[torch.Tensor] = None,
+                          q_bar: Optional[torch.Tensor] = None, v_bar: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None,
+                          v: Optional[torch.Tensor] = None):
+    """(pos, vel) of `point_kinematics_` pulled back: with the cotangents `pos_bar`, `vel_bar` (B, 3P; either may be None, not both), q_bar (B, nq) and v_bar
+    (B, nv) are overwritten with (∂(pos, vel)/∂q)ᵀ and (∂(pos, vel)/∂v)ᵀ applied to them, in the raw coordinates q as the other VJPs."""
+    f, P = state.flat, getattr(state, "npoints", 0)
+    q = state.q if q is None else q
+    v = state.v if v is None else v
+    state._check(q, f.nq, "q")
+    state._check(v, f.nv, "v")
+    state._check(pos_bar, 3 * P, "pos_bar")
+    state._check(vel_bar, 3 * P, "vel_bar")
+    state._check(q_bar, f.nq, "q_bar")
+    state._check(v_bar, f.nv, "v_bar")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_point_kinematics_vjp(state.ws.handle, state.batch, _ptr(q), _ptr(v), _ptr(pos_bar), _ptr(vel_bar), _ptr(q_bar), _ptr(v_bar),
+                                              ctypes.byref(opts))
+    _raise(st, "rbd_point_kinematics_vjp")
+    return q_bar, v_bar
+
+
+def point_jacobian_view(t: torch.Tensor, state: MechanismState, P: int, nv: int) -> torch.Tensor:
+    """The `jac` output of `point_kinematics_` as (B, P, 3, nv).  A view when the layout allows, else a copy."""
+    per = t if state.layout == "aos" else t.t()
+    return per.reshape(per.shape[0], P, nv, 3).transpose(2, 3)
+
+
 def unpack_lower(packed, nv: int):
     """(B, nv (nv + 1) / 2) packed lower triangles (LAPACK 'L': columns back to back from their diagonals down) -> (B, nv, nv) with the strict upper part zero."""
     import numpy as np
