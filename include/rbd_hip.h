@@ -495,6 +495,28 @@ int rbd_point_kinematics(rbd_ws_t* ws, int32_t B, const void* q, const void* v, 
 int rbd_point_kinematics_vjp(rbd_ws_t* ws, int32_t B, const void* q, const void* v, const void* pos_bar, const void* vel_bar, void* q_bar, void* v_bar,
                              const rbd_opts_t* opts);
 
+/* Reverse mode through soft contact (700 addition): the pullbacks of rbd_contact_dynamics and of rbd_dynamics_contact for a mechanism with contact points and
+ * an environment — the reference's default point model (Hunt–Crossley normal force, viscoelastic Coulomb friction, half-spaces), differentiated on the branch
+ * the forward pass takes per (point, half-space) pair: outside (every cotangent zero), clamped normal force, sticking, slipping.  On a branch boundary the
+ * model is not differentiable and the result is that of the branch taken; a Hunt–Crossley exponent n < 1 at zero penetration is not finite.
+ * Semantics as the other VJPs: raw coordinates q, device pointers only (RBD_MEM_HOST: RBD_ERR_UNSUPPORTED), loop joints RBD_ERR_HAS_LOOPS, fp32 and fp64,
+ * both layouts, trees of any size; a mechanism without contact points or without an environment: RBD_ERR_INVALID_ARGUMENT (as rbd_contact_dynamics);
+ * a NULL q, v or s, or every cotangent NULL: RBD_ERR_INVALID_ARGUMENT; B == 0 is a successful no-op.  s (ns = 3·points·half-spaces) is const: the VJPs do
+ * not reset it.  Every output is nullable and OVERWRITTEN.  The first call of a workspace allocates (what every reverse-mode call shares, the contact
+ * points' path tables — kept apart from rbd_workspace_set_points' —, the per-point cotangents); no later call allocates or synchronises.
+ * rbd_workspace_last_kernel names contact_adjoint_kernel afterwards.
+ * rbd_contact_dynamics_vjp — pullback of contact_dynamics!: (cw_bar [6·n_bodies], sdot_bar [ns], s_out_bar [ns]) -> (q_bar, v_bar, s_bar); s_out is the
+ * friction state after the resets; any cotangent nullable (zero), not all three. */
+int rbd_contact_dynamics_vjp(rbd_ws_t* ws, int32_t B, const void* q, const void* v, const void* s, const void* cw_bar, const void* sdot_bar,
+                             const void* s_out_bar, void* q_bar, void* v_bar, void* s_bar, const rbd_opts_t* opts);
+/* rbd_dynamics_contact_vjp — pullback of dynamics!(result, state, τ, wext) with contact points, the ODE form (q, v, s, τ, wext) -> (v̇, ṡ, s after the
+ * resets): the forward contact launch, rbd_dynamics_vjp's pass at the total wrenches (its f̄ext is their cotangent: fext_bar, and the contact wrenches'),
+ * the contact model's pullback, and the contact points' kinematics pulled back and added to q̄, v̄.  vdot_bar may be NULL (zero) when sdot_bar or s_out_bar
+ * is given; vdot_out (nv) and sdot_out (ns) are nullable value outputs (the CRBA + Cholesky route, as rbd_dynamics_vjp). */
+int rbd_dynamics_contact_vjp(rbd_ws_t* ws, int32_t B, const void* q, const void* v, const void* s, const void* tau, const void* fext,
+                             const void* vdot_bar, const void* sdot_bar, const void* s_out_bar, void* vdot_out, void* sdot_out,
+                             void* q_bar, void* v_bar, void* s_bar, void* tau_bar, void* fext_bar, const rbd_opts_t* opts);
+
 /* ---- diagnostics ------------------------------------------------------------ */
 const char* rbd_status_string(int status);
 const char* rbd_last_hip_error(void);   /* thread-local text of the last HIP failure     */
@@ -511,7 +533,8 @@ const char* rbd_workspace_last_kernel(const rbd_ws_t* ws);
  * 700: forward-mode derivatives — rbd_inverse_dynamics_jvp, rbd_dynamics_jvp, rbd_inverse_dynamics_derivatives, rbd_dynamics_derivatives;
  *      added to 700 without a new version: rbd_simulate_jvp, rbd_simulate_step_derivatives (derivatives of simulate steps);
  *      rbd_inverse_dynamics_vjp, rbd_dynamics_vjp (reverse mode); rbd_simulate_vjp (reverse mode through simulate steps);
- *      rbd_workspace_set_points, rbd_point_kinematics, rbd_point_kinematics_vjp (point kinematics). */
+ *      rbd_workspace_set_points, rbd_point_kinematics, rbd_point_kinematics_vjp (point kinematics);
+ *      rbd_contact_dynamics_vjp, rbd_dynamics_contact_vjp (reverse mode through soft contact). */
 #define RBD_HIP_H_VERSION 700
 int rbd_version(void);
 /* Run-time specialisation.  The one-lane-per-state kernels (mass_matrix! and mass_matrix! + Cholesky at large batches) exist in a second form

@@ -30,7 +30,8 @@ using LinearAlgebra
 
 export BatchedMechanismState, BatchedDynamicsResult, DeviceMatrix, RbdComm, gather!, gatherv!, mass_matrix_solve_packed!, synchronize, librbd_hip, TorqueTable, PDControl,
     inverse_dynamics_jvp!, dynamics_jvp!, inverse_dynamics_derivatives!, dynamics_derivatives!, simulate_jvp!, simulate_step_derivatives!,
-    inverse_dynamics_vjp!, dynamics_vjp!, simulate_vjp!, set_points!, point_kinematics!, point_jacobian!, point_velocity!, point_kinematics_vjp!
+    inverse_dynamics_vjp!, dynamics_vjp!, simulate_vjp!, set_points!, point_kinematics!, point_jacobian!, point_velocity!, point_kinematics_vjp!,
+    contact_dynamics_vjp!, dynamics_contact_vjp!
 
 const librbd_hip = Ref("librbd_hip.so")   # set to <repo>/rigidbodydynamics.jl_amd/csrc/librbd_hip.so
 const libhip = Ref("libamdhip64.so")
@@ -805,6 +806,42 @@ function point_kinematics_vjp!(q̄, v̄, state::BatchedMechanismState{T}; pos̄ 
         state.ws, B, state.q, state.v, nullable(pos̄), nullable(vel̄), nullable(q̄), nullable(v̄), opts(state)), "rbd_point_kinematics_vjp")
     finish(state)
     q̄, v̄
+end
+
+"""`contact_dynamics_vjp!(q̄, v̄, s̄, state; c̄w, ṡ̄, s̄out)` — `contact_dynamics!` pulled back on the branch each (point, half-space) pair takes: the cotangents
+of the contact wrenches `c̄w` (6·n_bodies × B), of ṡ and of the friction state after the resets (ns × B; each may be `nothing`, not all) give q̄, v̄, s̄
+(overwritten).  `state.s` is read, not reset (`rbd_contact_dynamics_vjp`)."""
+function contact_dynamics_vjp!(q̄, v̄, s̄, state::BatchedMechanismState{T}; c̄w = nothing, ṡ̄ = nothing, s̄out = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, ns, B = state.model.nq, state.model.nv, size(state.s, 1), batchsize(state)
+    for (x, n) in ((q̄, nq), (v̄, nv), (s̄, ns), (ṡ̄, ns), (s̄out, ns))
+        x === nothing || size(x) == (n, B) || throw(DimensionMismatch("cotangent buffer has wrong size"))
+    end
+    check(ccall((:rbd_contact_dynamics_vjp, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, state.q, state.v, state.s, nullable(c̄w), nullable(ṡ̄), nullable(s̄out), nullable(q̄), nullable(v̄), nullable(s̄), opts(state)),
+        "rbd_contact_dynamics_vjp")
+    finish(state)
+    q̄, v̄, s̄
+end
+
+"""`dynamics_contact_vjp!(q̄, v̄, s̄, τ̄, state; v̇̄, ṡ̄, s̄out, torques, externalwrenches, f̄ext, v̇out, ṡout)` — `dynamics!` of a mechanism with contact points
+pulled back, the ODE form (q, v, s, τ, wext) -> (v̇, ṡ, s after the resets), in one call: the cotangents `v̇̄` (nv × B), `ṡ̄`, `s̄out` (ns × B; each may be
+`nothing`, not all) give q̄, v̄, s̄, τ̄ and f̄ext (overwritten).  `state.s` is read, not reset (`rbd_dynamics_contact_vjp`)."""
+function dynamics_contact_vjp!(q̄, v̄, s̄, τ̄, state::BatchedMechanismState{T}; v̇̄ = nothing, ṡ̄ = nothing, s̄out = nothing, torques = nothing,
+        externalwrenches = nothing, f̄ext = nothing, v̇out = nothing, ṡout = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, ns, B = state.model.nq, state.model.nv, size(state.s, 1), batchsize(state)
+    for (x, n) in ((q̄, nq), (v̄, nv), (s̄, ns), (τ̄, nv), (v̇̄, nv), (ṡ̄, ns), (s̄out, ns), (v̇out, nv), (ṡout, ns))
+        x === nothing || size(x) == (n, B) || throw(DimensionMismatch("cotangent buffer has wrong size"))
+    end
+    check(ccall((:rbd_dynamics_contact_vjp, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, state.q, state.v, state.s, nullable(torques), nullable(densewrenches(state, externalwrenches)), nullable(v̇̄), nullable(ṡ̄),
+        nullable(s̄out), nullable(v̇out), nullable(ṡout), nullable(q̄), nullable(v̄), nullable(s̄), nullable(τ̄), nullable(f̄ext), opts(state)),
+        "rbd_dynamics_contact_vjp")
+    finish(state)
+    q̄, v̄, s̄, τ̄
 end
 
 # ---- multi-GPU: one process per GPU, the batch sharded by state, v̇ gathered over RCCL (SURVEY.md §8 e) ------------------------------

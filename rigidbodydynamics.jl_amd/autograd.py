@@ -1,5 +1,6 @@
 """torch.autograd through the library: `tau = inverse_dynamics(state, q, v, vd, fext)`, `vd = dynamics(state, q, v, tau, fext)` and
-`q1, v1 = simulate(state, q, v, tau, fext, dt=, nsteps=)` and `pos, vel = point_kinematics(state, q, v)` (reverse mode only) are differentiable functions of their tensor arguments, so `loss.backward()` (reverse mode) and `torch.func.jvp` / `torch.autograd.forward_ad` (forward mode) work through
+`q1, v1 = simulate(state, q, v, tau, fext, dt=, nsteps=)`, and, reverse mode only, `pos, vel = point_kinematics(state, q, v)` and
+`vd, sd, s_out = dynamics_contact(state, q, v, s, tau, fext)` (a mechanism with contact points) are differentiable functions of their tensor arguments, so `loss.backward()` (reverse mode) and `torch.func.jvp` / `torch.autograd.forward_ad` (forward mode) work through
 them.
 
   - `state` (a MechanismState) supplies the workspace, the batch, the dtype and the layout; q, v, … are tensors of that layout ((B, n) with "aos",
@@ -19,7 +20,8 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _capi
-from .state import MechanismState, _ptr, _raise, dynamics_vjp_, inverse_dynamics_vjp_, point_kinematics_, point_kinematics_vjp_, simulate_vjp_
+from .state import (MechanismState, _ptr, _raise, dynamics_contact_vjp_, dynamics_vjp_, inverse_dynamics_vjp_, point_kinematics_, point_kinematics_vjp_,
+                    simulate_vjp_)
 
 
 def _prep(state: MechanismState, t: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
@@ -193,6 +195,44 @@ class _PointKinematics(torch.autograd.Function):
     @staticmethod
     def jvp(ctx, *tangents):
         raise NotImplementedError("point_kinematics: forward-mode AD is not implemented (use the Jacobian output of point_kinematics_)")
+
+
+class _DynamicsContact(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, state, q, v, s, tau, fext):
+        f = state.flat
+        q, v, s = _prep(state, q, f.nq, "q"), _prep(state, v, f.nv, "v"), _prep(state, s, f.ns, "s")
+        tau, fext = _prep(state, tau, f.nv, "torques"), _prep(state, fext, 6 * f.n_bodies, "externalwrenches")
+        vd, sd, s_out = _empty(state, f.nv), _empty(state, f.ns), s.clone()  # (rbd_dynamics_contact resets the friction state in place: on a copy)
+        state.ws.use_current_stream()
+        opts = state._opts()
+        _raise(_capi.lib().rbd_dynamics_contact(state.ws.handle, state.batch, _ptr(q), _ptr(v), _ptr(s_out), _ptr(tau), _ptr(fext), _ptr(vd), None, _ptr(sd),
+                                                None, None, ctypes.byref(opts)), "rbd_dynamics_contact")
+        ctx.state = state
+        ctx.save_for_backward(q, v, s, tau, fext)
+        return vd, sd, s_out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, vd_bar, sd_bar, s_out_bar):
+        state, f = ctx.state, ctx.state.flat
+        q, v, s, tau, fext = ctx.saved_tensors
+        _, nq_, nv_, ns_, nt_, nf_ = ctx.needs_input_grad
+        out = (_empty(state, f.nq, nq_), _empty(state, f.nv, nv_), _empty(state, f.ns, ns_), _empty(state, f.nv, nt_ and tau is not None),
+               _empty(state, 6 * f.n_bodies, nf_ and fext is not None))
+        if any(o is not None for o in out):
+            dynamics_contact_vjp_(state, _prep(state, vd_bar, f.nv, "vd_bar"), _prep(state, sd_bar, f.ns, "sd_bar"), _prep(state, s_out_bar, f.ns, "s_out_bar"),
+                                  tau, fext, *out, q=q, v=v, s=s)
+        return (None,) + out
+
+
+def dynamics_contact(state: MechanismState, q: torch.Tensor, v: torch.Tensor, s: torch.Tensor, tau: Optional[torch.Tensor] = None,
+                     fext: Optional[torch.Tensor] = None):
+    """(v̇, ṡ, s_out) = dynamics! of a mechanism with contact points and an environment, the ODE form: `s` (B, ns) is the friction state, s_out the same
+    after the resets of the points out of contact (`s` itself is not modified).  Differentiable in q, v, s, tau and fext, reverse mode only: backward through
+    all three outputs is one rbd_dynamics_contact_vjp, the derivative of the branch each (point, half-space) pair takes (outside, clamped, sticking,
+    slipping).  The value is rbd_dynamics_contact's; the derivatives are the CRBA + Cholesky route's, as `dynamics`."""
+    return _DynamicsContact.apply(state, q, v, s, tau, fext)
 
 
 def point_kinematics(state: MechanismState, q: torch.Tensor, v: torch.Tensor):

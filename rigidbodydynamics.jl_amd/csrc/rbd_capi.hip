@@ -209,6 +209,11 @@ struct rbd_ws {
   // rbd_workspace_set_points: the points' tables (rbd_point.hpp PointPlan; d_pt_i: poff, path, uni, ubeg, upts in one buffer, d_pt_r: the points); the tables of
   // `tan` are built by then (tan_tbl_ready) without the dynamics! buffers of the derivative entry points
   bool tan_tbl_ready = false; PointPlan pts{}; void* d_pt_i = nullptr; void* d_pt_r = nullptr;
+  // rbd_contact_dynamics_vjp / rbd_dynamics_contact_vjp: the model's contact points as a PointPlan of their own (a caller's points stay), the per-point
+  // cotangents contact_adjoint_kernel hands to point_adjoint_kernel, the total wrenches' cotangent when the caller takes no fext_bar, and the copy of s the
+  // forward contact launch resets
+  bool ct_ready = false; PointPlan ct_pts{}; void* d_ct_i = nullptr; void* d_ct_r = nullptr; void* d_ct_pbar = nullptr; void* d_ct_vbar = nullptr;
+  void* d_ct_wbar = nullptr; void* d_ct_s = nullptr;
 };
 
 // RBD_TUNE="key=value,key=value,...": the developer knobs of the tests and sweep scripts in ONE environment variable (batch thresholds between the lane
@@ -1101,7 +1106,8 @@ int rbd_workspace_destroy(rbd_ws_t* w) {
   (void)hipSetDevice(w->device);
   void* ptrs[] = {w->d_big_L, w->d_big_tbl, w->d_big_rb, w->d_big_scratch, w->d_fused_i, w->d_tauwork, w->d_rr_chain_i, w->d_rr_chain_r, w->d_rrtrack_ri, w->d_rrtrack_rr, w->d_rrwalk_wk, w->d_cp_body, w->d_cp_r, w->d_hs_r, w->d_tw, w->d_cw, w->d_s0, w->d_sacc, w->d_sdot, w->d_rows, w->d_walk_wk, w->d_state_ops, w->d_state_cols, w->d_state_sr, w->d_Msoa, w->d_track_ri, w->d_track_rr, w->d_bank_ib[0], w->d_bank_ib[1], w->d_bank_rb[0], w->d_bank_rb[1], w->d_ib, w->d_rb, w->d_nslots, w->d_dof_body, w->d_anc, w->d_row_mask, w->d_M, w->d_c, w->d_K, w->d_k, (void*)w->d_notpd, w->d_body, w->d_scratch, w->d_loop_i, w->d_loop_r, w->d_loop_path, w->d_jt_ref, w->d_voff_ref, w->d_axis_ref, w->d_axis2_ref,
                   w->d_tan_tbl, w->d_tan_rb, w->d_tan_scratch, w->d_tan_M, w->d_tan_L, w->d_tan_c, w->d_tan_vd, w->d_tan_rhs, w->d_tan_x,
-                  w->d_sim_val, w->d_sim_tan, w->d_adj_scratch, w->d_adj_rhs, w->d_adj_lam, w->d_adj_x, w->d_sav_joints, w->d_sav, w->d_sav_ckpt, w->d_pt_i, w->d_pt_r};
+                  w->d_sim_val, w->d_sim_tan, w->d_adj_scratch, w->d_adj_rhs, w->d_adj_lam, w->d_adj_x, w->d_sav_joints, w->d_sav, w->d_sav_ckpt, w->d_pt_i, w->d_pt_r,
+                  w->d_ct_i, w->d_ct_r, w->d_ct_pbar, w->d_ct_vbar, w->d_ct_wbar, w->d_ct_s};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (void* p : w->stage) if (p) (void)hipFree(p);
   {
@@ -2403,15 +2409,13 @@ int rbd_model_contact_dims(const rbd_model_t* m, int32_t* n_contact_points, int3
   return RBD_OK;
 }
 
-// contact_dynamics! on device pointers: per-body kinematics (the RNEA launch exports them; its bias torques go to the workspace),
-// then the contact kernel.  dcw / dtw nullable.
-static int run_contact(rbd_ws* w, int32_t B, const Opts& o, const void* dq, const void* dv, void* ds, void* dsd, const void* df, void* dcw, void* dtw) {
+// the per-body kinematics [state][body][24] of (q, v) into w->d_body (the RNEA launch exports them; its bias torques go to the workspace)
+static int run_contact_kinematics(rbd_ws* w, int32_t B, const Opts& o, const void* dq, const void* dv) {
   const rbd_model* m = w->model;
   const size_t es = esize(w);
   int st;
   if ((st = ensure(&w->d_body, &w->d_body_bytes, es * (size_t)m->nb * 24 * B)) || (st = ensure(&w->d_c, &w->d_c_bytes, es * (size_t)m->nv * B))) return st;
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B), Lf = layout_of(o.layout, 6L * m->nb, B);
-  const Layout Ls = layout_of(o.layout, 3L * m->ncp * m->nhs, B);
   if (m->big && (st = big_scratch(w, B))) return st;
   return by_dtype(w->dtype, [&](auto t) -> int {
     using T = decltype(t);
@@ -2421,6 +2425,17 @@ static int run_contact(rbd_ws* w, int32_t B, const Opts& o, const void* dq, cons
     } else {
       HIP_TRY(launch_rnea<T>(w->dm, B, dq, dv, nullptr, nullptr, w->d_c, nullptr, w->d_body, Lq, Lv, Lf, w->stream));
     }
+    return RBD_OK;
+  });
+}
+
+// contact_dynamics! on device pointers: per-body kinematics, then the contact kernel.  dcw / dtw nullable.
+static int run_contact(rbd_ws* w, int32_t B, const Opts& o, const void* dq, const void* dv, void* ds, void* dsd, const void* df, void* dcw, void* dtw) {
+  const rbd_model* m = w->model;
+  if (int st = run_contact_kinematics(w, B, o, dq, dv)) return st;
+  const Layout Lf = layout_of(o.layout, 6L * m->nb, B), Ls = layout_of(o.layout, 3L * m->ncp * m->nhs, B);
+  return by_dtype(w->dtype, [&](auto t) -> int {
+    using T = decltype(t);
     HIP_TRY(launch_contact<T>(w->ctm, B, w->d_body, ds, dsd, df, dcw, dtw, Ls, Lf, w->stream));
     return RBD_OK;
   });
@@ -2688,6 +2703,23 @@ int tan_tables(rbd_ws* w) {
     w->tan.tbl = (const int32_t*)w->d_tan_tbl;
   }
   w->tan_tbl_ready = true;
+  return RBD_OK;
+}
+
+// the tables of np points (point k on reference body body[k] at r[3k … 3k + 2]) on the device: rbd_workspace_set_points, and the model's contact points for
+// the contact VJPs.  *d_i, *d_r: the two buffers (NULL on entry)
+int point_plan_upload(rbd_ws* w, int np, const int32_t* body, const double* r, void** d_i, void** d_r, PointPlan* out) {
+  const rbd_model* m = w->model;
+  int st;
+  const PointPlanTables T = point_plan(m->nb, m->parent_ref.data(), np, body);
+  const std::vector<int32_t>&poff = T.poff, &path = T.path, &uni = T.uni, &ubeg = T.ubeg, &upts = T.upts;
+  std::vector<int32_t> all;
+  const size_t o_path = poff.size(), o_uni = o_path + path.size(), o_ubeg = o_uni + uni.size(), o_upts = o_ubeg + ubeg.size();
+  for (const std::vector<int32_t>* v : {&poff, &path, &uni, &ubeg, &upts}) all.insert(all.end(), v->begin(), v->end());
+  if ((st = upload(d_i, all.data(), all.size() * sizeof(int32_t)))) return st;
+  if ((st = upload_real(d_r, std::vector<double>(r, r + 3 * (size_t)np), w->dtype))) return st;
+  const int32_t* d = (const int32_t*)*d_i;
+  *out = PointPlan{np, (int32_t)uni.size(), d, d + o_path, d + o_uni, d + o_ubeg, d + o_upts, *d_r};
   return RBD_OK;
 }
 
@@ -3027,6 +3059,51 @@ int adj_dyn_vjp(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, 
   return RBD_OK;
 }
 
+// ---- reverse mode through soft contact (header 700 addition): rbd_contact_dynamics_vjp, rbd_dynamics_contact_vjp --------------------------------------------
+// the first contact VJP of a workspace allocates, for max_batch states: what every reverse-mode call shares, the model's contact points as a PointPlan of
+// their own, the per-point cotangents, the total wrenches and their cotangent, the copy of s, and what the forward contact launch writes; no later call does
+int ct_ensure(rbd_ws* w) {
+  const rbd_model* m = w->model;
+  const size_t es = esize(w), B = (size_t)w->max_batch;
+  int st;
+  if ((st = adj_ensure(w))) return st;
+  if (w->ct_ready) return RBD_OK;
+  if (w->ct_pts.np == 0) {
+    for (void** p : {&w->d_ct_i, &w->d_ct_r})  // (left by a call that ran out of memory half way)
+      if (*p) { (void)hipFree(*p); *p = nullptr; }
+    std::vector<double> r(3 * (size_t)m->ncp);
+    for (int i = 0; i < m->ncp; ++i)
+      for (int j = 0; j < 3; ++j) r[3 * (size_t)i + j] = m->cp_r[(size_t)i * CP_STRIDE + CP_LOC + j];
+    if ((st = point_plan_upload(w, m->ncp, m->cp_body.data(), r.data(), &w->d_ct_i, &w->d_ct_r, &w->ct_pts))) return st;
+  }
+  const size_t sizes[4] = {es * 3 * m->ncp * B, es * 3 * m->ncp * B, es * 6 * m->nb * B, es * 3 * m->ncp * m->nhs * B};
+  void** bufs[4] = {&w->d_ct_pbar, &w->d_ct_vbar, &w->d_ct_wbar, &w->d_ct_s};
+  for (int k = 0; k < 4; ++k)
+    if (!*bufs[k]) HIP_TRY(hipMalloc(bufs[k], sizes[k]));
+  if ((st = ensure(&w->d_body, &w->d_body_bytes, es * (size_t)m->nb * 24 * B)) || (st = ensure(&w->d_c, &w->d_c_bytes, es * (size_t)m->nv * B)) ||
+      (st = ensure(&w->d_tw, &w->d_tw_bytes, es * (size_t)6 * m->nb * B)))
+    return st;
+  w->ct_ready = true;
+  return RBD_OK;
+}
+
+// contact_adjoint_kernel at the per-body kinematics in w->d_body, then point_adjoint_kernel over the contact points: the cotangents of the bodies' wrenches
+// (wbar), of ṡ and of s after the resets -> s_bar and (q_bar, v_bar) — ADDED to what these hold with accum (the adjoint RNEA pass wrote its share before)
+template <typename T>
+int ct_adjoint(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, const void* s, const void* wbar, const void* sdot_bar, const void* s_out_bar,
+               void* q_bar, void* v_bar, void* s_bar, int accum) {
+  const rbd_model* m = w->model;
+  if (!q_bar && !v_bar && !s_bar) return RBD_OK;
+  const Layout Ls = layout_of(layout, 3L * m->ncp * m->nhs, B), Lf = layout_of(layout, 6L * m->nb, B), L3 = layout_of(layout, 3L * m->ncp, B);
+  HIP_TRY(launch_contact_adjoint<T>(w->ctm, B, w->d_body, s, wbar, sdot_bar, s_out_bar, s_bar, w->d_ct_pbar, w->d_ct_vbar, Ls, Lf, L3, w->stream));
+  if (!q_bar && !v_bar) return RBD_OK;
+  AdjArgs<T> A = adj_args<T>(w, B, layout, q, v, nullptr, nullptr);
+  A.qbar = (T*)q_bar; A.vbar = (T*)v_bar; A.accum = accum;
+  PointAdjArgs<T> C{(const T*)w->d_ct_pbar, (const T*)w->d_ct_vbar, L3};
+  HIP_TRY(launch_point_adjoint<T>(w->tan, w->ct_pts, A, C, w->d_adj_scratch, w->adj_states, w->stream));
+  return RBD_OK;
+}
+
 // ---- reverse mode through simulate steps (header 700 addition): rbd_simulate_vjp ----------------------------------------------------------------------
 enum : long { SAV_CKPT_CAP = 1L << 30 };  // bytes of step starts kept while every step's fits; beyond that two-level (√n) checkpointing
 
@@ -3348,16 +3425,7 @@ int rbd_workspace_set_points(rbd_ws_t* w, int32_t npoints, const int32_t* body, 
   if (npoints == 0) return RBD_OK;
   int st;
   if ((st = tan_tables(w))) return st;
-  const PointPlanTables T = point_plan(m->nb, m->parent_ref.data(), npoints, body);
-  const std::vector<int32_t>&poff = T.poff, &path = T.path, &uni = T.uni, &ubeg = T.ubeg, &upts = T.upts;
-  std::vector<int32_t> all;
-  const size_t o_path = poff.size(), o_uni = o_path + path.size(), o_ubeg = o_uni + uni.size(), o_upts = o_ubeg + ubeg.size();
-  for (const std::vector<int32_t>* v : {&poff, &path, &uni, &ubeg, &upts}) all.insert(all.end(), v->begin(), v->end());
-  if ((st = upload(&w->d_pt_i, all.data(), all.size() * sizeof(int32_t)))) return st;
-  if ((st = upload_real(&w->d_pt_r, std::vector<double>(r, r + 3 * (size_t)npoints), w->dtype))) return st;
-  const int32_t* d = (const int32_t*)w->d_pt_i;
-  w->pts = PointPlan{npoints, (int32_t)uni.size(), d, d + o_path, d + o_uni, d + o_ubeg, d + o_upts, w->d_pt_r};
-  return RBD_OK;
+  return point_plan_upload(w, npoints, body, r, &w->d_pt_i, &w->d_pt_r, &w->pts);
 }
 
 int rbd_point_kinematics(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* vdot, void* pos, void* vel, void* acc, void* jac,
@@ -3413,6 +3481,66 @@ int rbd_point_kinematics_vjp(rbd_ws_t* w, int32_t B, const void* q, const void* 
     return launch_point_adjoint<T>(w->tan, w->pts, A, C, w->d_adj_scratch, w->adj_states, w->stream);
   }));
   return RBD_OK;
+}
+
+// ---- reverse mode through soft contact (rbd_contact.hpp): rbd_contact_dynamics_vjp, rbd_dynamics_contact_vjp ----------------------------------------------------
+static int contact_vjp_scope(rbd_ws* w, int32_t B, const rbd_opts_t* opts, Opts* o) {
+  if (int st = begin_call(w, B, opts, kAnySize, o)) return st;
+  if (w->model->nloops > 0) return RBD_ERR_HAS_LOOPS;
+  if (w->model->ncp == 0 || w->model->nhs == 0) return RBD_ERR_INVALID_ARGUMENT;  // (as rbd_contact_dynamics: use rbd_dynamics_vjp)
+  if (o->memory != RBD_MEM_DEVICE) return RBD_ERR_UNSUPPORTED;
+  return RBD_OK;
+}
+
+int rbd_contact_dynamics_vjp(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* s, const void* cw_bar, const void* sdot_bar, const void* s_out_bar,
+                             void* q_bar, void* v_bar, void* s_bar, const rbd_opts_t* opts) {
+  Opts o;
+  int st = contact_vjp_scope(w, B, opts, &o);
+  if (st != RBD_OK) return st;
+  if (!q || !v || !s || (!cw_bar && !sdot_bar && !s_out_bar)) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  if ((st = ct_ensure(w))) return st;
+  Timed t(w);
+  w->last_kernel = "contact_adjoint_kernel + point_adjoint_kernel";
+  if ((st = run_contact_kinematics(w, B, o, q, v))) return st;
+  return by_dtype(w->dtype, [&](auto t) { return ct_adjoint<decltype(t)>(w, B, o.layout, q, v, s, cw_bar, sdot_bar, s_out_bar, q_bar, v_bar, s_bar, 0); });
+}
+
+int rbd_dynamics_contact_vjp(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* s, const void* tau, const void* fext, const void* vdot_bar,
+                             const void* sdot_bar, const void* s_out_bar, void* vdot_out, void* sdot_out, void* q_bar, void* v_bar, void* s_bar, void* tau_bar,
+                             void* fext_bar, const rbd_opts_t* opts) {
+  Opts o;
+  int st = contact_vjp_scope(w, B, opts, &o);
+  if (st != RBD_OK) return st;
+  if (!q || !v || !s || (!vdot_bar && !sdot_bar && !s_out_bar)) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  if ((st = ct_ensure(w))) return st;
+  const rbd_model* m = w->model;
+  const size_t es = esize(w);
+  Timed t(w);
+  w->last_kernel = "tangent_solve_kernel + adjoint_rnea_kernel + contact_adjoint_kernel + point_adjoint_kernel";
+  // the forward contact launch resets the friction state of the points outside: on a copy (s is the caller's, const); total wrenches into the workspace
+  HIP_TRY(hipMemcpyAsync(w->d_ct_s, s, es * 3 * m->ncp * m->nhs * B, hipMemcpyDeviceToDevice, w->stream));
+  if ((st = run_contact(w, B, o, q, v, w->d_ct_s, sdot_out, fext, nullptr, w->d_tw))) return st;
+  return by_dtype(w->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    int st;
+    const void* wbar = nullptr;
+    if (vdot_bar) {
+      // v̇ as a function of the total wrenches: its f̄ext is their cotangent — the caller's fext_bar (totalwrenches = fext + contactwrenches) and the contact
+      // wrenches' — and q̄, v̄ are the dynamics' share, which the contact points' is added to
+      void* wb = fext_bar ? fext_bar : ((q_bar || v_bar || s_bar) ? w->d_ct_wbar : nullptr);
+      if ((st = adj_dyn_vjp<T>(w, B, o.layout, q, v, tau, w->d_tw, vdot_bar, vdot_out, q_bar, v_bar, tau_bar, wb))) return st;
+      wbar = wb;
+    } else {  // no cotangent of v̇: τ and fext reach ṡ and s_out through nothing
+      if (vdot_out && (st = tan_dynamics_value<T>(w, B, o.layout, q, v, tau, w->d_tw, vdot_out))) return st;
+      if (tau_bar) HIP_TRY(hipMemsetAsync(tau_bar, 0, es * m->nv * B, w->stream));
+      if (fext_bar) HIP_TRY(hipMemsetAsync(fext_bar, 0, es * 6 * m->nb * B, w->stream));
+    }
+    return ct_adjoint<T>(w, B, o.layout, q, v, s, wbar, sdot_bar, s_out_bar, q_bar, v_bar, s_bar, vdot_bar ? 1 : 0);
+  });
 }
 
 }  // extern "C"

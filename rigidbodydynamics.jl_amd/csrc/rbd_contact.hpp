@@ -1,0 +1,162 @@
+// rbd_contact.hpp — the soft contact model of one (contact point, half-space) pair and its hand-written pullback (rbd_contact_dynamics_vjp,
+// rbd_dynamics_contact_vjp).  The model is the reference's default (src/contact.jl: HuntCrossleyModel :98-119, ViscoelasticCoulombModel :122-178,
+// HalfSpace3D :202-228) with the arithmetic of contact_kernel (rbd_contact_kernels.hip), which stays the forward path:
+//   sep = (pos − h)·n;  outside (sep > 0): f = 0, ẋ = 0, the friction state x is reset to 0
+//   z = −sep, ż = −vel·n, fn = max(0, λ zⁿ ż + k zⁿ)                       Hunt–Crossley
+//   v_t = vel + ż n, f_s⁰ = −k_s x − b v_t, f_s = f_s⁰ · min(1, μ fn / ‖f_s⁰‖)    viscoelastic Coulomb: stick, or slip on the cone
+//   ẋ = (−k_s x − f_s) / b,  f = fn n + f_s,  the body's wrench += (pos × f; f)
+// contact_pair_force<S> is templated on the scalar, like point_kin_state<S>: tests/test_contact_vjp_cpu.py takes J·d from its Dual<double, 1> instantiation
+// and checks contact_pair_adjoint<double> against it.  contact_pair_adjoint is the derivative of the branch the forward pass takes:
+//   outside            every cotangent is zero (x_out = 0 and ẋ = 0 whatever the inputs);
+//   clamped (fn ≤ 0)   the normal force and the slip scale contribute nothing;
+//   sticking           f_s = f_s⁰;
+//   slipping           f_s = f_s⁰ · (μ fn / ‖f_s⁰‖) differentiated in THAT form — sqrt(m2 / n2) has an infinite derivative in m2 at fn = 0;
+//   zⁿ                 n zⁿ⁻¹, which pow gives the one-sided limit of at z = 0 for n ≥ 1 (0, or 1 when n = 1); n < 1 at z = 0 is not finite.
+// On a branch boundary (sep = 0, fn = 0, ‖f_s⁰‖ = μ fn) the model is not differentiable; the pullback is then that of the branch taken.
+#pragma once
+#include "rbd_point.hpp"
+
+namespace rbd {
+
+RBD_HD double ct_val(double x) { return x; }
+RBD_HD float ct_val(float x) { return x; }
+template <typename T, int N> RBD_HD T ct_val(const Dual<T, N>& x) { return x.v; }
+RBD_HD double ct_pow(double x, double n) { return pow(x, n); }
+RBD_HD float ct_pow(float x, float n) { return powf(x, n); }
+RBD_HD double ct_sqrt(double x) { return sqrt(x); }
+RBD_HD float ct_sqrt(float x) { return sqrtf(x); }
+RBD_HD double ct_div(double a, double b) { return a / b; }
+RBD_HD float ct_div(float a, float b) { return a / b; }
+template <typename T, int N> RBD_HD Dual<T, N> ct_pow(const Dual<T, N>& x, T n) {
+  Dual<T, N> r;
+  r.v = ct_pow(x.v, n);
+  const T g = n * ct_pow(x.v, n - T(1));
+#pragma unroll
+  for (int j = 0; j < N; ++j) r.d[j] = g * x.d[j];
+  return r;
+}
+// (at x = 0 the tangent is taken as zero: the one place the model forms sqrt(0) is the slip scale of a clamped pair, whose force is identically zero nearby)
+template <typename T, int N> RBD_HD Dual<T, N> ct_sqrt(const Dual<T, N>& x) {
+  Dual<T, N> r;
+  r.v = ct_sqrt(x.v);
+  const T g = x.v > T(0) ? T(0.5) / r.v : T(0);
+#pragma unroll
+  for (int j = 0; j < N; ++j) r.d[j] = g * x.d[j];
+  return r;
+}
+template <typename T, int N> RBD_HD Dual<T, N> ct_div(const Dual<T, N>& a, const Dual<T, N>& b) {
+  Dual<T, N> r;
+  const T ib = T(1) / b.v;
+  r.v = a.v * ib;
+#pragma unroll
+  for (int j = 0; j < N; ++j) r.d[j] = (a.d[j] - r.v * b.d[j]) * ib;
+  return r;
+}
+
+// One pair.  pos, vel: the contact point in the root frame; x: its friction state for this half-space; c: the point's CP_STRIDE parameters; H: the half-space
+// (point, unit outward normal).  Returns whether the point is inside; f (3) and xd = ẋ (3) are always written (zero outside, where the caller resets x).
+template <typename S> RBD_HD bool contact_pair_force(const S* pos, const S* vel, const S* x, const typename ScalarOf<S>::type* c,
+                                                     const typename ScalarOf<S>::type* H, S* f, S* xd) {
+  using T = typename ScalarOf<S>::type;
+  const T* n = H + 3;
+  const S sep = (pos[0] - H[0]) * n[0] + (pos[1] - H[1]) * n[1] + (pos[2] - H[2]) * n[2];  // separation (contact.jl:224)
+  if (!(ct_val(sep) <= T(0))) {  // reset! the state, zero! the derivative (mechanism_algorithms.jl:714-715)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { f[j] = S(T(0)); xd[j] = S(T(0)); }
+    return false;
+  }
+  const S z = -sep;
+  const S zd = -(vel[0] * n[0] + vel[1] * n[1] + vel[2] * n[2]);
+  const S zn = ct_pow(z, c[CP_HCN]);
+  S fn = c[CP_HCL] * zn * zd + c[CP_HCK] * zn;  // HuntCrossley normal_force (:115-118)
+  if (!(ct_val(fn) > T(0))) fn = S(T(0));
+  S fs[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) fs[j] = (-c[CP_K]) * x[j] - c[CP_B] * (vel[j] + zd * n[j]);  // friction_force (:150-169): the stick force
+  const S n2 = fs[0] * fs[0] + fs[1] * fs[1] + fs[2] * fs[2], m2 = (c[CP_MU] * fn) * (c[CP_MU] * fn);
+  if (ct_val(n2) > ct_val(m2)) {  // clipped to the friction cone
+    const S sc = ct_sqrt(ct_div(m2, n2));
+#pragma unroll
+    for (int j = 0; j < 3; ++j) fs[j] = fs[j] * sc;
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    xd[j] = ((-c[CP_K]) * x[j] - fs[j]) / c[CP_B];  // dynamics! of the friction state (:171-178)
+    f[j] = fn * n[j] + fs[j];
+  }
+  return true;
+}
+
+// The pullback of one pair.  fb, tqb: the cotangent (τ̄q; f̄) of the body's wrench (pos × f; f) (each nullable: zero); xdb: that of ẋ; xob: that of the friction
+// state after the reset (each nullable).  pos_bar, vel_bar, x_bar (3 each) are OVERWRITTEN.  Returns whether the point is inside.
+template <typename T> RBD_HD bool contact_pair_adjoint(const T* pos, const T* vel, const T* x, const T* c, const T* H, const T* fb, const T* tqb, const T* xdb,
+                                                       const T* xob, T* pos_bar, T* vel_bar, T* x_bar) {
+  const T* n = H + 3;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) { pos_bar[j] = T(0); vel_bar[j] = T(0); x_bar[j] = T(0); }
+  const T sep = (pos[0] - H[0]) * n[0] + (pos[1] - H[1]) * n[1] + (pos[2] - H[2]) * n[2];
+  if (!(sep <= T(0))) return false;
+  // the forward values of the branch
+  const T z = -sep, zd = -(vel[0] * n[0] + vel[1] * n[1] + vel[2] * n[2]);
+  const T zn = ct_pow(z, c[CP_HCN]);
+  const T fr = c[CP_HCL] * zn * zd + c[CP_HCK] * zn;
+  const bool pushing = fr > T(0);
+  const T fn = pushing ? fr : T(0);
+  T f0[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) f0[j] = -c[CP_K] * x[j] - c[CP_B] * (vel[j] + zd * n[j]);
+  const T n2 = f0[0] * f0[0] + f0[1] * f0[1] + f0[2] * f0[2], mf = c[CP_MU] * fn;
+  const bool slip = n2 > mf * mf;
+  const T in0 = slip ? T(1) / ct_sqrt(n2) : T(0);  // (n2 > m2 ≥ 0)
+  const T sc = slip ? mf * in0 : T(1);
+  // f = fn n + f_s, the wrench (pos × f; f): f̄ += τ̄q × pos, pos_bar = f × τ̄q
+  T fbar[3] = {fb ? fb[0] : T(0), fb ? fb[1] : T(0), fb ? fb[2] : T(0)};
+  if (tqb) {
+    T f[3], t3[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) f[j] = fn * n[j] + sc * f0[j];
+    cross3(tqb, pos, t3);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) fbar[j] += t3[j];
+    cross3(f, tqb, pos_bar);
+  }
+  T fnb = fbar[0] * n[0] + fbar[1] * n[1] + fbar[2] * n[2];
+  // ẋ = (−k_s x − f_s) / b
+  T fsb[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const T g = xdb ? xdb[j] / c[CP_B] : T(0);
+    fsb[j] = fbar[j] - g;
+    x_bar[j] = -c[CP_K] * g + (xob ? xob[j] : T(0));
+  }
+  // f_s = sc f_s⁰ with sc = μ fn / ‖f_s⁰‖ when slipping: f̄_s⁰ = sc (f̄_s − u (u·f̄_s)), f̄n += μ (u·f̄_s), u = f_s⁰ / ‖f_s⁰‖
+  if (slip) {
+    const T ub = (f0[0] * fsb[0] + f0[1] * fsb[1] + f0[2] * fsb[2]) * in0;
+    fnb += c[CP_MU] * ub;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) fsb[j] = sc * (fsb[j] - f0[j] * in0 * ub);
+  }
+  // f_s⁰ = −k_s x − b v_t, v_t = vel + ż n
+  T zdb = T(0);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    x_bar[j] -= c[CP_K] * fsb[j];
+    vel_bar[j] = -c[CP_B] * fsb[j];
+    zdb += vel_bar[j] * n[j];
+  }
+  // fn = max(0, zⁿ (λ ż + k)), zⁿ pulled back with n zⁿ⁻¹
+  T zb = T(0);
+  if (pushing) {
+    zdb += fnb * c[CP_HCL] * zn;
+    zb = fnb * (c[CP_HCL] * zd + c[CP_HCK]) * c[CP_HCN] * ct_pow(z, c[CP_HCN] - T(1));
+  }
+  // ż = −vel·n, z = −(pos − h)·n
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    vel_bar[j] -= zdb * n[j];
+    pos_bar[j] -= zb * n[j];
+  }
+  return true;
+}
+
+}  // namespace rbd

@@ -7,8 +7,12 @@
 // against every half-space and adds its wrench to its body's; it writes contactwrenches and totalwrenches = wext + contactwrenches
 // (mechanism_algorithms.jl:851-856) for EVERY body, so the forward-dynamics launch that follows reads one wrench buffer.
 // No contact configuration is on a BASELINE hot path: clarity over speed here.
+//
+// contact_adjoint_kernel: the pullback of contact_kernel (rbd_contact.hpp contact_pair_adjoint), one thread per state between the adjoint RNEA pass, whose
+// f̄ext is the cotangent of the wrenches it reads, and point_adjoint_kernel, which reads the per-point cotangents it writes.
 #include "rbd_device.hpp"
 #include "rbd_internal.hpp"
+#include "rbd_contact.hpp"
 
 namespace rbd {
 
@@ -95,6 +99,58 @@ __global__ __launch_bounds__(256) void contact_kernel(ContactModel M, long B, co
   }
 }
 
+// For every contact point: pos and vel again from the exported per-body kinematics, the cotangent (τ̄q; f̄) of its body's wrench (wbar, nullable: zero), the
+// cotangents of ṡ and of s after the resets (sdbar, sobar, nullable) per half-space -> s_bar (nullable) and the point's pos_bar, vel_bar summed over the
+// half-spaces (3 np values per state each, layout L3: what point_adjoint_kernel reads).  Every output element is written.
+template <typename T>
+__global__ __launch_bounds__(256) void contact_adjoint_kernel(ContactModel M, long B, const T* __restrict__ body, const T* __restrict__ s,
+                                                             const T* __restrict__ wbar, const T* __restrict__ sdbar, const T* __restrict__ sobar,
+                                                             T* __restrict__ sbar, T* __restrict__ pbar, T* __restrict__ vbar, Layout Ls, Layout Lf, Layout L3) {
+  const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const T* cp = reinterpret_cast<const T*>(M.cp);
+  const T* hs = reinterpret_cast<const T*>(M.hs);
+  const long bs = b * Ls.sb, bf = b * Lf.sb, b3 = b * L3.sb;
+  for (int ip = 0; ip < M.np; ++ip) {
+    const int body_i = M.cbody[ip];
+    const T* k = body + (b * M.nb + body_i) * 24;
+    const T* c = cp + (long)ip * CP_STRIDE;
+    T pt[3], vel[3], t3[3], wb[6], pb[3] = {T(0), T(0), T(0)}, vb[3] = {T(0), T(0), T(0)};
+    matvec3(k, c + CP_LOC, pt);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) pt[j] += k[9 + j];
+    cross3(k + 12, pt, t3);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) vel[j] = t3[j] + k[15 + j];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) wb[j] = wbar ? wbar[(long)(6 * body_i + j) * Lf.sk + bf] : T(0);
+    for (int h = 0; h < M.nh; ++h) {
+      const long so = (long)(ip * M.nh + h) * 3;
+      T x[3], xdb[3], xob[3], p1[3], v1[3], xb[3];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const long o = (so + j) * Ls.sk + bs;
+        x[j] = s[o];
+        xdb[j] = sdbar ? sdbar[o] : T(0);
+        xob[j] = sobar ? sobar[o] : T(0);
+      }
+      contact_pair_adjoint<T>(pt, vel, x, c, hs + (long)h * 6, wb + 3, wb, xdb, xob, p1, v1, xb);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        pb[j] += p1[j];
+        vb[j] += v1[j];
+        if (sbar) sbar[(so + j) * Ls.sk + bs] = xb[j];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const long o = (long)(3 * ip + j) * L3.sk + b3;
+      pbar[o] = pb[j];
+      vbar[o] = vb[j];
+    }
+  }
+}
+
 // the additional state through a Runge–Kutta step, stage by stage like mk_stage_kernel does (q, v):
 //   stage 0: s0 = s;  stage k = 1..3: acc += b_k ṡ_k, s = s0 + a_{k+1,k} dt ṡ_k;  stage 4: s = s0 + dt (acc + b_4 ṡ_4)
 // with the runge_kutta_4 tableau (ode_integrators.jl:48-55): a = 1/2, 1/2, 1; b = 1/6, 1/3, 1/3, 1/6.
@@ -118,12 +174,23 @@ hipError_t launch_contact(const ContactModel& M, long B, const void* body, void*
   return hipGetLastError();
 }
 template <typename T>
+hipError_t launch_contact_adjoint(const ContactModel& M, long B, const void* body, const void* s, const void* wbar, const void* sdbar, const void* sobar, void* sbar,
+                                  void* pbar, void* vbar, Layout Ls, Layout Lf, Layout L3, hipStream_t st) {
+  contact_adjoint_kernel<T><<<(unsigned)((B + 255) / 256), 256, 0, st>>>(M, B, (const T*)body, (const T*)s, (const T*)wbar, (const T*)sdbar, (const T*)sobar, (T*)sbar,
+                                                                         (T*)pbar, (T*)vbar, Ls, Lf, L3);
+  return hipGetLastError();
+}
+template <typename T>
 hipError_t launch_contact_stage(long n, int stage, double dt, void* s, const void* sdot, void* s0, void* acc, hipStream_t st) {
   contact_stage_kernel<T><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, stage, (T)dt, (T*)s, (const T*)sdot, (T*)s0, (T*)acc);
   return hipGetLastError();
 }
 template hipError_t launch_contact<double>(const ContactModel&, long, const void*, void*, void*, const void*, void*, void*, Layout, Layout, hipStream_t);
 template hipError_t launch_contact<float>(const ContactModel&, long, const void*, void*, void*, const void*, void*, void*, Layout, Layout, hipStream_t);
+template hipError_t launch_contact_adjoint<double>(const ContactModel&, long, const void*, const void*, const void*, const void*, const void*, void*, void*, void*, Layout,
+                                                  Layout, Layout, hipStream_t);
+template hipError_t launch_contact_adjoint<float>(const ContactModel&, long, const void*, const void*, const void*, const void*, const void*, void*, void*, void*, Layout,
+                                                 Layout, Layout, hipStream_t);
 template hipError_t launch_contact_stage<double>(long, int, double, void*, const void*, void*, void*, hipStream_t);
 template hipError_t launch_contact_stage<float>(long, int, double, void*, const void*, void*, void*, hipStream_t);
 

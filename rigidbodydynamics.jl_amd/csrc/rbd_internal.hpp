@@ -71,6 +71,9 @@ namespace rbd {
 template <typename T>
 hipError_t launch_contact(const ContactModel& M, long B, const void* body, void* s, void* sdot, const void* fext, void* contactwrenches, void* totalwrenches,
                           Layout Ls, Layout Lf, hipStream_t st);
+template <typename T>
+hipError_t launch_contact_adjoint(const ContactModel& M, long B, const void* body, const void* s, const void* wbar, const void* sdbar, const void* sobar, void* sbar,
+                                  void* pbar, void* vbar, Layout Ls, Layout Lf, Layout L3, hipStream_t st);
 template <typename T> hipError_t launch_contact_stage(long n, int stage, double dt, void* s, const void* sdot, void* s0, void* acc, hipStream_t st);
 // rbd_walk_kernels.hip: one wavefront per track, one lane per state
 template <typename T>

@@ -144,16 +144,16 @@ RBD_HD void point_kin_state(const BigModel& M, const int32_t* path, int n, const
   }
 }
 
-// (q̄, v̄) = Jᵀ(pos_bar, vel_bar) for state `st` over the union of the paths.  A: q, v and their layouts, qbar / vbar (overwritten: zero off the union), sign 1,
+// (q̄, v̄) = Jᵀ(pos_bar, vel_bar) for state `st` over the union of the paths.  A: q, v and their layouts, qbar / vbar (overwritten: zero off the union; added to with accum), sign 1,
 // no vdot.  sc: the adjoint scratch of adjoint_rnea_state, element (field, body) at (field nb + body) ld + slot; only K and K̄ are used.
 template <typename T> RBD_HD void point_adjoint_state(const BigModel& M, const PointPlan& P, const AdjArgs<T>& A, const PointAdjArgs<T>& C, long st, T* sc, long ld, long slot) {
   auto at = [&](int f, int i) -> T& { return sc[((long)f * M.nb + i) * ld + slot]; };
   const T* rbase = reinterpret_cast<const T*>(M.rb);
   const T* rpt = reinterpret_cast<const T*>(P.r);
-  // the coordinates of joints off every path take no part
-  if (A.qbar)
+  // the coordinates of joints off every path take no part (A.accum: the pullback is ADDED to what qbar / vbar hold — rbd_dynamics_contact_vjp)
+  if (A.qbar && !A.accum)
     for (int k = 0; k < M.nq; ++k) A.qbar[(long)k * A.Lq.sk + layout_base(A.Lq, st)] = T(0);
-  if (A.vbar)
+  if (A.vbar && !A.accum)
     for (int k = 0; k < M.nv; ++k) A.vbar[(long)k * A.Lv.sk + layout_base(A.Lv, st)] = T(0);
   // A. parents first: K = (R, p, twist) (the kinematic half of sweep 1 of adjoint_rnea_state), and K̄ seeded by the points on the body
   for (int u = 0; u < P.nu; ++u) {

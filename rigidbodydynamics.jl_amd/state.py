@@ -1123,3 +1123,70 @@ def bank_plan(flat):
         return {"lanes": v[0].value, "L0": v[1].value, "bodies": (v[2].value, v[3].value), "aba": bool(v[4].value)}
     finally:
         L.rbd_model_destroy(h)
+
+
+# ---- reverse mode through soft contact (rbd_contact_dynamics_vjp, rbd_dynamics_contact_vjp): the reference's default point model differentiated on the branch
+# each (point, half-space) pair takes.  `s` (B, ns) is read, never reset; it defaults to the state's.
+
+def contact_dynamics_vjp_(state: MechanismState, cw_bar: Optional[torch.Tensor] = None, sd_bar: Optional[torch.Tensor] = None,
+                          s_out_bar: Optional[torch.Tensor] = None, q_bar: Optional[torch.Tensor] = None, v_bar: Optional[torch.Tensor] = None,
+                          s_bar: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None,
+                          s: Optional[torch.Tensor] = None):
+    """`contact_dynamics!` pulled back: the cotangents of the contact wrenches `cw_bar` (B, 6·n_bodies), of ṡ `sd_bar` and of the friction state after the
+    resets `s_out_bar` (B, ns) (each may be None, not all) -> q_bar (B, nq), v_bar (B, nv), s_bar (B, ns), overwritten."""
+    f = state.flat
+    q = state.q if q is None else q
+    v = state.v if v is None else v
+    s = state.s if s is None else s
+    state._check(q, f.nq, "q")
+    state._check(v, f.nv, "v")
+    state._check(s, f.ns, "s")
+    state._check(cw_bar, 6 * f.n_bodies, "cw_bar")
+    state._check(sd_bar, f.ns, "sd_bar")
+    state._check(s_out_bar, f.ns, "s_out_bar")
+    state._check(q_bar, f.nq, "q_bar")
+    state._check(v_bar, f.nv, "v_bar")
+    state._check(s_bar, f.ns, "s_bar")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_contact_dynamics_vjp(state.ws.handle, state.batch, _ptr(q), _ptr(v), _ptr(s), _ptr(cw_bar), _ptr(sd_bar), _ptr(s_out_bar),
+                                              _ptr(q_bar), _ptr(v_bar), _ptr(s_bar), ctypes.byref(opts))
+    _raise(st, "rbd_contact_dynamics_vjp")
+    return q_bar, v_bar, s_bar
+
+
+def dynamics_contact_vjp_(state: MechanismState, vd_bar: Optional[torch.Tensor] = None, sd_bar: Optional[torch.Tensor] = None,
+                          s_out_bar: Optional[torch.Tensor] = None, torques: Optional[torch.Tensor] = None, externalwrenches: Optional[torch.Tensor] = None,
+                          q_bar: Optional[torch.Tensor] = None, v_bar: Optional[torch.Tensor] = None, s_bar: Optional[torch.Tensor] = None,
+                          tau_bar: Optional[torch.Tensor] = None, fext_bar: Optional[torch.Tensor] = None, vdout: Optional[torch.Tensor] = None,
+                          sdout: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None,
+                          s: Optional[torch.Tensor] = None):
+    """`dynamics!` of a mechanism with contact points pulled back, the ODE form (q, v, s, τ, f_ext) -> (v̇, ṡ, s after the resets): the cotangents `vd_bar`
+    (B, nv), `sd_bar`, `s_out_bar` (B, ns) (each may be None, not all) -> q_bar, v_bar, s_bar, tau_bar, fext_bar, overwritten, in one call; `vdout` / `sdout`
+    receive v̇ and ṡ themselves."""
+    f = state.flat
+    q = state.q if q is None else q
+    v = state.v if v is None else v
+    s = state.s if s is None else s
+    state._check(q, f.nq, "q")
+    state._check(v, f.nv, "v")
+    state._check(s, f.ns, "s")
+    state._check(torques, f.nv, "torques")
+    state._check(externalwrenches, 6 * f.n_bodies, "externalwrenches")
+    state._check(vd_bar, f.nv, "vd_bar")
+    state._check(sd_bar, f.ns, "sd_bar")
+    state._check(s_out_bar, f.ns, "s_out_bar")
+    state._check(vdout, f.nv, "vdout")
+    state._check(sdout, f.ns, "sdout")
+    state._check(q_bar, f.nq, "q_bar")
+    state._check(v_bar, f.nv, "v_bar")
+    state._check(s_bar, f.ns, "s_bar")
+    state._check(tau_bar, f.nv, "tau_bar")
+    state._check(fext_bar, 6 * f.n_bodies, "fext_bar")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_dynamics_contact_vjp(state.ws.handle, state.batch, _ptr(q), _ptr(v), _ptr(s), _ptr(torques), _ptr(externalwrenches), _ptr(vd_bar),
+                                              _ptr(sd_bar), _ptr(s_out_bar), _ptr(vdout), _ptr(sdout), _ptr(q_bar), _ptr(v_bar), _ptr(s_bar), _ptr(tau_bar),
+                                              _ptr(fext_bar), ctypes.byref(opts))
+    _raise(st, "rbd_dynamics_contact_vjp")
+    return q_bar, v_bar, s_bar, tau_bar, fext_bar
