@@ -516,6 +516,24 @@ int rbd_contact_dynamics_vjp(rbd_ws_t* ws, int32_t B, const void* q, const void*
 int rbd_dynamics_contact_vjp(rbd_ws_t* ws, int32_t B, const void* q, const void* v, const void* s, const void* tau, const void* fext,
                              const void* vdot_bar, const void* sdot_bar, const void* s_out_bar, void* vdot_out, void* sdot_out,
                              void* q_bar, void* v_bar, void* s_bar, void* tau_bar, void* fext_bar, const rbd_opts_t* opts);
+/* rbd_simulate_contact_vjp (700 addition): reverse mode through nsteps steps of rbd_simulate_contact — the gradient of a scalar loss of the final state
+ * (q, v, s), one cotangent per state: rbd_simulate_vjp's checkpointed RK4 adjoint with the friction state s carried through the tableau in both directions
+ * and, at every stage state, rbd_dynamics_contact_vjp's composition (the forward contact launch, the dynamics VJP at the total wrenches, the contact
+ * model's pullback, the contact points' kinematic pullback).
+ *  - q, v, s: IN/OUT, advanced by nsteps (the CRBA + Cholesky value route at every stage state: rbd_simulate_contact's state to rounding).
+ *  - q_bar (nq), v_bar (nv), s_bar (ns): IN/OUT, all required — the cotangent of the final state on entry, that of the initial state on return.
+ *  - tau_bar (nv), fext_bar (6·n_bodies): nullable, OVERWRITTEN with the gradient in the held τ / fext, summed over every stage of every step.
+ *  - The gradient is that of the branch each (point, half-space) pair takes AT EACH STAGE STATE; a pair may change branch between stages and steps.  The
+ *    reset of an outside pair's friction state happens in the stage state only and never reaches the state after the step, as in rbd_simulate_contact.
+ *  - Semantics as rbd_dynamics_contact_vjp (raw coordinates, device pointers only, fp32 and fp64, both layouts, trees of any size; RBD_MEM_HOST:
+ *    RBD_ERR_UNSUPPORTED; loop joints: RBD_ERR_HAS_LOOPS; no contact points or no environment: RBD_ERR_INVALID_ARGUMENT — use rbd_simulate_vjp).
+ *    dt <= 0, nsteps < 0 or a NULL q, v, s, q_bar, v_bar or s_bar: RBD_ERR_INVALID_ARGUMENT; B == 0 is a no-op; nsteps == 0 leaves the state and the
+ *    three cotangents and zeroes tau_bar / fext_bar.
+ *  - Step starts (q, v, s) are kept while nsteps·(nq + nv + ns)·B values fit in 1 GiB, else two-level checkpointing as rbd_simulate_vjp.  The first call
+ *    of a workspace allocates, and a call that needs more room for step starts than any before; nothing else allocates or synchronises.
+ *  - rbd_workspace_last_kernel names contact_stage_adjoint_kernel afterwards, among the others.  Per-step torques: one call per step. */
+int rbd_simulate_contact_vjp(rbd_ws_t* ws, int32_t B, void* q, void* v, void* s, const void* tau, const void* fext, double dt, int32_t nsteps,
+                             void* q_bar, void* v_bar, void* s_bar, void* tau_bar, void* fext_bar, const rbd_opts_t* opts);
 
 /* ---- diagnostics ------------------------------------------------------------ */
 const char* rbd_status_string(int status);
@@ -534,7 +552,8 @@ const char* rbd_workspace_last_kernel(const rbd_ws_t* ws);
  *      added to 700 without a new version: rbd_simulate_jvp, rbd_simulate_step_derivatives (derivatives of simulate steps);
  *      rbd_inverse_dynamics_vjp, rbd_dynamics_vjp (reverse mode); rbd_simulate_vjp (reverse mode through simulate steps);
  *      rbd_workspace_set_points, rbd_point_kinematics, rbd_point_kinematics_vjp (point kinematics);
- *      rbd_contact_dynamics_vjp, rbd_dynamics_contact_vjp (reverse mode through soft contact). */
+ *      rbd_contact_dynamics_vjp, rbd_dynamics_contact_vjp (reverse mode through soft contact);
+ *      rbd_simulate_contact_vjp (reverse mode through simulate steps with soft contact). */
 #define RBD_HIP_H_VERSION 700
 int rbd_version(void);
 /* Run-time specialisation.  The one-lane-per-state kernels (mass_matrix! and mass_matrix! + Cholesky at large batches) exist in a second form

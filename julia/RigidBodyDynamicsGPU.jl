@@ -31,7 +31,7 @@ using LinearAlgebra
 export BatchedMechanismState, BatchedDynamicsResult, DeviceMatrix, RbdComm, gather!, gatherv!, mass_matrix_solve_packed!, synchronize, librbd_hip, TorqueTable, PDControl,
     inverse_dynamics_jvp!, dynamics_jvp!, inverse_dynamics_derivatives!, dynamics_derivatives!, simulate_jvp!, simulate_step_derivatives!,
     inverse_dynamics_vjp!, dynamics_vjp!, simulate_vjp!, set_points!, point_kinematics!, point_jacobian!, point_velocity!, point_kinematics_vjp!,
-    contact_dynamics_vjp!, dynamics_contact_vjp!
+    contact_dynamics_vjp!, dynamics_contact_vjp!, simulate_contact_vjp!
 
 const librbd_hip = Ref("librbd_hip.so")   # set to <repo>/rigidbodydynamics.jl_amd/csrc/librbd_hip.so
 const libhip = Ref("libamdhip64.so")
@@ -840,6 +840,27 @@ function dynamics_contact_vjp!(q̄, v̄, s̄, τ̄, state::BatchedMechanismState
         state.ws, B, state.q, state.v, state.s, nullable(torques), nullable(densewrenches(state, externalwrenches)), nullable(v̇̄), nullable(ṡ̄),
         nullable(s̄out), nullable(v̇out), nullable(ṡout), nullable(q̄), nullable(v̄), nullable(s̄), nullable(τ̄), nullable(f̄ext), opts(state)),
         "rbd_dynamics_contact_vjp")
+    finish(state)
+    q̄, v̄, s̄, τ̄
+end
+
+"""`simulate_contact_vjp!(q̄, v̄, s̄, state, Δt; nsteps = 1, torques, externalwrenches, τ̄, f̄ext)` — `nsteps` Munthe-Kaas RK4 steps of `simulate` of a mechanism
+with contact points pulled back (`state`'s q, v and s advanced in place): q̄ (nq × B), v̄ (nv × B), s̄ (ns × B) hold the cotangent of the final state on entry
+and that of the initial state on return; τ̄, f̄ext (each may be `nothing`) are overwritten with the gradient in the held torques / wrenches over every stage.
+The gradient is that of the branch each (point, half-space) pair takes at each stage state (`rbd_simulate_contact_vjp`)."""
+function simulate_contact_vjp!(q̄::Buffer{T}, v̄::Buffer{T}, s̄::Buffer{T}, state::BatchedMechanismState{T}, Δt::Real; nsteps::Integer = 1, torques = nothing,
+        externalwrenches = nothing, τ̄ = nothing, f̄ext = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, ns, B = state.model.nq, state.model.nv, size(state.s, 1), batchsize(state)
+    Δt > 0 || throw(ArgumentError("Δt must be positive"))
+    nsteps >= 0 || throw(ArgumentError("nsteps must be non-negative"))
+    for (x, n) in ((q̄, nq), (v̄, nv), (s̄, ns), (τ̄, nv))
+        x === nothing || size(x) == (n, B) || throw(DimensionMismatch("cotangent buffer has wrong size"))
+    end
+    check(ccall((:rbd_simulate_contact_vjp, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Cdouble, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, state.q, state.v, state.s, nullable(torques), nullable(densewrenches(state, externalwrenches)), Float64(Δt), Int32(nsteps), q̄, v̄, s̄,
+        nullable(τ̄), nullable(f̄ext), opts(state)), "rbd_simulate_contact_vjp")
     finish(state)
     q̄, v̄, s̄, τ̄
 end

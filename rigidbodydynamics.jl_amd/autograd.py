@@ -1,6 +1,7 @@
 """torch.autograd through the library: `tau = inverse_dynamics(state, q, v, vd, fext)`, `vd = dynamics(state, q, v, tau, fext)` and
 `q1, v1 = simulate(state, q, v, tau, fext, dt=, nsteps=)`, and, reverse mode only, `pos, vel = point_kinematics(state, q, v)` and
-`vd, sd, s_out = dynamics_contact(state, q, v, s, tau, fext)` (a mechanism with contact points) are differentiable functions of their tensor arguments, so `loss.backward()` (reverse mode) and `torch.func.jvp` / `torch.autograd.forward_ad` (forward mode) work through
+`vd, sd, s_out = dynamics_contact(state, q, v, s, tau, fext)` and `q1, v1, s1 = simulate_contact(state, q, v, s, tau, fext, dt=, nsteps=)` (a mechanism with
+contact points) are differentiable functions of their tensor arguments, so `loss.backward()` (reverse mode) and `torch.func.jvp` / `torch.autograd.forward_ad` (forward mode) work through
 them.
 
   - `state` (a MechanismState) supplies the workspace, the batch, the dtype and the layout; q, v, … are tensors of that layout ((B, n) with "aos",
@@ -21,7 +22,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _capi
 from .state import (MechanismState, _ptr, _raise, dynamics_contact_vjp_, dynamics_vjp_, inverse_dynamics_vjp_, point_kinematics_, point_kinematics_vjp_,
-                    simulate_vjp_)
+                    simulate_contact_vjp_, simulate_vjp_)
 
 
 def _prep(state: MechanismState, t: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
@@ -224,6 +225,53 @@ class _DynamicsContact(torch.autograd.Function):
             dynamics_contact_vjp_(state, _prep(state, vd_bar, f.nv, "vd_bar"), _prep(state, sd_bar, f.ns, "sd_bar"), _prep(state, s_out_bar, f.ns, "s_out_bar"),
                                   tau, fext, *out, q=q, v=v, s=s)
         return (None,) + out
+
+
+class _SimulateContact(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, state, q, v, s, tau, fext, dt, nsteps):
+        f = state.flat
+        q, v, s = _prep(state, q, f.nq, "q"), _prep(state, v, f.nv, "v"), _prep(state, s, f.ns, "s")
+        tau, fext = _prep(state, tau, f.nv, "torques"), _prep(state, fext, 6 * f.n_bodies, "externalwrenches")
+        q1, v1, s1 = q.clone(), v.clone(), s.clone()
+        state.ws.use_current_stream()
+        opts = state._opts()
+        _raise(_capi.lib().rbd_simulate_contact(state.ws.handle, state.batch, _ptr(q1), _ptr(v1), _ptr(s1), _ptr(tau), _ptr(fext), ctypes.c_double(dt),
+                                                int(nsteps), ctypes.byref(opts)), "rbd_simulate_contact")
+        ctx.state, ctx.dt, ctx.nsteps = state, float(dt), int(nsteps)
+        ctx.save_for_backward(q, v, s, tau, fext)
+        return q1, v1, s1
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, q1_bar, v1_bar, s1_bar):
+        state, f = ctx.state, ctx.state.flat
+        q, v, s, tau, fext = ctx.saved_tensors
+        _, nq_, nv_, ns_, nt_, nf_, _, _ = ctx.needs_input_grad
+        if not (nq_ or nv_ or ns_ or nt_ or nf_):
+            return (None,) * 8
+        # (the steps run again from the saved inputs, on copies: the library advances q, v, s in place)
+        qs, vs, ss = q.clone(), v.clone(), s.clone()
+        qb = _prep(state, q1_bar, f.nq, "q_bar").clone() if q1_bar is not None else torch.zeros_like(q)
+        vb = _prep(state, v1_bar, f.nv, "v_bar").clone() if v1_bar is not None else torch.zeros_like(v)
+        sb = _prep(state, s1_bar, f.ns, "s_bar").clone() if s1_bar is not None else torch.zeros_like(s)
+        tb, fb = _empty(state, f.nv, nt_ and tau is not None), _empty(state, 6 * f.n_bodies, nf_ and fext is not None)
+        simulate_contact_vjp_(qb, vb, sb, state, ctx.dt, ctx.nsteps, torques=tau, externalwrenches=fext, tau_bar=tb, fext_bar=fb, q=qs, v=vs, s=ss)
+        return None, qb if nq_ else None, vb if nv_ else None, sb if ns_ else None, tb, fb, None, None
+
+
+def simulate_contact(state: MechanismState, q: torch.Tensor, v: torch.Tensor, s: torch.Tensor, tau: Optional[torch.Tensor] = None,
+                     fext: Optional[torch.Tensor] = None, dt: float = 1e-3, nsteps: int = 1):
+    """(q⁺, v⁺, s⁺) after `nsteps` Munthe-Kaas RK4 steps of `simulate` of a mechanism with contact points and an environment, with the torques `tau` and
+    wrenches `fext` held (None: zero / none); `s` (B, ns) is the friction state.  Differentiable in q, v, s, tau and fext, reverse mode only.  The value is
+    rbd_simulate_contact's (on copies: q, v and s are not modified); backward runs the steps again from the saved inputs through one
+    rbd_simulate_contact_vjp, the derivative of the branch each (point, half-space) pair takes at each stage state, with dynamics! on the CRBA + Cholesky
+    route (as `simulate`).  Per-step controls: call this once per step with that step's tau; torch's saved tensors are then the checkpoints."""
+    if not float(dt) > 0:
+        raise ValueError("dt must be positive")
+    if int(nsteps) < 0:
+        raise ValueError("nsteps must be non-negative")
+    return _SimulateContact.apply(state, q, v, s, tau, fext, float(dt), int(nsteps))
 
 
 def dynamics_contact(state: MechanismState, q: torch.Tensor, v: torch.Tensor, s: torch.Tensor, tau: Optional[torch.Tensor] = None,

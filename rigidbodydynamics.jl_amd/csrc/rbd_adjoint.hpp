@@ -31,6 +31,7 @@ template <typename T> struct AdjArgs {
   T sign;                            // dynamics!: −1 (the implicit-function identity)
   int accum;                         // 1: ADD to qbar, vbar, vdbar, fbar instead of overwriting them (rbd_simulate_vjp sums over stages)
   T* lbar;                           // nullable: λ is added here (Lv; rbd_simulate_vjp's τ̄)
+  int fset;                          // 1: fbar is OVERWRITTEN even with accum (rbd_simulate_contact_vjp: the contact pullback needs one stage's f̄ alone)
 };
 
 // ---- adjoints of the spatial primitives (rbd_device.hpp): given the output's adjoint ō, ADD the inputs' adjoints ----------------------------------------
@@ -385,7 +386,7 @@ template <typename T> RBD_HD void adjoint_rnea_state(const BigModel& M, const Ad
       at(ADJ_WB + k, i) = Wb[k];
       if (A.fbar) {
         T& o = A.fbar[(long)(6 * i + k) * A.Lf.sk + layout_base(A.Lf, st)];
-        o = A.accum ? o - A.sign * Wb[k] : -A.sign * Wb[k];
+        o = A.accum && !A.fset ? o - A.sign * Wb[k] : -A.sign * Wb[k];
       }
     }
     xmotion_adj(K, K + 9, m, W, Kb, Kb + 9, (T*)nullptr);

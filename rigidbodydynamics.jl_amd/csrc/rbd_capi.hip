@@ -214,6 +214,8 @@ struct rbd_ws {
   // forward contact launch resets
   bool ct_ready = false; PointPlan ct_pts{}; void* d_ct_i = nullptr; void* d_ct_r = nullptr; void* d_ct_pbar = nullptr; void* d_ct_vbar = nullptr;
   void* d_ct_wbar = nullptr; void* d_ct_s = nullptr;
+  // rbd_simulate_contact_vjp: the friction state's stage states 1-3, running sum and ṡ of one step, and the cotangents of s0 and of the sum (7 ns values per state)
+  bool sct_ready = false; void* d_sct = nullptr; size_t d_sct_bytes = 0;
 };
 
 // RBD_TUNE="key=value,key=value,...": the developer knobs of the tests and sweep scripts in ONE environment variable (batch thresholds between the lane
@@ -1107,7 +1109,7 @@ int rbd_workspace_destroy(rbd_ws_t* w) {
   void* ptrs[] = {w->d_big_L, w->d_big_tbl, w->d_big_rb, w->d_big_scratch, w->d_fused_i, w->d_tauwork, w->d_rr_chain_i, w->d_rr_chain_r, w->d_rrtrack_ri, w->d_rrtrack_rr, w->d_rrwalk_wk, w->d_cp_body, w->d_cp_r, w->d_hs_r, w->d_tw, w->d_cw, w->d_s0, w->d_sacc, w->d_sdot, w->d_rows, w->d_walk_wk, w->d_state_ops, w->d_state_cols, w->d_state_sr, w->d_Msoa, w->d_track_ri, w->d_track_rr, w->d_bank_ib[0], w->d_bank_ib[1], w->d_bank_rb[0], w->d_bank_rb[1], w->d_ib, w->d_rb, w->d_nslots, w->d_dof_body, w->d_anc, w->d_row_mask, w->d_M, w->d_c, w->d_K, w->d_k, (void*)w->d_notpd, w->d_body, w->d_scratch, w->d_loop_i, w->d_loop_r, w->d_loop_path, w->d_jt_ref, w->d_voff_ref, w->d_axis_ref, w->d_axis2_ref,
                   w->d_tan_tbl, w->d_tan_rb, w->d_tan_scratch, w->d_tan_M, w->d_tan_L, w->d_tan_c, w->d_tan_vd, w->d_tan_rhs, w->d_tan_x,
                   w->d_sim_val, w->d_sim_tan, w->d_adj_scratch, w->d_adj_rhs, w->d_adj_lam, w->d_adj_x, w->d_sav_joints, w->d_sav, w->d_sav_ckpt, w->d_pt_i, w->d_pt_r,
-                  w->d_ct_i, w->d_ct_r, w->d_ct_pbar, w->d_ct_vbar, w->d_ct_wbar, w->d_ct_s};
+                  w->d_ct_i, w->d_ct_r, w->d_ct_pbar, w->d_ct_vbar, w->d_ct_wbar, w->d_ct_s, w->d_sct};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (void* p : w->stage) if (p) (void)hipFree(p);
   {
@@ -3165,21 +3167,90 @@ template <typename T> MkAdjArgs<T> sav_args(rbd_ws* w, int32_t B, int layout, do
   return A;
 }
 
+// ---- the friction state beside (q, v) (rbd_simulate_contact_vjp): the optional contact argument of the sav_* templates -----------------------------------------
+// the first call of a workspace allocates what rbd_simulate_vjp and the contact VJPs do, and the friction state's buffers (for max_batch states)
+int sct_ensure(rbd_ws* w) {
+  const rbd_model* m = w->model;
+  int st;
+  if ((st = sav_ensure(w)) || (st = ct_ensure(w))) return st;
+  if (w->sct_ready) return RBD_OK;
+  if ((st = ensure(&w->d_sct, &w->d_sct_bytes, esize(w) * 7 * 3 * (size_t)m->ncp * m->nhs * w->max_batch))) return st;
+  w->sct_ready = true;
+  return RBD_OK;
+}
+
+template <typename T> struct SctBufs {
+  T *ss[3], *acc, *sdot, *s0b, *accb;
+};
+template <typename T> SctBufs<T> sct_bufs(rbd_ws* w) {
+  const long n = 3L * w->model->ncp * w->model->nhs * w->max_batch;
+  T* p = (T*)w->d_sct;
+  SctBufs<T> b;
+  for (int i = 0; i < 3; ++i) { b.ss[i] = p; p += n; }
+  b.acc = p; p += n; b.sdot = p; p += n; b.s0b = p; p += n; b.accb = p;
+  return b;
+}
+
+// one step's friction state: s0 its start (a checkpoint slot or the caller's s: only read), sn the state after the step (the value pass; may be s0), s_bar
+// the cotangent (the backward pass).  NULL for a mechanism without contact: rbd_simulate_vjp's launches as they were.
+struct SavContact { const Opts* o; const void* s0; void* sn; void* s_bar; };
+
+// the friction state at stage state `stage`: stage 0 a COPY of s0 (the forward contact launch resets the pairs outside — never a step's start), else the
+// workspace's stage buffer
+template <typename T> T* sct_stage_state(rbd_ws* w, int stage) { return stage == 0 ? (T*)w->d_ct_s : sct_bufs<T>(w).ss[stage - 1]; }
+
+// contact_dynamics! at a stage state: the per-body kinematics into w->d_body, ṡ into the workspace, the total wrenches fext + contact into w->d_tw
+template <typename T> int sct_contact(rbd_ws* w, int32_t B, const SavContact& C, int stage, const T* qs, const T* vs, const void* fext) {
+  const rbd_model* m = w->model;
+  T* ss = sct_stage_state<T>(w, stage);
+  if (stage == 0) HIP_TRY(hipMemcpyAsync(ss, C.s0, sizeof(T) * 3 * m->ncp * m->nhs * B, hipMemcpyDeviceToDevice, w->stream));
+  return run_contact(w, B, *C.o, qs, vs, ss, sct_bufs<T>(w).sdot, fext, nullptr, w->d_tw);
+}
+
+// the friction state's value stage map (contact_stage_value_kernel), after sct_contact left ṡ of the stage state
+template <typename T> int sct_value_step(rbd_ws* w, int32_t B, const SavContact& C, int stage, double dt) {
+  const rbd_model* m = w->model;
+  const SctBufs<T> b = sct_bufs<T>(w);
+  HIP_TRY(launch_contact_stage_value<T>(3L * m->ncp * m->nhs * B, stage, dt, C.s0, b.sdot, b.acc, stage == 3 ? C.sn : (void*)b.ss[stage], w->stream));
+  return RBD_OK;
+}
+
+// the friction state's and the contact model's share of one stage pulled back, after the adjoint RNEA pass wrote THIS stage's cotangent of the total wrenches
+// to w->d_ct_wbar: contact_stage_adjoint_kernel (the tableau, the pairs, s̄, f̄ext += the stage's, the per-point cotangents), then point_adjoint_kernel ADDING the
+// contact points' kinematic pullback to the stage state's q̄, v̄
+template <typename T>
+int sct_backward_step(rbd_ws* w, int32_t B, int layout, const SavContact& C, int stage, double dt, const T* qs, const T* vs, void* q_bar, void* v_bar, void* fext_bar) {
+  const rbd_model* m = w->model;
+  const SctBufs<T> b = sct_bufs<T>(w);
+  const Layout Ls = layout_of(layout, 3L * m->ncp * m->nhs, B), Lf = layout_of(layout, 6L * m->nb, B), L3 = layout_of(layout, 3L * m->ncp, B);
+  HIP_TRY(launch_contact_stage_adjoint<T>(w->ctm, B, stage, dt, w->d_body, sct_stage_state<T>(w, stage), w->d_ct_wbar, fext_bar, C.s_bar, b.s0b, b.accb, w->d_ct_pbar,
+                                          w->d_ct_vbar, Ls, Lf, L3, w->stream));
+  AdjArgs<T> A = adj_args<T>(w, B, layout, qs, vs, nullptr, nullptr);
+  A.qbar = (T*)q_bar; A.vbar = (T*)v_bar; A.accum = 1;
+  PointAdjArgs<T> P{(const T*)w->d_ct_pbar, (const T*)w->d_ct_vbar, L3};
+  HIP_TRY(launch_point_adjoint<T>(w->tan, w->ct_pts, A, P, w->d_adj_scratch, w->adj_states, w->stream));
+  return RBD_OK;
+}
+
 // stages 0 … last of one step from (q0, v0), values only (the route of sim_tan_run: dynamics! by CRBA + Cholesky at every stage state, then the stage
 // map): the stage states 1-3 and the running sums into the workspace, the state after the step (last = 3) into (qout, vout), which may be (q0, v0).
+// With contact (C): dynamics! at the total wrenches of the stage state, and the friction state through the same tableau.
 template <typename T>
-int sav_value_step(rbd_ws* w, int32_t B, int layout, const T* q0, const T* v0, const void* tau, const void* fext, double dt, int last, T* qout, T* vout) {
+int sav_value_step(rbd_ws* w, int32_t B, int layout, const T* q0, const T* v0, const void* tau, const void* fext, double dt, int last, T* qout, T* vout,
+                   const SavContact* C = nullptr) {
   const SavBufs<T> b = sav_bufs<T>(w);
   const int32_t* jl = (const int32_t*)w->d_sav_joints;
   for (int stage = 0; stage <= last; ++stage) {
     const T* qs = stage == 0 ? q0 : b.qs[stage - 1];
     const T* vs = stage == 0 ? v0 : b.vs[stage - 1];
     int st;
-    if ((st = tan_dynamics_value<T>(w, B, layout, qs, vs, tau, fext, w->d_tan_vd))) return st;
+    if (C && (st = sct_contact<T>(w, B, *C, stage, qs, vs, fext))) return st;
+    if ((st = tan_dynamics_value<T>(w, B, layout, qs, vs, tau, C ? w->d_tw : fext, w->d_tan_vd))) return st;
     MkAdjArgs<T> A = sav_args<T>(w, B, layout, dt, stage);
     A.q0 = q0; A.v0 = v0; A.qs = qs; A.vs = vs; A.vd = (const T*)w->d_tan_vd; A.accp = b.accp; A.accv = b.accv;
     A.qn = stage == 3 ? qout : b.qs[stage]; A.vn = stage == 3 ? vout : b.vs[stage];
     HIP_TRY(launch_mk_stage_classes<T>(A, jl, w->sav_nn, jl + 3 * w->sav_nn, w->sav_nw, 0, w->stream));
+    if (C && (st = sct_value_step<T>(w, B, *C, stage, dt))) return st;
   }
   return RBD_OK;
 }
@@ -3187,60 +3258,74 @@ int sav_value_step(rbd_ws* w, int32_t B, int layout, const T* q0, const T* v0, c
 // One step pulled back: (q_bar, v_bar) hold the cotangent of the state after the step on entry and that of (q0, v0) on return; τ̄ and f̄ext accumulate.
 // Stages 3 … 0: the stage map's pullback (v̇̄_i, the stage state's cotangent, the base point's), λ_i = M_i⁻¹ v̇̄_i, then the adjoint RNEA at the stage state
 // with sign −1 ADDING −(∂ID)ᵀλ_i to the stage state's cotangent and f̄ext, and λ_i to τ̄.  `fresh`: the stage states, the sums and stage 3's factor and v̇
-// are this step's already (the forward pass's last step).
+// are this step's already (the forward pass's last step).  With contact (C): the values at the stage's total wrenches, whose cotangent of THIS stage alone the
+// adjoint RNEA pass writes to w->d_ct_wbar (f̄ext is a sum over stages; the contact pullback must not see the sum), then sct_backward_step.
 template <typename T>
 int sav_backward_step(rbd_ws* w, int32_t B, int layout, const T* q0, const T* v0, const void* tau, const void* fext, double dt, bool fresh, void* q_bar,
-                      void* v_bar, void* tau_bar, void* fext_bar) {
+                      void* v_bar, void* tau_bar, void* fext_bar, const SavContact* C = nullptr) {
   const rbd_model* m = w->model;
   const SavBufs<T> b = sav_bufs<T>(w);
   const int32_t* jl = (const int32_t*)w->d_sav_joints;
   const Layout Li{B, 1};
   int st;
-  if (!fresh && (st = sav_value_step<T>(w, B, layout, q0, v0, tau, fext, dt, 2, nullptr, nullptr))) return st;
+  if (!fresh && (st = sav_value_step<T>(w, B, layout, q0, v0, tau, fext, dt, 2, nullptr, nullptr, C))) return st;
   for (int stage = 3; stage >= 0; --stage) {
     const T* qs = stage == 0 ? q0 : b.qs[stage - 1];
     const T* vs = stage == 0 ? v0 : b.vs[stage - 1];
-    if (!(fresh && stage == 3) && (st = tan_dynamics_value<T>(w, B, layout, qs, vs, tau, fext, w->d_tan_vd))) return st;
+    if (C && !(fresh && stage == 3) && (st = sct_contact<T>(w, B, *C, stage, qs, vs, fext))) return st;
+    if (!(fresh && stage == 3) && (st = tan_dynamics_value<T>(w, B, layout, qs, vs, tau, C ? w->d_tw : fext, w->d_tan_vd))) return st;
     MkAdjArgs<T> S = sav_args<T>(w, B, layout, dt, stage);
     S.q0 = q0; S.qs = qs; S.vs = vs; S.accp = b.accp;
     S.qsb = (T*)q_bar; S.vsb = (T*)v_bar; S.q0b = b.q0b; S.v0b = b.v0b; S.vdb = b.vdb; S.apb = b.apb; S.avb = b.avb;
     HIP_TRY(launch_mk_stage_classes<T>(S, jl, w->sav_nn, jl + 3 * w->sav_nn, w->sav_nw, 1, w->stream));
     const ColOut<T> lam{(T*)w->d_adj_lam, Li, nullptr, Layout{0, 0}, INT32_MAX, m->nv};
     HIP_TRY(launch_tangent_solve<T>(m->nv, B, 0, 1, w->d_tan_L, Li, b.vdb, 0, lam, w->d_adj_x, w->stream));
-    AdjArgs<T> A = adj_args<T>(w, B, layout, qs, vs, w->d_tan_vd, fext);
+    AdjArgs<T> A = adj_args<T>(w, B, layout, qs, vs, w->d_tan_vd, C ? w->d_tw : fext);
     A.lam = lam.a; A.Llam = Li;
-    A.qbar = (T*)q_bar; A.vbar = (T*)v_bar; A.fbar = (T*)fext_bar; A.lbar = (T*)tau_bar;
-    A.sign = T(-1); A.accum = 1;
+    A.qbar = (T*)q_bar; A.vbar = (T*)v_bar; A.fbar = (T*)(C ? w->d_ct_wbar : fext_bar); A.lbar = (T*)tau_bar;
+    A.sign = T(-1); A.accum = 1; A.fset = C ? 1 : 0;
     HIP_TRY(launch_adjoint_rnea<T>(w->tan, A, w->d_adj_scratch, w->adj_states, w->stream));
+    if (C && (st = sct_backward_step<T>(w, B, layout, *C, stage, dt, qs, vs, q_bar, v_bar, fext_bar))) return st;
   }
   return RBD_OK;
 }
 
-// nsteps steps forward (the step starts kept as `P` says; q, v advanced in place), then backward from the last step to the first
+// nsteps steps forward (the step starts kept as `P` says; q, v advanced in place), then backward from the last step to the first.  co: the options of a call with
+// contact (rbd_simulate_contact_vjp), whose slots hold (q, v, s) and whose friction state sx and cotangent sx_bar travel beside (q, v); NULL without.
 template <typename T>
 int sav_run(rbd_ws* w, int32_t B, int layout, void* q, void* v, const void* tau, const void* fext, double dt, int nsteps, SavPlan P, void* q_bar, void* v_bar,
-            void* tau_bar, void* fext_bar) {
+            void* tau_bar, void* fext_bar, const Opts* co = nullptr, void* sx = nullptr, void* sx_bar = nullptr) {
   const rbd_model* m = w->model;
-  const long nq = m->nq, nv = m->nv, slot = (nq + nv) * B;
+  const long nq = m->nq, nv = m->nv, ns = co ? 3L * m->ncp * m->nhs : 0, slot = (nq + nv + ns) * B;
   const size_t es = sizeof(T);
   T* ck = (T*)w->d_sav_ckpt;
   auto cq = [&](int i) { return ck + i * slot; };
   auto cv = [&](int i) { return ck + i * slot + nq * B; };
+  auto cs = [&](int i) { return ck + i * slot + (nq + nv) * B; };
   auto keep = [&](int i, const void* qf, const void* vf) -> hipError_t {
     hipError_t e = hipMemcpyAsync(cq(i), qf, es * nq * B, hipMemcpyDeviceToDevice, w->stream);
+    if (e == hipSuccess && co) e = hipMemcpyAsync(cs(i), sx, es * ns * B, hipMemcpyDeviceToDevice, w->stream);
     return e != hipSuccess ? e : hipMemcpyAsync(cv(i), vf, es * nv * B, hipMemcpyDeviceToDevice, w->stream);
+  };
+  SavContact ct{co, nullptr, nullptr, sx_bar};
+  auto contact = [&](const void* s0, void* sn) -> const SavContact* {  // (one step's friction state: from s0 to sn)
+    if (!co) return nullptr;
+    ct.s0 = s0; ct.sn = sn;
+    return &ct;
   };
   int st;
   if (P.S == 1) {  // every start kept: step s from slot s into slot s + 1 (the last into (q, v))
     HIP_TRY(keep(0, q, v));
     for (int s = 0; s < nsteps; ++s) {
       const bool last = s == nsteps - 1;
-      if ((st = sav_value_step<T>(w, B, layout, cq(s), cv(s), tau, fext, dt, 3, last ? (T*)q : cq(s + 1), last ? (T*)v : cv(s + 1)))) return st;
+      if ((st = sav_value_step<T>(w, B, layout, cq(s), cv(s), tau, fext, dt, 3, last ? (T*)q : cq(s + 1), last ? (T*)v : cv(s + 1),
+                                  contact(cs(s), last ? (T*)sx : cs(s + 1)))))
+        return st;
     }
   } else {  // every S-th start kept, (q, v) stepped in place
     for (int s = 0; s < nsteps; ++s) {
       if (s % P.S == 0) HIP_TRY(keep(s / P.S, q, v));
-      if ((st = sav_value_step<T>(w, B, layout, (T*)q, (T*)v, tau, fext, dt, 3, (T*)q, (T*)v))) return st;
+      if ((st = sav_value_step<T>(w, B, layout, (T*)q, (T*)v, tau, fext, dt, 3, (T*)q, (T*)v, contact(sx, sx)))) return st;
     }
   }
   bool fresh = P.S == 1;  // (the forward pass's last step left its stage states, sums and stage-3 factor)
@@ -3248,13 +3333,23 @@ int sav_run(rbd_ws* w, int32_t B, int layout, void* q, void* v, const void* tau,
     const int s0 = g * P.S, n = std::min(P.S, nsteps - s0);
     auto start = [&](int j) { return j == 0 ? g : P.K + j - 1; };  // (the slot of step s0 + j's start)
     for (int j = 1; j < n; ++j)  // the segment's starts recomputed from its kept one
-      if ((st = sav_value_step<T>(w, B, layout, cq(start(j - 1)), cv(start(j - 1)), tau, fext, dt, 3, cq(start(j)), cv(start(j))))) return st;
+      if ((st = sav_value_step<T>(w, B, layout, cq(start(j - 1)), cv(start(j - 1)), tau, fext, dt, 3, cq(start(j)), cv(start(j)),
+                                  contact(cs(start(j - 1)), cs(start(j))))))
+        return st;
     for (int j = n - 1; j >= 0; --j) {
-      if ((st = sav_backward_step<T>(w, B, layout, cq(start(j)), cv(start(j)), tau, fext, dt, fresh, q_bar, v_bar, tau_bar, fext_bar))) return st;
+      if ((st = sav_backward_step<T>(w, B, layout, cq(start(j)), cv(start(j)), tau, fext, dt, fresh, q_bar, v_bar, tau_bar, fext_bar, contact(cs(start(j)), nullptr))))
+        return st;
       fresh = false;
     }
   }
   return RBD_OK;
+}
+
+// rbd_simulate_contact_vjp's run: sav_run with the friction state beside (q, v)
+template <typename T>
+int sct_run(rbd_ws* w, int32_t B, const Opts& o, void* q, void* v, void* s, const void* tau, const void* fext, double dt, int nsteps, SavPlan P, void* q_bar,
+            void* v_bar, void* s_bar, void* tau_bar, void* fext_bar) {
+  return sav_run<T>(w, B, o.layout, q, v, tau, fext, dt, nsteps, P, q_bar, v_bar, tau_bar, fext_bar, &o, s, s_bar);
 }
 }  // namespace
 
@@ -3540,6 +3635,33 @@ int rbd_dynamics_contact_vjp(rbd_ws_t* w, int32_t B, const void* q, const void* 
       if (fext_bar) HIP_TRY(hipMemsetAsync(fext_bar, 0, es * 6 * m->nb * B, w->stream));
     }
     return ct_adjoint<T>(w, B, o.layout, q, v, s, wbar, sdot_bar, s_out_bar, q_bar, v_bar, s_bar, vdot_bar ? 1 : 0);
+  });
+}
+
+int rbd_simulate_contact_vjp(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, const void* tau, const void* fext, double dt, int32_t nsteps, void* q_bar,
+                             void* v_bar, void* s_bar, void* tau_bar, void* fext_bar, const rbd_opts_t* opts) {
+  Opts o;
+  int st = contact_vjp_scope(w, B, opts, &o);
+  if (st != RBD_OK) return st;
+  if (!(dt > 0) || nsteps < 0 || !q || !v || !s || !q_bar || !v_bar || !s_bar) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0) return RBD_OK;
+  const rbd_model* m = w->model;
+  if (m->nv == 0) return RBD_ERR_UNSUPPORTED;  // (contact points on a mechanism that cannot move: nothing to differentiate)
+  const size_t es = esize(w);
+  HIP_TRY(hipSetDevice(w->device));
+  // τ̄ and f̄ext are sums over every stage of every step: zero first (all of them when nothing moves)
+  if (tau_bar) HIP_TRY(hipMemsetAsync(tau_bar, 0, es * m->nv * B, w->stream));
+  if (fext_bar) HIP_TRY(hipMemsetAsync(fext_bar, 0, es * 6 * m->nb * B, w->stream));
+  if (nsteps == 0) return RBD_OK;
+  if ((st = sct_ensure(w))) return st;
+  const size_t slot_bytes = es * (size_t)(m->nq + m->nv + 3 * m->ncp * m->nhs) * B;
+  const SavPlan P = sav_plan(slot_bytes, nsteps);
+  if ((st = ensure(&w->d_sav_ckpt, &w->d_sav_ckpt_bytes, slot_bytes * P.slots))) return st;  // (only a call that needs more room than any before)
+  Timed t(w);
+  w->last_kernel = "value_mk_stage_kernel + contact_kernel + contact_stage_value_kernel + adjoint_mk_stage_kernel + tangent_solve_kernel + adjoint_rnea_kernel + "
+                   "contact_stage_adjoint_kernel + point_adjoint_kernel";
+  return by_dtype(w->dtype, [&](auto t) {
+    return sct_run<decltype(t)>(w, B, o, q, v, s, tau, fext, dt, nsteps, P, q_bar, v_bar, s_bar, tau_bar, fext_bar);
   });
 }
 

@@ -1,5 +1,5 @@
 // rbd_contact.hpp — the soft contact model of one (contact point, half-space) pair and its hand-written pullback (rbd_contact_dynamics_vjp,
-// rbd_dynamics_contact_vjp).  The model is the reference's default (src/contact.jl: HuntCrossleyModel :98-119, ViscoelasticCoulombModel :122-178,
+// rbd_dynamics_contact_vjp), and the friction state's Runge–Kutta tableau with its pullback (rbd_simulate_contact_vjp).  The model is the reference's default (src/contact.jl: HuntCrossleyModel :98-119, ViscoelasticCoulombModel :122-178,
 // HalfSpace3D :202-228) with the arithmetic of contact_kernel (rbd_contact_kernels.hip), which stays the forward path:
 //   sep = (pos − h)·n;  outside (sep > 0): f = 0, ẋ = 0, the friction state x is reset to 0
 //   z = −sep, ż = −vel·n, fn = max(0, λ zⁿ ż + k zⁿ)                       Hunt–Crossley
@@ -157,6 +157,41 @@ template <typename T> RBD_HD bool contact_pair_adjoint(const T* pos, const T* ve
     pos_bar[j] -= zb * n[j];
   }
   return true;
+}
+
+// ---- the friction state through the Runge–Kutta tableau (rbd_simulate_contact_vjp) ---------------------------------------------------------------------------
+// contact_stage_kernel's map (runge_kutta_4, ode_integrators.jl:48-55) in its value form, stage k = 0 … 3 like mk_stage_value_joint: from the step's start s0
+// and ṡ_k at stage state k, the next stage state s_{k+1} = s0 + dt a_k ṡ_k and the running sum acc = Σ_{j ≤ k} dt b_j ṡ_j (stages 0-2; acc is not read at stage
+// 0), or at stage 3 the state after the step s⁺ = s0 + acc + dt b_3 ṡ_3.  The stage states stay apart from s0: the reset of an outside pair's state happens in
+// the stage state only.  Templated on the scalar: tests/test_simulate_contact_vjp_cpu.py takes J·d from the Dual<double, 1> instantiation.
+template <typename T> RBD_HD T contact_tableau_a(int stage) { return stage == 2 ? T(1) : T(0.5); }
+template <typename T> RBD_HD T contact_tableau_b(int stage) { return stage == 0 || stage == 3 ? T(1) / T(6) : T(1) / T(3); }
+
+template <typename S> RBD_HD void contact_stage_value(int stage, typename ScalarOf<S>::type dt, const S& s0, const S& sd, S& acc, S& sn) {
+  using T = typename ScalarOf<S>::type;
+  const T wb = dt * contact_tableau_b<T>(stage), wa = dt * contact_tableau_a<T>(stage);
+  const S sum = stage == 0 ? wb * sd : acc + wb * sd;
+  if (stage < 3) {
+    acc = sum;
+    sn = s0 + wa * sd;
+  } else {
+    sn = s0 + sum;
+  }
+}
+
+// Its pullback, stages 3 … 0.  snb: the cotangent of the stage's output (stage 3: of s⁺).  s0b: the cotangent of s0 collected over the stages done so far
+// (written at 3, added to at 2 … 0); accb: in, the cotangent of the sum out (stages 0-2; ignored at 3), out, that of the sum in (zero at stage 0, which does
+// not read it).  sdb = ṡ̄_k is written.
+template <typename T> RBD_HD void contact_stage_adjoint(int stage, T dt, T snb, T& s0b, T& accb, T& sdb) {
+  const T wb = dt * contact_tableau_b<T>(stage), wa = dt * contact_tableau_a<T>(stage);
+  if (stage == 3) {
+    s0b = snb; accb = snb;
+    sdb = wb * snb;
+  } else {
+    sdb = wa * snb + wb * accb;
+    s0b += snb;
+    if (stage == 0) accb = T(0);
+  }
 }
 
 }  // namespace rbd

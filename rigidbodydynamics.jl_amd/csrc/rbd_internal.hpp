@@ -75,6 +75,10 @@ template <typename T>
 hipError_t launch_contact_adjoint(const ContactModel& M, long B, const void* body, const void* s, const void* wbar, const void* sdbar, const void* sobar, void* sbar,
                                   void* pbar, void* vbar, Layout Ls, Layout Lf, Layout L3, hipStream_t st);
 template <typename T> hipError_t launch_contact_stage(long n, int stage, double dt, void* s, const void* sdot, void* s0, void* acc, hipStream_t st);
+template <typename T> hipError_t launch_contact_stage_value(long n, int stage, double dt, const void* s0, const void* sdot, void* acc, void* sn, hipStream_t st);
+template <typename T>
+hipError_t launch_contact_stage_adjoint(const ContactModel& M, long B, int stage, double dt, const void* body, const void* s, const void* wbar, void* fbar, void* sbar,
+                                        void* s0b, void* accb, void* pbar, void* vbar, Layout Ls, Layout Lf, Layout L3, hipStream_t st);
 // rbd_walk_kernels.hip: one wavefront per track, one lane per state
 template <typename T>
 hipError_t launch_aba_walk(const WalkModel& M, int flt, int gen, int pair, long B, size_t lds_bytes, const void* q, const void* v, const void* tau, const void* fext,

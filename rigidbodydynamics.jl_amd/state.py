@@ -1190,3 +1190,42 @@ def dynamics_contact_vjp_(state: MechanismState, vd_bar: Optional[torch.Tensor] 
                                               _ptr(fext_bar), ctypes.byref(opts))
     _raise(st, "rbd_dynamics_contact_vjp")
     return q_bar, v_bar, s_bar, tau_bar, fext_bar
+
+
+def simulate_contact_vjp_(q_bar: torch.Tensor, v_bar: torch.Tensor, s_bar: torch.Tensor, state: MechanismState, dt: float, nsteps: int = 1,
+                          torques: Optional[torch.Tensor] = None, externalwrenches: Optional[torch.Tensor] = None, tau_bar: Optional[torch.Tensor] = None,
+                          fext_bar: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None,
+                          s: Optional[torch.Tensor] = None):
+    """`nsteps` steps of `simulate_` of a mechanism with contact points pulled back (constant `torques` and `externalwrenches`): `state.q`, `state.v`, `state.s`
+    are advanced in place; `q_bar` (B, nq), `v_bar` (B, nv) and `s_bar` (B, ns) hold the cotangent of the final state on entry and that of the initial state on
+    return; `tau_bar` (B, nv) and `fext_bar` (B, 6·n_bodies), optional, are overwritten with the gradient in the held torques / wrenches, summed over every
+    stage of every step.  The gradient is that of the branch each (point, half-space) pair takes at each stage state.  Per-step torques: one call per step,
+    the cotangent chaining through q_bar, v_bar, s_bar (autograd.simulate_contact does this).  `q` / `v` / `s` (advanced instead of the state's own) default to
+    `state.q` / `state.v` / `state.s`."""
+    f = state.flat
+    q = state.q if q is None else q
+    v = state.v if v is None else v
+    s = state.s if s is None else s
+    if not float(dt) > 0:
+        raise ValueError("dt must be positive")
+    if int(nsteps) < 0:
+        raise ValueError("nsteps must be non-negative")
+    if q_bar is None or v_bar is None or s_bar is None:
+        raise ValueError("q_bar, v_bar and s_bar are required (in / out)")
+    state._check(q, f.nq, "q")
+    state._check(v, f.nv, "v")
+    state._check(s, f.ns, "s")
+    state._check(q_bar, f.nq, "q_bar")
+    state._check(v_bar, f.nv, "v_bar")
+    state._check(s_bar, f.ns, "s_bar")
+    state._check(torques, f.nv, "torques")
+    state._check(externalwrenches, 6 * f.n_bodies, "externalwrenches")
+    state._check(tau_bar, f.nv, "tau_bar")
+    state._check(fext_bar, 6 * f.n_bodies, "fext_bar")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_simulate_contact_vjp(state.ws.handle, state.batch, _ptr(q), _ptr(v), _ptr(s), _ptr(torques), _ptr(externalwrenches),
+                                              ctypes.c_double(dt), int(nsteps), _ptr(q_bar), _ptr(v_bar), _ptr(s_bar), _ptr(tau_bar), _ptr(fext_bar),
+                                              ctypes.byref(opts))
+    _raise(st, "rbd_simulate_contact_vjp")
+    return q_bar, v_bar, s_bar, tau_bar, fext_bar
