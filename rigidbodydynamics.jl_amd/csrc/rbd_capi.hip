@@ -1,53 +1,10 @@
 // rbd_capi.hip — the C ABI of librbd_hip.so (include/rbd_hip.h): model flattening for the device,
 // workspace/stream management, argument checking, kernel dispatch.  No torch types, no CPU fallback:
 // every hot-path entry point launches HIP kernels or fails with a status code.
-#include <hip/hip_runtime.h>
-#include <chrono>
-#include <climits>
-#include <cmath>
-#include <unistd.h>
-
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <new>
-#include <string>
-#include <vector>
-
-#include "rbd_hip.h"
-#include "rbd_internal.hpp"
-#include "rbd_chain_plan.hpp"
-#include "rbd_track_plan.hpp"
-#include "rbd_walk_plan.hpp"
-#include "rbd_reroot.hpp"
-#include "rbd_state_plan.hpp"
-#include "rbd_jit.hpp"
-#include "rbd_mk_fuse.hpp"
-#include "rbd_tangent.hpp"
-#include "rbd_tangent_mk.hpp"
-#include "rbd_adjoint.hpp"
-#include "rbd_adjoint_mk.hpp"
-#include "rbd_point.hpp"
-#include "rbd_point_plan.hpp"
+#include "rbd_capi_internal.hpp"
 enum { BANK_LDS_PAIRS_HOST = 30 };  // = BANK_LDS_PAIRS of rbd_bank.hpp (16 parked + 14 exchange pairs per lane; checked in rbd_bank_kernels.hip)
 
-using namespace rbd;
-
-static thread_local std::string g_last_hip_error;
-
-#define HIP_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ != hipSuccess) {                                                                        \
-      g_last_hip_error = std::string(#expr) + ": " + hipGetErrorString(e_);                        \
-      return (e_ == hipErrorOutOfMemory) ? RBD_ERR_OUT_OF_MEMORY : RBD_ERR_HIP;                    \
-    }                                                                                              \
-  } while (0)
-
-// f(T()) with T the scalar type of `dtype`: one argument list for the fp64 and the fp32 instantiation of a launch
-template <class F>
-static auto by_dtype(int dtype, F&& f) { return dtype == RBD_F64 ? f(double()) : f(float()); }
+thread_local std::string g_last_hip_error;
 
 static int joint_nq_host(int t) {
   switch (t) {
@@ -70,157 +27,9 @@ static int joint_nv_host(int t) {
   }
 }
 
-struct rbd_model {
-  int32_t nb = 0, nq = 0, nv = 0, nc = 0, nloops = 0;
-  int32_t lps = 1, nlevels = 0, maxchild = 0, maxnvj = 0;
-  double gravity[3] = {0, 0, 0};
-  std::vector<int32_t> ib;      // nb * IB_STRIDE
-  std::vector<double> rb;       // nb * RB_STRIDE
-  std::vector<int32_t> nslots;  // nlevels
-  uint64_t perm_down = 0;
-  int32_t inner_floating = 0, has3dof = 0;
-  std::vector<int32_t> slot_of, order;  // reference body index <-> DFS pre-order slot
-  std::vector<int32_t> dof_body;
-  std::vector<int32_t> anc;     // nb * nlevels
-  std::vector<uint64_t> row_mask;  // nv x row_words
-  int32_t row_words = 1;
-  std::vector<rbd_loop_joint_t> loops;
-  std::vector<int32_t> loop_i, loop_path, jt_ref, voff_ref, parent_ref, qoff_ref;  // loop tables (reference body indices)
-  std::vector<int32_t> mk1, mkf;  // the joints as the integrator stage folded into the compiled dynamics! kernels sees them (rbd_mk_fuse.hpp)
-  bool loop_fused_ok = false;
-  bool big = false;  // more than 64 bodies: only the any-size kernels of rbd_big_kernels.hip apply (reference-order tables below)
-  std::vector<int32_t> big_tbl;
-  std::vector<double> big_rb;  // small enough, and only 1-dof / fixed tree joints with parents before children: loop_fused_small_kernel
-  std::vector<double> loop_r, axis_ref, axis2_ref;
-  // banked lane-per-body mapping (aba_bank_kernel): two bodies per lane, split at level bank_L0; bank_lps == 0: not applicable
-  int32_t bank_lps = 0, bank_L0 = 0, bank_nb[2] = {0, 0}, bank_aba_ok = 0;
-  std::vector<int32_t> bank_ib[2];
-  std::vector<double> bank_rb[2];
-  uint64_t bank_perm_down = 0;
-  ChainPlan chain;  // the chains of the tree packed on G tracks by list scheduling: what the track / walk plans are built on (rbd_model_chain_plan exposes it)
-  TrackPlan track;  // the track schedule of the walk kernels (track.ok == false: mechanism outside their scope)
-  // the tree re-rooted at its centre (rbd_reroot.hpp): its own slots, banks and track / walk plans; used by the ABA kernels that support it
-  Reroot rr;
-  struct RrSlots {
-    bool ok = false;
-    int32_t nlevels = 0;
-    std::vector<int32_t> ib, nslots;
-    std::vector<double> rb;
-    TrackPlan track;
-    WalkPlan walk;
-  } rrs;
-  // soft contact (src/contact.jl): points in the order of the additional state, half-spaces with unit normals
-  int32_t ncp = 0, nhs = 0;
-  std::vector<int32_t> cp_body;
-  std::vector<double> cp_r, hs_r;  // ncp * CP_STRIDE, nhs * 6
-  WalkPlan walk;    // parking slots of aba_walk_kernel on top of the track plan (walk.ok == false: track plan missing or too many steps)
-  StatePlan state;  // plan of the one-lane-per-state kernels (state.ok == false: mechanism outside their scope)
-  StatePlan state_wide;  // ... of the ones compiled for the mechanism when it has 3-dof joints / 6-dof joints below the world (state.ok == false, state_wide.ok)
-  const StatePlan& spec_plan() const { return state.ok ? state : state_wide; }
-};
-
-// A program compiled for the mechanism at run time (rbd_jit.hip): `tried` once the answer is final (the module loaded, or no module), its source while the
-// compilation is pending (generated once).  The slots of a workspace: the SPEC_* families at spec_slot(family), then the program of a small loop mechanism, the
-// banked program and the 12 walk programs (SPEC_WALK + 4 kind + 2 rerooted + pair, as spec_walk)
-struct SpecSlot { bool tried = false; hipModule_t mod = nullptr; std::string src; };
-enum { SPEC_LOOP = SPEC_SLOTS, SPEC_BANK, SPEC_WALK, SPEC_PROGRAMS = SPEC_WALK + 12 };
-// the kernel of run_aba's last launch, as far as simulate_core routes by it: the lane-per-state program compiled for the mechanism (aba_spec_*), its fp64 form
-// with the spare rows in the HBM stash (aba_spec_gst_f64), the walk program compiled for the mechanism (aba_walk_spec), any other
-enum AbaProgram { ABA_OTHER, ABA_SPEC, ABA_SPEC_STASH, ABA_WALK_SPEC };
-// a compiled kernel that is held against the kernels built with the library on its first use by a workspace, and whether it has been (first_use)
-struct SpecKernel { hipFunction_t f = nullptr; bool checked = false; };
-
-struct rbd_ws {
-  const rbd_model* model = nullptr;
-  int32_t device = 0, dtype = RBD_F64, max_batch = 0;
-  hipStream_t stream = nullptr;
-  DevModel dm{};
-  BankModel bm{}; void* d_bank_ib[2] = {nullptr, nullptr}; void* d_bank_rb[2] = {nullptr, nullptr};
-  // the re-rooted tree (rbd_reroot.hpp): banked records, chain table, walk plan
-  void* d_rr_chain_i = nullptr; void* d_rr_chain_r = nullptr;
-  WalkModel wm_rr{}; bool walk_rr = false; void* d_rrtrack_ri = nullptr; void* d_rrtrack_rr = nullptr; void* d_rrwalk_wk = nullptr; size_t walk_rr_lds_bytes = 0, walk_rr_lds_bytes_pair = 0;
-  TrackModel tm{}; void* d_track_ri = nullptr; void* d_track_rr = nullptr;  // the track plan's records: what the walk kernels read
-  ContactModel ctm{}; void* d_cp_body = nullptr; void* d_cp_r = nullptr; void* d_hs_r = nullptr;  // soft contact tables
-  void* d_tw = nullptr; void* d_cw = nullptr; void* d_s0 = nullptr; void* d_sacc = nullptr; void* d_sdot = nullptr; void* d_rows = nullptr; size_t d_rows_bytes = 0, d_tw_bytes = 0, d_cw_bytes = 0, d_s0_bytes = 0, d_sacc_bytes = 0, d_sdot_bytes = 0;
-  WalkModel wm{}; void* d_walk_wk = nullptr; size_t walk_lds_bytes = 0, walk_lds_bytes_pair = 0; long walk_min_batch = 0, walk_pair_min_batch = 0, sim_walk_min_batch = 1;
-  // run-time specialised programs (rbd_jit.hip), loaded on the first use of a route that has them (spec_module), and their kernels; null: not available
-  SpecSlot spec_prog[SPEC_PROGRAMS];
-  hipFunction_t spec_kin = nullptr, spec_jac = nullptr, spec_mom = nullptr, spec_energy = nullptr, spec_com = nullptr; long spec_kin_min_batch = (long)1 << 62;  // the kinematics by-products compiled for the mechanism (SPEC_KIN, round 6)
-  hipFunction_t spec_crba = nullptr, spec_crba_perm = nullptr, spec_emit = nullptr, spec_loop = nullptr, spec_bank_fused = nullptr;
-  // (the kernels checked on their first use: first_use)
-  SpecKernel spec_chol, spec_chol_nom, spec_chol_packed;  // (each checked with crba_spec_perm before it: M emitted | M_out = NULL | M as the packed triangle)
-  SpecKernel spec_aba, spec_aba_nofext, spec_aba_gst, spec_aba_gst_nofext, spec_rnea;
-  SpecKernel spec_bank_aba, spec_bank_rnea;  // (the banked programs; spec_bank_aba's check drops spec_bank_fused with it)
-  SpecKernel spec_walk[12];  // [dynamics! | inverse dynamics | dynamics!, four `simulate` stages per launch][re-rooted tree][two fp32 states per lane]
-  int spec_f64_max_scratch = 0;  // (RBD_TUNE spec_f64_max_scratch; set from the measurement in workspace_create)
-  // fp64 dynamics! of those mechanisms: the program with its spare rows in the HBM stash (two wavefronts per CU, a longer chain) against the one with every row in
-  // LDS (one per CU): RBD_TUNE spec_f64_stash = 1 always / 0 never / -1 whichever needs fewer chain-times for the batch; the chains' ratio in percent
-  int spec_f64_stash = -1, spec_f64_stash_ratio = 170, spec_f64_stash_ratio_fext = 120, spec_ncu = 256;
-  // first use of a run-time compiled program by this workspace: its result on the first states of the call against the kernels built with the library
-  // (first_use; RBD_TUNE first_use_check=0 for timing experiments with programs that are wrong by construction)
-  bool spec_first_use_check = true, spec_first_use_inject = false;
-  int spec_aba_scratch = 0, spec_aba_nofext_scratch = 0, spec_rnea_scratch = 0;  // bytes per lane spilled by those kernels: only a kernel without any is picked on its own (it runs 3.4 times slower with: the dispatcher admits fewer wavefronts)
-  bool no_reroot = false, loop_no_fused = false; int spec_max_scratch = 512;  // RBD_TUNE: walk_no_reroot, loop_no_fused (tests: the original tree / the three-launch loop route), spec_max_scratch (spilled bytes per lane above which a compiled kernel steps aside)
-  bool spec_walk_f32 = true;  // fp32 batches through the compiled walk kernels too (RBD_SPEC_WALK_F32=0: not)
-  std::vector<double> loop_gains; bool custom_gains = false;  // rbd_workspace_set_loop_gains: this workspace's Baumgarte gains (4 per loop joint), and whether they differ from the model's
-  void* bound_M = nullptr; void* bound_c = nullptr;  // rbd_workspace_bind_result: the caller's own M / c buffers for the CRBA route of rbd_dynamics
-  long spec_aba_min_batch = 0, spec_rnea_min_batch = 0, spec_walk_min_batch = 0, walk_one_round_batch = 0, rnea_walk_min_batch = 0;
-  StateModel sm{}; void* d_state_ops = nullptr; void* d_state_cols = nullptr; void* d_state_sr = nullptr; long state_min_batch = 0; long mass_min_batch = (long)1 << 62, mass_solve_min_batch = (long)1 << 62; long spec_aba_fused_min_batch = (long)1 << 62; long sim_walk_max_batch = 0; bool state_aot = false;  // state_aot: the interpreting one-lane-per-state kernels take the mechanism
-  void* d_Msoa = nullptr; size_t d_Msoa_bytes = 0; long Msoa_B = -1; int Msoa_perm = -1;  // batch-innermost staging of M for the one-lane-per-state CRBA when the caller's layout is AOS
-  long bank_min_batch = 0, rnea_bank_min_batch = 0, bank_resident_states = 0;
-  void* d_ib = nullptr; void* d_rb = nullptr; void* d_nslots = nullptr; void* d_dof_body = nullptr; void* d_anc = nullptr; void* d_row_mask = nullptr;
-  // staging for RBD_MEM_HOST (lazy; HostIO)
-  void* stage[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t stage_bytes[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  // internal device scratch (mass matrix / bias for the CRBA route), lazy
-  void* d_M = nullptr; void* d_c = nullptr; void* d_K = nullptr; void* d_k = nullptr;
-  size_t d_M_bytes = 0, d_c_bytes = 0, d_K_bytes = 0, d_k_bytes = 0;
-  void* d_body = nullptr; void* d_scratch = nullptr; size_t d_body_bytes = 0, d_scratch_bytes = 0;
-  BigModel big{}; void* d_big_tbl = nullptr; void* d_big_rb = nullptr; void* d_big_scratch = nullptr; size_t d_big_scratch_bytes = 0; void* d_big_L = nullptr; size_t d_big_L_bytes = 0;  // rbd_big_kernels.hip (d_big_L: the Cholesky factor, result.L)
-  void* d_fused_i = nullptr;  // loop_fused_small_kernel: parent, q offset, slot by reference body index
-  void* d_loop_i = nullptr; void* d_loop_r = nullptr; void* d_loop_path = nullptr; void* d_jt_ref = nullptr; void* d_voff_ref = nullptr; void* d_axis_ref = nullptr; void* d_axis2_ref = nullptr;
-  MkBuffers mk{}; void* d_vdwork = nullptr; size_t mk_elems = 0;  // Munthe-Kaas integrator scratch (lazy)
-  void* d_tauwork = nullptr; size_t d_tauwork_bytes = 0;  // torques of the device-side PD controller (un-fused integrator path)
-  int* d_notpd = nullptr;  // device flag: some state's mass matrix was not positive definite (checked by rbd_sync)
-  int32_t result_layout = RBD_LAYOUT_SOA; int32_t result_B = 0;
-  // timing
-  int32_t timing = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool ev_pending = false;
-  const char* last_kernel = "";  // dominant kernel of the last rbd_dynamics / rbd_simulate / rbd_mass_matrix_solve call
-  int last_aba = ABA_OTHER;  // what the last run_aba launched (AbaProgram): simulate_core routes by it
-  // the derivative entry points (rbd_tangent_kernels.hip): the tree in the reference's order for every mechanism (BigModel tables), the tangent scratch
-  // (tan_threads (state, chunk) threads per launch) and the dynamics! buffers — M, its factor, c, v̇, tangent right-hand sides for tan_ntan directions,
-  // and for more than 64 coordinates the solve's own vectors — allocated by the first derivative call and when ntan grows
-  bool tan_ready = false; BigModel tan{}; void* d_tan_tbl = nullptr; void* d_tan_rb = nullptr; void* d_tan_scratch = nullptr; size_t d_tan_scratch_bytes = 0; long tan_threads = 0; int tan_ntan = 0;
-  void* d_tan_M = nullptr; void* d_tan_L = nullptr; void* d_tan_c = nullptr; void* d_tan_vd = nullptr; void* d_tan_rhs = nullptr; void* d_tan_x = nullptr;
-  size_t d_tan_M_bytes = 0, d_tan_L_bytes = 0, d_tan_c_bytes = 0, d_tan_vd_bytes = 0, d_tan_rhs_bytes = 0, d_tan_x_bytes = 0;
-  // the simulate derivatives (rbd_simulate_jvp, rbd_simulate_step_derivatives): the stage states' values, and the tangents of one pass of sim_tan_w directions
-  void* d_sim_val = nullptr; void* d_sim_tan = nullptr; size_t d_sim_val_bytes = 0, d_sim_tan_bytes = 0; int sim_tan_w = 0;
-  // the reverse-mode entry points (rbd_inverse_dynamics_vjp, rbd_dynamics_vjp): the adjoint scratch (adj_states states per launch), the cotangent of v̇
-  // staged batch-innermost, λ = M⁻¹ v̇̄ when the caller passes no τ̄, and for more than 64 coordinates the solve's own vector
-  bool adj_ready = false; long adj_states = 0;
-  void* d_adj_scratch = nullptr; void* d_adj_rhs = nullptr; void* d_adj_lam = nullptr; void* d_adj_x = nullptr;
-  size_t d_adj_scratch_bytes = 0, d_adj_rhs_bytes = 0, d_adj_lam_bytes = 0, d_adj_x_bytes = 0;
-  // rbd_simulate_vjp: the joints by class (1-coordinate / the rest, (jtype, qoff, voff) each), the stage states of one step and the cotangents of the
-  // backward pass (d_sav), and the step starts kept (d_sav_ckpt, sav_ckpt_bytes)
-  bool sav_ready = false; int sav_nn = 0, sav_nw = 0;
-  void* d_sav_joints = nullptr; void* d_sav = nullptr; void* d_sav_ckpt = nullptr; size_t d_sav_bytes = 0, d_sav_ckpt_bytes = 0;
-  // rbd_workspace_set_points: the points' tables (rbd_point.hpp PointPlan; d_pt_i: poff, path, uni, ubeg, upts in one buffer, d_pt_r: the points); the tables of
-  // `tan` are built by then (tan_tbl_ready) without the dynamics! buffers of the derivative entry points
-  bool tan_tbl_ready = false; PointPlan pts{}; void* d_pt_i = nullptr; void* d_pt_r = nullptr;
-  // rbd_contact_dynamics_vjp / rbd_dynamics_contact_vjp: the model's contact points as a PointPlan of their own (a caller's points stay), the per-point
-  // cotangents contact_adjoint_kernel hands to point_adjoint_kernel, the total wrenches' cotangent when the caller takes no fext_bar, and the copy of s the
-  // forward contact launch resets
-  bool ct_ready = false; PointPlan ct_pts{}; void* d_ct_i = nullptr; void* d_ct_r = nullptr; void* d_ct_pbar = nullptr; void* d_ct_vbar = nullptr;
-  void* d_ct_wbar = nullptr; void* d_ct_s = nullptr;
-  // rbd_simulate_contact_vjp: the friction state's stage states 1-3, running sum and ṡ of one step, and the cotangents of s0 and of the sum (7 ns values per state)
-  bool sct_ready = false; void* d_sct = nullptr; size_t d_sct_bytes = 0;
-};
-
 // RBD_TUNE="key=value,key=value,...": the developer knobs of the tests and sweep scripts in ONE environment variable (batch thresholds between the lane
 // mappings, routes forced off).  Read when a model / workspace is created; `has`: the key was given.  Users need none of them.
-static long tune(const char* key, long dflt, bool* has = nullptr) {
+long tune(const char* key, long dflt, bool* has) {
   if (has) *has = false;
   const char* e = getenv("RBD_TUNE");
   if (!e) return dflt;
@@ -797,35 +606,22 @@ int rbd_model_dims(const rbd_model_t* m, int32_t* nb, int32_t* nq, int32_t* nv, 
   return RBD_OK;
 }
 
-static int upload(void** dst, const void* src, size_t bytes) {
-  HIP_TRY(hipMalloc(dst, bytes ? bytes : 16));
-  if (bytes) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-  return RBD_OK;
-}
-
-// a table of real numbers, in the scalar type of `dtype`
-static int upload_real(void** dst, const std::vector<double>& src, int dtype) {
-  if (dtype == RBD_F64) return upload(dst, src.data(), src.size() * sizeof(double));
-  const std::vector<float> f(src.begin(), src.end());
-  return upload(dst, f.data(), f.size() * sizeof(float));
-}
-
 // the loop joints' tables on the device (workspace copies: rbd_workspace_set_loop_gains rewrites the gains in place)
 static int upload_loop_tables(rbd_ws* w, const rbd_model* m, int dtype) {
   int st = RBD_OK;
   if (st == RBD_OK && m->nloops > 0) {
-    st = upload(&w->d_loop_i, m->loop_i.data(), m->loop_i.size() * sizeof(int32_t));
-    if (st == RBD_OK) st = upload(&w->d_loop_path, m->loop_path.data(), m->loop_path.size() * sizeof(int32_t));
-    if (st == RBD_OK) st = upload(&w->d_jt_ref, m->jt_ref.data(), m->jt_ref.size() * sizeof(int32_t));
-    if (st == RBD_OK) st = upload(&w->d_voff_ref, m->voff_ref.data(), m->voff_ref.size() * sizeof(int32_t));
+    st = upload(w->d_loop_i, m->loop_i.data(), m->loop_i.size() * sizeof(int32_t));
+    if (st == RBD_OK) st = upload(w->d_loop_path, m->loop_path.data(), m->loop_path.size() * sizeof(int32_t));
+    if (st == RBD_OK) st = upload(w->d_jt_ref, m->jt_ref.data(), m->jt_ref.size() * sizeof(int32_t));
+    if (st == RBD_OK) st = upload(w->d_voff_ref, m->voff_ref.data(), m->voff_ref.size() * sizeof(int32_t));
     if (st == RBD_OK && m->loop_fused_ok) {
       std::vector<int32_t> xi(3 * (size_t)m->nb);
       for (int i = 0; i < m->nb; ++i) { xi[3 * i] = m->parent_ref[i]; xi[3 * i + 1] = m->qoff_ref[i]; xi[3 * i + 2] = m->slot_of[i]; }
-      st = upload(&w->d_fused_i, xi.data(), xi.size() * sizeof(int32_t));
+      st = upload(w->d_fused_i, xi.data(), xi.size() * sizeof(int32_t));
     }
-    if (st == RBD_OK) st = upload_real(&w->d_loop_r, m->loop_r, dtype);
-    if (st == RBD_OK) st = upload_real(&w->d_axis_ref, m->axis_ref, dtype);
-    if (st == RBD_OK) st = upload_real(&w->d_axis2_ref, m->axis2_ref, dtype);
+    if (st == RBD_OK) st = upload_real(w->d_loop_r, m->loop_r, dtype);
+    if (st == RBD_OK) st = upload_real(w->d_axis_ref, m->axis_ref, dtype);
+    if (st == RBD_OK) st = upload_real(w->d_axis2_ref, m->axis2_ref, dtype);
   }
   return st;
 }
@@ -833,12 +629,12 @@ static int upload_loop_tables(rbd_ws* w, const rbd_model* m, int dtype) {
 // soft contact: the points' and half-spaces' tables on the device (contact_kernel)
 static int upload_contact_tables(rbd_ws* w, const rbd_model* m, int dtype) {
   if (m->ncp <= 0) return RBD_OK;
-  int st = upload(&w->d_cp_body, m->cp_body.data(), m->cp_body.size() * sizeof(int32_t));
-  if (st == RBD_OK) st = upload_real(&w->d_cp_r, m->cp_r, dtype);
-  if (st == RBD_OK) st = upload_real(&w->d_hs_r, m->hs_r, dtype);
+  int st = upload(w->d_cp_body, m->cp_body.data(), m->cp_body.size() * sizeof(int32_t));
+  if (st == RBD_OK) st = upload_real(w->d_cp_r, m->cp_r, dtype);
+  if (st == RBD_OK) st = upload_real(w->d_hs_r, m->hs_r, dtype);
   if (st != RBD_OK) return st;
   w->ctm.nb = m->nb; w->ctm.np = m->ncp; w->ctm.nh = m->nhs;
-  w->ctm.cbody = (const int32_t*)w->d_cp_body; w->ctm.cp = w->d_cp_r; w->ctm.hs = w->d_hs_r;
+  w->ctm.cbody = (const int32_t*)w->d_cp_body.p; w->ctm.cp = w->d_cp_r.p; w->ctm.hs = w->d_hs_r.p;
   return RBD_OK;
 }
 
@@ -852,33 +648,34 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
   }
   if (device < 0 || device >= ndev) return RBD_ERR_INVALID_ARGUMENT;
   HIP_TRY(hipSetDevice(device));
-  rbd_ws* w = new (std::nothrow) rbd_ws();
+  std::unique_ptr<rbd_ws> owner(new (std::nothrow) rbd_ws());  // (an early return below frees what was uploaded so far)
+  rbd_ws* w = owner.get();
   if (!w) return RBD_ERR_OUT_OF_MEMORY;
   w->model = m; w->device = device; w->dtype = dtype; w->max_batch = max_batch; w->stream = (hipStream_t)stream;
   if (m->big) {  // the any-size fallback needs its two tables only
-    int st = upload(&w->d_big_tbl, m->big_tbl.data(), m->big_tbl.size() * sizeof(int32_t));
-    if (st == RBD_OK) st = upload_real(&w->d_big_rb, m->big_rb, dtype);
-    if (st == RBD_OK) { int zero = 0; st = upload((void**)&w->d_notpd, &zero, sizeof(int)); }
+    int st = upload(w->d_big_tbl, m->big_tbl.data(), m->big_tbl.size() * sizeof(int32_t));
+    if (st == RBD_OK) st = upload_real(w->d_big_rb, m->big_rb, dtype);
+    if (st == RBD_OK) { int zero = 0; st = upload(w->d_notpd, &zero, sizeof(int)); }
     if (st == RBD_OK) st = upload_loop_tables(w, m, dtype);
     if (st == RBD_OK) st = upload_contact_tables(w, m, dtype);
-    if (st != RBD_OK) { rbd_workspace_destroy(w); return st; }
-    w->big.nb = m->nb; w->big.nq = m->nq; w->big.nv = m->nv; w->big.tbl = (const int32_t*)w->d_big_tbl; w->big.rb = w->d_big_rb;
+    if (st != RBD_OK) return st;
+    w->big.nb = m->nb; w->big.nq = m->nq; w->big.nv = m->nv; w->big.tbl = (const int32_t*)w->d_big_tbl.p; w->big.rb = w->d_big_rb.p;
     memcpy(w->big.gravity, m->gravity, sizeof w->big.gravity);
     w->last_kernel = "big_* kernels (one thread per state, HBM scratch)";
-    *out = w;
+    *out = owner.release();
     return RBD_OK;
   }
-  int st = upload(&w->d_ib, m->ib.data(), m->ib.size() * sizeof(int32_t));
-  if (st == RBD_OK) st = upload_real(&w->d_rb, m->rb, dtype);
-  if (st == RBD_OK) st = upload(&w->d_dof_body, m->dof_body.data(), m->dof_body.size() * sizeof(int32_t));
-  if (st == RBD_OK) st = upload(&w->d_anc, m->anc.data(), m->anc.size() * sizeof(int32_t));
-  if (st == RBD_OK) st = upload(&w->d_row_mask, m->row_mask.data(), m->row_mask.size() * sizeof(uint64_t));
-  if (st == RBD_OK) { int zero = 0; st = upload((void**)&w->d_notpd, &zero, sizeof(int)); }
+  int st = upload(w->d_ib, m->ib.data(), m->ib.size() * sizeof(int32_t));
+  if (st == RBD_OK) st = upload_real(w->d_rb, m->rb, dtype);
+  if (st == RBD_OK) st = upload(w->d_dof_body, m->dof_body.data(), m->dof_body.size() * sizeof(int32_t));
+  if (st == RBD_OK) st = upload(w->d_anc, m->anc.data(), m->anc.size() * sizeof(int32_t));
+  if (st == RBD_OK) st = upload(w->d_row_mask, m->row_mask.data(), m->row_mask.size() * sizeof(uint64_t));
+  if (st == RBD_OK) { int zero = 0; st = upload(w->d_notpd, &zero, sizeof(int)); }
   if (st == RBD_OK) st = upload_loop_tables(w, m, dtype);
-  if (st != RBD_OK) { rbd_workspace_destroy(w); return st; }
+  if (st != RBD_OK) return st;
   DevModel& dm = w->dm;
   dm.nb = m->nb; dm.nq = m->nq; dm.nv = m->nv; dm.lps = m->lps; dm.nlevels = m->nlevels; dm.maxchild = m->maxchild; dm.maxnvj = m->maxnvj;
-  dm.ib = (const int32_t*)w->d_ib; dm.rb = w->d_rb;
+  dm.ib = (const int32_t*)w->d_ib.p; dm.rb = w->d_rb.p;
   dm.perm_down = m->perm_down;
   dm.inner_floating = m->inner_floating;
   dm.has3dof = m->has3dof;
@@ -890,17 +687,17 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
     ++dm.nheavy;
   }
   nslots_pack_desc(dm.ns_desc, m->nslots.data(), m->nlevels);
-  dm.dof_body = (const int32_t*)w->d_dof_body; dm.anc = (const int32_t*)w->d_anc; dm.row_mask = (const uint64_t*)w->d_row_mask; dm.row_words = m->row_words;
+  dm.dof_body = (const int32_t*)w->d_dof_body.p; dm.anc = (const int32_t*)w->d_anc.p; dm.row_mask = (const uint64_t*)w->d_row_mask.p; dm.row_words = m->row_words;
   memcpy(dm.gravity, m->gravity, sizeof dm.gravity);
   if (m->bank_lps > 0) {
     BankModel& bm = w->bm;
     for (int k = 0; k < 2 && st == RBD_OK; ++k) {
-      st = upload(&w->d_bank_ib[k], m->bank_ib[k].data(), m->bank_ib[k].size() * sizeof(int32_t));
+      st = upload(w->d_bank_ib[k], m->bank_ib[k].data(), m->bank_ib[k].size() * sizeof(int32_t));
       if (st != RBD_OK) break;
-      st = upload_real(&w->d_bank_rb[k], m->bank_rb[k], dtype);
-      bm.ib[k] = (const int32_t*)w->d_bank_ib[k]; bm.rb[k] = w->d_bank_rb[k]; bm.nbk[k] = m->bank_nb[k];
+      st = upload_real(w->d_bank_rb[k], m->bank_rb[k], dtype);
+      bm.ib[k] = (const int32_t*)w->d_bank_ib[k].p; bm.rb[k] = w->d_bank_rb[k].p; bm.nbk[k] = m->bank_nb[k];
     }
-    if (st != RBD_OK) { rbd_workspace_destroy(w); return st; }
+    if (st != RBD_OK) return st;
     bm.lps = m->bank_lps; bm.nlevels = m->nlevels; bm.L0 = m->bank_L0; bm.perm_down = m->bank_perm_down;
     bm.simple = bank_simple(m);  // every tree joint revolute, apart from 6-dof joints on the world
     if (tune("bank_generic", 0)) bm.simple = 0;  // tests: the generic instantiation on a mechanism the SIMPLE one would take
@@ -932,20 +729,20 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
   if (m->rrs.ok) {
     const Reroot& R = m->rr;
     const rbd_model::RrSlots& S = m->rrs;
-    st = upload(&w->d_rr_chain_i, R.chain_i.data(), R.chain_i.size() * sizeof(int32_t));
-    if (st == RBD_OK) st = upload_real(&w->d_rr_chain_r, R.chain_r, dtype);
+    st = upload(w->d_rr_chain_i, R.chain_i.data(), R.chain_i.size() * sizeof(int32_t));
+    if (st == RBD_OK) st = upload_real(w->d_rr_chain_r, R.chain_r, dtype);
     RerootView V{};
     V.nchain = (int32_t)(R.chain_i.size() / RC_I_STRIDE); V.fq = R.fq; V.fv = R.fv;
-    V.chain_i = (const int32_t*)w->d_rr_chain_i; V.chain_r = w->d_rr_chain_r;
+    V.chain_i = (const int32_t*)w->d_rr_chain_i.p; V.chain_r = w->d_rr_chain_r.p;
     memcpy(V.fXp, R.fXp, sizeof V.fXp);
     if (st == RBD_OK && S.track.ok && S.walk.ok) {
       const TrackPlan& P = S.track;
-      st = upload(&w->d_rrtrack_ri, P.ri.data(), P.ri.size() * sizeof(int32_t));
-      if (st == RBD_OK) st = upload_real(&w->d_rrtrack_rr, P.rr, dtype);
-      if (st == RBD_OK) st = upload(&w->d_rrwalk_wk, S.walk.wk.data(), S.walk.wk.size() * sizeof(int32_t));
+      st = upload(w->d_rrtrack_ri, P.ri.data(), P.ri.size() * sizeof(int32_t));
+      if (st == RBD_OK) st = upload_real(w->d_rrtrack_rr, P.rr, dtype);
+      if (st == RBD_OK) st = upload(w->d_rrwalk_wk, S.walk.wk.data(), S.walk.wk.size() * sizeof(int32_t));
       WalkModel& wm = w->wm_rr;
       wm.ns = P.ns; wm.G = P.G; wm.nA = P.nA; wm.nB = P.nB; wm.nS = S.walk.nS; wm.nq = m->nq; wm.nv = m->nv; wm.reroot = V;
-      wm.ri = (const int32_t*)w->d_rrtrack_ri; wm.rr = w->d_rrtrack_rr; wm.wk = (const int32_t*)w->d_rrwalk_wk;
+      wm.ri = (const int32_t*)w->d_rrtrack_ri.p; wm.rr = w->d_rrtrack_rr.p; wm.wk = (const int32_t*)w->d_rrwalk_wk.p;
       for (int k = 0; k < 5; ++k) { wm.sfm[k] = 0; for (int s2 = 0; s2 < P.ns; ++s2) wm.sfm[k] |= (uint64_t)((P.sf[s2] >> k) & 1) << s2; }
       memcpy(wm.gravity, m->gravity, sizeof wm.gravity);
       const size_t es2 = dtype == RBD_F64 ? 8 : 4;
@@ -955,23 +752,23 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
       if (w->walk_rr_lds_bytes_pair > 160 * 1024) w->walk_rr_lds_bytes_pair = 0;
       w->walk_rr = st == RBD_OK && (w->walk_rr_lds_bytes > 0 || w->walk_rr_lds_bytes_pair > 0);
     }
-    if (st != RBD_OK) { rbd_workspace_destroy(w); return st; }
+    if (st != RBD_OK) return st;
   }
   if (m->track.ok) {
     const TrackPlan& P = m->track;
-    st = upload(&w->d_track_ri, P.ri.data(), P.ri.size() * sizeof(int32_t));
-    if (st == RBD_OK) st = upload_real(&w->d_track_rr, P.rr, dtype);
-    if (st != RBD_OK) { rbd_workspace_destroy(w); return st; }
+    st = upload(w->d_track_ri, P.ri.data(), P.ri.size() * sizeof(int32_t));
+    if (st == RBD_OK) st = upload_real(w->d_track_rr, P.rr, dtype);
+    if (st != RBD_OK) return st;
     TrackModel& tm = w->tm;
-    tm.ns = P.ns; tm.G = P.G; tm.nA = P.nA; tm.nB = P.nB; tm.ri = (const int32_t*)w->d_track_ri; tm.rr = w->d_track_rr;
+    tm.ns = P.ns; tm.G = P.G; tm.nA = P.nA; tm.nB = P.nB; tm.ri = (const int32_t*)w->d_track_ri.p; tm.rr = w->d_track_rr.p;
     for (int k = 0; k < 5; ++k) { tm.sfm[k] = 0; for (int s2 = 0; s2 < P.ns; ++s2) tm.sfm[k] |= (uint64_t)((P.sf[s2] >> k) & 1) << s2; }
     memcpy(tm.gravity, m->gravity, sizeof tm.gravity);
   }
-  if ((st = upload_contact_tables(w, m, dtype)) != RBD_OK) { rbd_workspace_destroy(w); return st; }
+  if ((st = upload_contact_tables(w, m, dtype)) != RBD_OK) return st;
   if (m->track.ok && m->walk.ok) {
     const TrackPlan& P = m->track;
-    st = upload(&w->d_walk_wk, m->walk.wk.data(), m->walk.wk.size() * sizeof(int32_t));
-    if (st != RBD_OK) { rbd_workspace_destroy(w); return st; }
+    st = upload(w->d_walk_wk, m->walk.wk.data(), m->walk.wk.size() * sizeof(int32_t));
+    if (st != RBD_OK) return st;
     // the walk kernel compiled for the mechanism (aba_walk_spec): from the batch size at which RBD_ALGO_ABA picks the walk kernel by itself on a humanoid — smaller
     // batches that force the mapping (tests, sweeps) keep the interpreting kernel and its zero start-up cost (the compile takes about a minute per mechanism, once)
     w->spec_walk_min_batch = 8192;
@@ -979,7 +776,7 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
     w->spec_walk_f32 = tune("spec_walk_f32", 1) != 0;
     WalkModel& wm = w->wm;
     wm.ns = P.ns; wm.G = P.G; wm.nA = P.nA; wm.nB = P.nB; wm.nS = m->walk.nS; wm.nq = m->nq; wm.nv = m->nv;
-    wm.ri = (const int32_t*)w->d_track_ri; wm.rr = w->d_track_rr; wm.wk = (const int32_t*)w->d_walk_wk;
+    wm.ri = (const int32_t*)w->d_track_ri.p; wm.rr = w->d_track_rr.p; wm.wk = (const int32_t*)w->d_walk_wk.p;
     for (int k = 0; k < 5; ++k) wm.sfm[k] = w->tm.sfm[k];
     memcpy(wm.gravity, m->gravity, sizeof wm.gravity);
     const size_t es = dtype == RBD_F64 ? 8 : 4;
@@ -991,7 +788,7 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
     {
       const size_t l1 = std::max(w->walk_lds_bytes, w->walk_rr ? w->walk_rr_lds_bytes : (size_t)0), l2 = std::max(w->walk_lds_bytes_pair, w->walk_rr ? w->walk_rr_lds_bytes_pair : (size_t)0);
       const hipError_t e = by_dtype(dtype, [&](auto t) { return configure_walk_kernel<decltype(t)>(P.has_floating, P.general, l1, l2); });  // (l2 = 0 in fp64)
-      if (e != hipSuccess) { g_last_hip_error = std::string("configure_walk_kernel: ") + hipGetErrorString(e); rbd_workspace_destroy(w); return RBD_ERR_HIP; }
+      if (e != hipSuccess) { g_last_hip_error = std::string("configure_walk_kernel: ") + hipGetErrorString(e); return RBD_ERR_HIP; }
     }
     // the packed form from the batch size at which the 64-state workgroups no longer fit the chip in one round (RBD_WALK_PAIR_MIN_BATCH overrides)
     {
@@ -1021,13 +818,13 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
   }
   if (m->state.ok && m->state.nlevels <= state_max_levels(dtype == RBD_F64 ? 8 : 4)) {
     const StatePlan& P = m->state;
-    st = upload(&w->d_state_ops, P.ops.data(), P.ops.size() * sizeof(int32_t));
-    if (st == RBD_OK) st = upload(&w->d_state_cols, P.cols.data(), P.cols.size() * sizeof(int32_t));
-    if (st == RBD_OK) st = upload_real(&w->d_state_sr, P.sr, dtype);
-    if (st != RBD_OK) { rbd_workspace_destroy(w); return st; }
+    st = upload(w->d_state_ops, P.ops.data(), P.ops.size() * sizeof(int32_t));
+    if (st == RBD_OK) st = upload(w->d_state_cols, P.cols.data(), P.cols.size() * sizeof(int32_t));
+    if (st == RBD_OK) st = upload_real(w->d_state_sr, P.sr, dtype);
+    if (st != RBD_OK) return st;
     StateModel& sm = w->sm;
     sm.nb = m->nb; sm.nq = m->nq; sm.nv = m->nv; sm.nops = P.nops; sm.nlevels = P.nlevels;
-    sm.ops = (const int32_t*)w->d_state_ops; sm.cols = (const int32_t*)w->d_state_cols; sm.sr = w->d_state_sr; sm.row_mask = (const uint64_t*)w->d_row_mask;
+    sm.ops = (const int32_t*)w->d_state_ops.p; sm.cols = (const int32_t*)w->d_state_cols.p; sm.sr = w->d_state_sr.p; sm.row_mask = (const uint64_t*)w->d_row_mask.p;
     memcpy(sm.gravity, m->gravity, sizeof sm.gravity);
     // a lane per state pays once every SIMD of the chip has a wavefront of them (64 states x 4 SIMDs x CUs); below that the
     // lane-per-body kernels spread a small batch over more of the chip
@@ -1095,31 +892,16 @@ int rbd_workspace_create(const rbd_model_t* m, int32_t max_batch, int32_t device
   w->spec_first_use_inject = tune("first_use_inject", 0) != 0;  // (tests: every check finds a difference — the drop-and-recompute path of each route without a wrong program)
   {
     const hipError_t e = by_dtype(dtype, [](auto t) { return configure_bank_kernels<decltype(t)>(); });
-    if (e != hipSuccess) { g_last_hip_error = std::string("configure_bank_kernels: ") + hipGetErrorString(e); rbd_workspace_destroy(w); return RBD_ERR_HIP; }
+    if (e != hipSuccess) { g_last_hip_error = std::string("configure_bank_kernels: ") + hipGetErrorString(e); return RBD_ERR_HIP; }
   }
   dm.debug_stop = 0;
   w->no_reroot = tune("walk_no_reroot", 0) != 0; w->loop_no_fused = tune("loop_no_fused", 0) != 0; w->spec_max_scratch = (int)tune("spec_max_scratch", 512);
-  *out = w;
+  *out = owner.release();
   return RBD_OK;
 }
 
 int rbd_workspace_destroy(rbd_ws_t* w) {
-  if (!w) return RBD_OK;
-  (void)hipSetDevice(w->device);
-  void* ptrs[] = {w->d_big_L, w->d_big_tbl, w->d_big_rb, w->d_big_scratch, w->d_fused_i, w->d_tauwork, w->d_rr_chain_i, w->d_rr_chain_r, w->d_rrtrack_ri, w->d_rrtrack_rr, w->d_rrwalk_wk, w->d_cp_body, w->d_cp_r, w->d_hs_r, w->d_tw, w->d_cw, w->d_s0, w->d_sacc, w->d_sdot, w->d_rows, w->d_walk_wk, w->d_state_ops, w->d_state_cols, w->d_state_sr, w->d_Msoa, w->d_track_ri, w->d_track_rr, w->d_bank_ib[0], w->d_bank_ib[1], w->d_bank_rb[0], w->d_bank_rb[1], w->d_ib, w->d_rb, w->d_nslots, w->d_dof_body, w->d_anc, w->d_row_mask, w->d_M, w->d_c, w->d_K, w->d_k, (void*)w->d_notpd, w->d_body, w->d_scratch, w->d_loop_i, w->d_loop_r, w->d_loop_path, w->d_jt_ref, w->d_voff_ref, w->d_axis_ref, w->d_axis2_ref,
-                  w->d_tan_tbl, w->d_tan_rb, w->d_tan_scratch, w->d_tan_M, w->d_tan_L, w->d_tan_c, w->d_tan_vd, w->d_tan_rhs, w->d_tan_x,
-                  w->d_sim_val, w->d_sim_tan, w->d_adj_scratch, w->d_adj_rhs, w->d_adj_lam, w->d_adj_x, w->d_sav_joints, w->d_sav, w->d_sav_ckpt, w->d_pt_i, w->d_pt_r,
-                  w->d_ct_i, w->d_ct_r, w->d_ct_pbar, w->d_ct_vbar, w->d_ct_wbar, w->d_ct_s, w->d_sct};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  for (void* p : w->stage) if (p) (void)hipFree(p);
-  {
-    void* mkp[] = {w->mk.q0, w->mk.v0, w->mk.phid[0], w->mk.phid[1], w->mk.phid[2], w->mk.phid[3], w->mk.vd[0], w->mk.vd[1], w->mk.vd[2], w->mk.vd[3], w->d_vdwork};
-    for (void* p : mkp) if (p) (void)hipFree(p);
-  }
-  for (const SpecSlot& p : w->spec_prog) if (p.mod) (void)hipModuleUnload(p.mod);
-  if (w->ev0) (void)hipEventDestroy(w->ev0);
-  if (w->ev1) (void)hipEventDestroy(w->ev1);
-  delete w;
+  delete w;  // (~rbd_ws; the buffers free themselves)
   return RBD_OK;
 }
 
@@ -1154,7 +936,7 @@ int rbd_workspace_set_loop_gains(rbd_ws_t* w, const double* gains) {
   for (int l = 0; l < m->nloops; ++l) {
     double g64[4]; float g32[4];
     for (int k = 0; k < 4; ++k) { g64[k] = want[4 * (size_t)l + k]; g32[k] = (float)g64[k]; }
-    HIP_TRY(hipMemcpy((char*)w->d_loop_r + es * (64 * (size_t)l + 24), w->dtype == RBD_F64 ? (const void*)g64 : (const void*)g32, 4 * es, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy((char*)w->d_loop_r.p + es * (64 * (size_t)l + 24), w->dtype == RBD_F64 ? (const void*)g64 : (const void*)g32, 4 * es, hipMemcpyHostToDevice));
   }
   w->loop_gains = want;
   w->custom_gains = custom;
@@ -1180,9 +962,9 @@ int rbd_sync(rbd_ws_t* w) {
   HIP_TRY(hipSetDevice(w->device));
   HIP_TRY(hipStreamSynchronize(w->stream));
   int flag = 0;
-  HIP_TRY(hipMemcpy(&flag, w->d_notpd, sizeof(int), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&flag, (int*)w->d_notpd.p, sizeof(int), hipMemcpyDeviceToHost));
   if (flag) {
-    HIP_TRY(hipMemset(w->d_notpd, 0, sizeof(int)));
+    HIP_TRY(hipMemset((int*)w->d_notpd.p, 0, sizeof(int)));
     return RBD_ERR_NOT_POSITIVE_DEFINITE;  // LAPACK.potrf! would have thrown PosDefException
   }
   return RBD_OK;
@@ -1211,90 +993,26 @@ int rbd_workspace_last_kernel_ms(rbd_ws_t* w, float* ms) {
 }  // extern "C"
 
 // ---- dispatch helpers -------------------------------------------------------------------------
-namespace {
-
-size_t esize(const rbd_ws* w) { return w->dtype == RBD_F64 ? 8 : 4; }
-
-Layout layout_of(int layout, long n, long B) {
-  Layout L;
-  if (layout == RBD_LAYOUT_AOS) { L.sk = 1; L.sb = n; } else { L.sk = B; L.sb = 1; }
-  return L;
-}
-
-// a buffer with n scalars per state may only be missing when n == 0 (a mechanism whose tree joints are all Fixed has nq = nv = 0)
-inline bool missing(const void* p, long n) { return p == nullptr && n > 0; }
-
-struct Opts { int layout, memory, algorithm, stabilization; };
-
-// What every entry point that takes a batch checks first, in this order: the workspace, the model's size, the batch, the layout and the memory kind.  *o: the
-// options (the defaults when opts is NULL).  `any_size`: the entry point runs models of more than 64 bodies (on the any-size kernels of rbd_big_kernels.hip);
-// the others refuse them
-const bool kAnySize = true, kUpTo64Bodies = false;
-int begin_call(rbd_ws* w, int32_t B, const rbd_opts_t* opts, bool any_size, Opts* o) {
-  *o = opts ? Opts{opts->layout, opts->memory, opts->algorithm, opts->stabilization} : Opts{RBD_LAYOUT_SOA, RBD_MEM_DEVICE, RBD_ALGO_ABA, 1};
-  if (!w) return RBD_ERR_INVALID_ARGUMENT;
-  if (w->model->big && !any_size) return RBD_ERR_UNSUPPORTED;
-  if (B < 0 || B > w->max_batch) return RBD_ERR_DIMENSION_MISMATCH;
-  if (o->layout != RBD_LAYOUT_SOA && o->layout != RBD_LAYOUT_AOS) return RBD_ERR_INVALID_ARGUMENT;
-  if (o->memory != RBD_MEM_DEVICE && o->memory != RBD_MEM_HOST) return RBD_ERR_INVALID_ARGUMENT;
+int ensure(DevBuf& b, size_t need) {
+  if (b.bytes >= need) return RBD_OK;
+  b.reset();
+  HIP_TRY(hipMalloc(&b.p, need));
+  b.bytes = need;
   return RBD_OK;
 }
 
-struct Timed {
-  rbd_ws* w;
-  explicit Timed(rbd_ws* w_) : w(w_) { if (w->timing) (void)hipEventRecord(w->ev0, w->stream); }
-  ~Timed() { if (w->timing) { (void)hipEventRecord(w->ev1, w->stream); w->ev_pending = true; } }
-};
-
-int ensure(void** p, size_t* have, size_t need) {
-  if (*have >= need) return RBD_OK;
-  if (*p) HIP_TRY(hipFree(*p));
-  *p = nullptr; *have = 0;
-  HIP_TRY(hipMalloc(p, need));
-  *have = need;
+int upload(DevBuf& dst, const void* src, size_t bytes) {
+  dst.reset();  // (a table is uploaded once; one left by a call that failed half way is replaced)
+  if (int st = ensure(dst, bytes ? bytes : 16)) return st;
+  if (bytes) HIP_TRY(hipMemcpy(dst.p, src, bytes, hipMemcpyHostToDevice));
   return RBD_OK;
 }
 
-// The buffers of one call.  RBD_MEM_HOST: each buffer the caller passes is staged in a device buffer of the workspace (w->stage, taken in the order the
-// buffers are registered) — in() and inout() copy it there at once, finish() copies every out() and inout() buffer back; asynchronously on the workspace's
-// stream (the caller synchronises, rbd_sync).  RBD_MEM_DEVICE: every pointer is the device buffer itself.  A NULL buffer stays NULL.
-class HostIO {
- public:
-  HostIO(rbd_ws* w, int memory) : w_(w), host_(memory == RBD_MEM_HOST) {}
-  int in(const void* src, size_t bytes, const void** dev) {
-    void* d;
-    const int st = stage(const_cast<void*>(src), bytes, true, false, &d);
-    *dev = d;
-    return st;
-  }
-  int out(void* dst, size_t bytes, void** dev) { return stage(dst, bytes, false, true, dev); }
-  int inout(void* buf, size_t bytes, void** dev) { return stage(buf, bytes, true, true, dev); }
-  int finish() {
-    for (int k = 0; k < nout_; ++k) HIP_TRY(hipMemcpyAsync(out_[k].host, out_[k].dev, out_[k].bytes, hipMemcpyDeviceToHost, w_->stream));
-    return RBD_OK;
-  }
-
- private:
-  enum { kSlots = sizeof(rbd_ws::stage) / sizeof(void*) };
-  struct Out { void* host; const void* dev; size_t bytes; };
-  int stage(void* buf, size_t bytes, bool copy_in, bool copy_out, void** dev) {
-    *dev = buf;
-    if (!host_ || !buf) return RBD_OK;
-    const int k = nslot_++;
-    if (k >= kSlots) return RBD_ERR_INVALID_ARGUMENT;  // (more buffers than slots: a call site that outgrew w->stage)
-    if (int st = ensure(&w_->stage[k], &w_->stage_bytes[k], bytes)) return st;
-    *dev = w_->stage[k];
-    if (copy_in && bytes) HIP_TRY(hipMemcpyAsync(*dev, buf, bytes, hipMemcpyHostToDevice, w_->stream));
-    if (copy_out) out_[nout_++] = Out{buf, *dev, bytes};
-    return RBD_OK;
-  }
-  rbd_ws* w_;
-  bool host_;
-  int nslot_ = 0, nout_ = 0;
-  Out out_[kSlots];
-};
-
-}  // namespace
+int upload_real(DevBuf& dst, const std::vector<double>& src, int dtype) {
+  if (dtype == RBD_F64) return upload(dst, src.data(), src.size() * sizeof(double));
+  const std::vector<float> f(src.begin(), src.end());
+  return upload(dst, f.data(), f.size() * sizeof(float));
+}
 
 // the two-bodies-per-lane kernels: every tree joint revolute, apart from 6-dof joints on the world -> their SIMPLE instantiation
 static int bank_simple(const rbd_model* m) {
@@ -1386,7 +1104,7 @@ static hipFunction_t spec_walk(rbd_ws* w, bool rerooted, int kind = 0, int pair 
   return w->spec_walk[k].f;
 }
 // scratch of the any-size kernels (rbd_big_kernels.hip)
-static int big_scratch(rbd_ws* w, int32_t B) { return ensure(&w->d_big_scratch, &w->d_big_scratch_bytes, esize(w) * big_scratch_elems(w->big, B)); }
+int big_scratch(rbd_ws* w, int32_t B) { return ensure(w->d_big_scratch, esize(w) * big_scratch_elems(w->big, B)); }
 // small loop mechanisms compiled for the mechanism (rbd_loop_small.hpp against constant tables): nullptr when unavailable
 static hipFunction_t spec_loop(rbd_ws* w) {
   auto source = [&] { std::vector<int32_t> xi; return loop_program_source(w->model, w->dtype, &xi); };
@@ -1418,52 +1136,52 @@ int dynamics_loops_t(rbd_ws* w, int32_t B, const Opts& o, const void* dq, const 
   const int nv = m->nv, nc = m->nc;
   const long stride = (long)nv * nv + 2L * nc * nv + 2L * nc * nc + 2L * nv + 2L * nc;
   int st;
-  if ((st = ensure(&w->d_M, &w->d_M_bytes, es * (size_t)nv * nv * B)) || (st = ensure(&w->d_c, &w->d_c_bytes, es * (size_t)nv * B)) ||
-      (st = ensure(&w->d_K, &w->d_K_bytes, es * (size_t)(nc * nv > 0 ? nc * nv : 1) * B)) || (st = ensure(&w->d_k, &w->d_k_bytes, es * (size_t)(nc > 0 ? nc : 1) * B)) ||
-      (st = ensure(&w->d_body, &w->d_body_bytes, es * (size_t)m->nb * 24 * B)) || (st = ensure(&w->d_scratch, &w->d_scratch_bytes, es * (size_t)stride * B)))
+  if ((st = ensure(w->d_M, es * (size_t)nv * nv * B)) || (st = ensure(w->d_c, es * (size_t)nv * B)) ||
+      (st = ensure(w->d_K, es * (size_t)(nc * nv > 0 ? nc * nv : 1) * B)) || (st = ensure(w->d_k, es * (size_t)(nc > 0 ? nc : 1) * B)) ||
+      (st = ensure(w->d_body, es * (size_t)m->nb * 24 * B)) || (st = ensure(w->d_scratch, es * (size_t)stride * B)))
     return st;
   w->result_layout = o.layout; w->result_B = B;
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, nv, B), Lf = layout_of(o.layout, 6L * m->nb, B);
   const Layout Lm = layout_of(o.layout, (long)nv * nv, B), Lc = layout_of(o.layout, nc, B), Lk = layout_of(o.layout, (long)nc * nv, B);
   LoopView<T> V;
   V.nloops = m->nloops; V.nc = nc; V.nv = nv; V.nb = m->nb;
-  V.li = (const int32_t*)w->d_loop_i; V.lr = (const T*)w->d_loop_r; V.path = (const int32_t*)w->d_loop_path;
-  V.jt = (const int32_t*)w->d_jt_ref; V.voff = (const int32_t*)w->d_voff_ref; V.axis = (const T*)w->d_axis_ref; V.axis2 = (const T*)w->d_axis2_ref;
-  V.xi = (const int32_t*)w->d_fused_i; V.rb = (const T*)w->d_rb;
+  V.li = (const int32_t*)w->d_loop_i.p; V.lr = (const T*)w->d_loop_r.p; V.path = (const int32_t*)w->d_loop_path.p;
+  V.jt = (const int32_t*)w->d_jt_ref.p; V.voff = (const int32_t*)w->d_voff_ref.p; V.axis = (const T*)w->d_axis_ref.p; V.axis2 = (const T*)w->d_axis2_ref.p;
+  V.xi = (const int32_t*)w->d_fused_i.p; V.rb = (const T*)w->d_rb.p;
   Timed t(w);
   const bool no_fused = w->loop_no_fused;  // tests: the three-launch route on a mechanism the fused kernel would take
   if (hipFunction_t f = (m->loop_fused_ok && !no_fused) ? spec_loop(w) : nullptr) {  // the whole evaluation as straight-line code for this mechanism
     long Bl = B;
     int stab = o.stabilization;
-    void* dM = w->d_M; void* dc = w->d_c; void* dK = w->d_K; void* dk = w->d_k; int* notpd = w->d_notpd;
+    void* dM = w->d_M.p; void* dc = w->d_c.p; void* dK = w->d_K.p; void* dk = w->d_k.p; int* notpd = (int*)w->d_notpd.p;
     Layout a_Lq = Lq, a_Lm = Lm, a_Lv = Lv, a_Lf = Lf, a_Lc = Lc, a_Lk = Lk;
-    const T* gains = w->custom_gains ? (const T*)w->d_loop_r + 24 : nullptr;  // (nullptr: the model's gains, constants of the compiled code)
+    const T* gains = w->custom_gains ? (const T*)w->d_loop_r.p + 24 : nullptr;  // (nullptr: the model's gains, constants of the compiled code)
     void* args[] = {&Bl, &stab, &dq, &dv, &dtau, &df, &dM, &dc, &dvd, &dqd, &dlam, &dK, &dk, &a_Lq, &a_Lm, &a_Lv, &a_Lf, &a_Lc, &a_Lk, &notpd, &gains};
     HIP_TRY(hipModuleLaunchKernel(f, (unsigned)((B + 63) / 64), 1, 1, 64, 1, 1, 0, w->stream, args, nullptr));
     w->last_kernel = "loop_spec (compiled for the mechanism at run time)";
     return RBD_OK;
   }
   if (m->loop_fused_ok && !no_fused &&
-      launch_loop_fused<T>(V, B, o.stabilization, dq, dv, dtau, df, w->d_body, w->d_M, w->d_c, dvd, dqd, dlam, w->d_K, w->d_k, Lq, Lm, Lv, Lf, Lc, Lk, m->gravity,
-                           w->d_notpd, w->stream)) {
+      launch_loop_fused<T>(V, B, o.stabilization, dq, dv, dtau, df, w->d_body.p, w->d_M.p, w->d_c.p, dvd, dqd, dlam, w->d_K.p, w->d_k.p, Lq, Lm, Lv, Lf, Lc, Lk, m->gravity,
+                           (int*)w->d_notpd.p, w->stream)) {
     HIP_TRY(hipGetLastError());
     w->last_kernel = "loop_fused_small_kernel";
     return RBD_OK;
   }
   if (m->big) {  // more than 64 bodies: bias forces + per-body kinematics and the mass matrix from the any-size kernels, then the same constrained solve
     if ((st = big_scratch(w, B))) return st;
-    HIP_TRY(launch_big_rnea<T>(w->big, B, dq, dv, nullptr, df, w->d_c, dqd, w->d_big_scratch, nullptr, nullptr, Lq, Lv, Lf, w->stream));
-    HIP_TRY(launch_big_export_body<T>(w->big, B, w->d_big_scratch, w->d_body, w->stream));
-    HIP_TRY(launch_big_crba<T>(w->big, B, dq, w->d_M, w->d_big_scratch, Lq, Lm, w->stream));
-    HIP_TRY(launch_loop_solve<T>(V, B, o.stabilization, w->d_body, w->d_M, w->d_c, dtau, dvd, dlam, w->d_K, w->d_k, w->d_scratch, stride, Lm, Lv, Lc, Lk,
-                                 m->gravity, w->d_notpd, w->stream));
+    HIP_TRY(launch_big_rnea<T>(w->big, B, dq, dv, nullptr, df, w->d_c.p, dqd, w->d_big_scratch.p, nullptr, nullptr, Lq, Lv, Lf, w->stream));
+    HIP_TRY(launch_big_export_body<T>(w->big, B, w->d_big_scratch.p, w->d_body.p, w->stream));
+    HIP_TRY(launch_big_crba<T>(w->big, B, dq, w->d_M.p, w->d_big_scratch.p, Lq, Lm, w->stream));
+    HIP_TRY(launch_loop_solve<T>(V, B, o.stabilization, w->d_body.p, w->d_M.p, w->d_c.p, dtau, dvd, dlam, w->d_K.p, w->d_k.p, w->d_scratch.p, stride, Lm, Lv, Lc, Lk,
+                                 m->gravity, (int*)w->d_notpd.p, w->stream));
     w->last_kernel = "big_rnea + big_crba + loop_solve kernel";
     return RBD_OK;
   }
-  HIP_TRY(launch_rnea<T>(w->dm, B, dq, dv, nullptr, df, w->d_c, dqd, w->d_body, Lq, Lv, Lf, w->stream));
-  HIP_TRY(launch_crba<T>(w->dm, B, dq, w->d_M, Lq, Lm, 1, w->stream));
-  HIP_TRY(launch_loop_solve<T>(V, B, o.stabilization, w->d_body, w->d_M, w->d_c, dtau, dvd, dlam, w->d_K, w->d_k, w->d_scratch, stride, Lm, Lv, Lc, Lk,
-                               m->gravity, w->d_notpd, w->stream));
+  HIP_TRY(launch_rnea<T>(w->dm, B, dq, dv, nullptr, df, w->d_c.p, dqd, w->d_body.p, Lq, Lv, Lf, w->stream));
+  HIP_TRY(launch_crba<T>(w->dm, B, dq, w->d_M.p, Lq, Lm, 1, w->stream));
+  HIP_TRY(launch_loop_solve<T>(V, B, o.stabilization, w->d_body.p, w->d_M.p, w->d_c.p, dtau, dvd, dlam, w->d_K.p, w->d_k.p, w->d_scratch.p, stride, Lm, Lv, Lc, Lk,
+                               m->gravity, (int*)w->d_notpd.p, w->stream));
   w->last_kernel = "rnea_kernel + crba_kernel + loop_solve kernel";
   return RBD_OK;
 }
@@ -1479,7 +1197,6 @@ static void spec_load(rbd_ws* w, int family, bool force = false);  // the kernel
 // call (up to 256): a program that hiprtc miscompiled (round 6 met one in an experiment: profiles/r06_experiments.txt §8) is dropped, loudly, and the call
 // recomputed.  first_use: whether this launch is that check — not when the checks are off (RBD_TUNE first_use_check=0), the kernel was checked, the stream is
 // capturing, or `wanted` is false (the outputs the check needs are missing, or the launch is a `simulate` stage or has one fused in); marks the kernel checked.
-static bool capturing(rbd_ws* w);
 static bool first_use(rbd_ws* w, SpecKernel& k, bool wanted) {
   if (!wanted || !w->spec_first_use_check || k.checked || capturing(w)) return false;
   k.checked = true;
@@ -1543,7 +1260,7 @@ static int run_rnea(rbd_ws* w, int32_t B, int mapping, const void* dq, const voi
   if (m->big) {
     int st = big_scratch(w, B);
     if (st) return st;
-    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_big_rnea<decltype(t)>(w->big, B, dq, dv, dvd, df, dtau, dqd, w->d_big_scratch, dacc, djw, Lq, Lv, Lf, w->stream); }));
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_big_rnea<decltype(t)>(w->big, B, dq, dv, dvd, df, dtau, dqd, w->d_big_scratch.p, dacc, djw, Lq, Lv, Lf, w->stream); }));
     return RBD_OK;
   }
   if (mapping == RBD_ALGO_ABA_BANKS && m->bank_lps == 0) return RBD_ERR_UNSUPPORTED;
@@ -1566,10 +1283,10 @@ static int run_rnea(rbd_ws* w, int32_t B, int mapping, const void* dq, const voi
       Layout Lo = Lf;
       void *oacc = dacc, *ojw = djw;
       if (staged) {
-        if (int st = ensure(&w->d_rows, &w->d_rows_bytes, 2 * each)) return st;
+        if (int st = ensure(w->d_rows, 2 * each)) return st;
         Lo = Layout{ld, 1};
-        if (dacc) oacc = w->d_rows;
-        if (djw) ojw = (char*)w->d_rows + each;
+        if (dacc) oacc = w->d_rows.p;
+        if (djw) ojw = (char*)w->d_rows.p + each;
       }
       void* args[] = {&Bl, &dq, &dv, &dvd, &df, &dtau, &Lq, &Lv, &Lf, &oacc, &ojw, &Lo};
       HIP_TRY(hipModuleLaunchKernel(w->spec_rnea.f, (unsigned)((B + 63) / 64), 1, 1, 64, 1, 1, 0, w->stream, args, nullptr));
@@ -1697,8 +1414,8 @@ static int run_aba(rbd_ws* w, int32_t B, int algorithm, const void* dq, const vo
       void* stash = nullptr;
       if (w->dtype == RBD_F64) {  // the HBM stash of aba_spec_gst_f64 (rbd_spec.hpp aba_spec GST): (nb + 10 n3) values per state, batch-innermost; grown on demand like every workspace buffer
         if (stash_program) {
-          if (int st = ensure(&w->d_rows, &w->d_rows_bytes, sizeof(double) * (size_t)(m->nb + 10 * m->spec_plan().n3) * (size_t)B)) return st;
-          stash = w->d_rows;
+          if (int st = ensure(w->d_rows, sizeof(double) * (size_t)(m->nb + 10 * m->spec_plan().n3) * (size_t)B)) return st;
+          stash = w->d_rows.p;
         }
       }
       void* args64[] = {&Bl, &dq, &dv, &dtau, &df, &dvd, &dqd, &Lq, &Lv, &Lf, &gxd, &gyd, &gzd, &F, &stash};
@@ -1857,7 +1574,7 @@ static hipError_t launch_crba_spec(rbd_ws* w, hipFunction_t f, long B, const voi
 
 // the sparsity-specialised tile Cholesky on the permuted staging buffer (and, before it, the caller's M from the same buffer)
 static hipError_t launch_chol_spec(rbd_ws* w, long B, const void* Mg, const void* tau, const void* c, void* x, Layout Lv, void* Mcopy, Layout Lc, bool packed = false) {
-  int* notpd = w->d_notpd;
+  int* notpd = (int*)w->d_notpd.p;
   void* args[] = {&B, &Mg, &tau, &c, &x, &Lv, &notpd, &Mcopy, &Lc};
   return hipModuleLaunchKernel(!Mcopy ? w->spec_chol_nom.f : packed ? w->spec_chol_packed.f : w->spec_chol.f, (unsigned)((B + 15) / 16), 1, 1, 64, 1, 1, 0, w->stream, args, nullptr);
 }
@@ -1867,12 +1584,12 @@ static hipError_t launch_chol_spec(rbd_ws* w, long B, const void* Mg, const void
 // only store the non-zeros.
 static int stage_m(rbd_ws* w, int32_t B, bool permuted) {
   const rbd_model* m = w->model;
-  void* const before = w->d_Msoa;
+  void* const before = w->d_Msoa.p;
   const size_t bytes = esize(w) * (size_t)m->nv * m->nv * (((size_t)B + 15) & ~(size_t)15);
   int st;
-  if ((st = ensure(&w->d_Msoa, &w->d_Msoa_bytes, bytes))) return st;
-  if (w->Msoa_B != B || w->d_Msoa != before || w->Msoa_perm != (int)permuted) {
-    HIP_TRY(hipMemsetAsync(w->d_Msoa, 0, bytes, w->stream));
+  if ((st = ensure(w->d_Msoa, bytes))) return st;
+  if (w->Msoa_B != B || w->d_Msoa.p != before || w->Msoa_perm != (int)permuted) {
+    HIP_TRY(hipMemsetAsync(w->d_Msoa.p, 0, bytes, w->stream));
     w->Msoa_B = B;
     w->Msoa_perm = (int)permuted;
   }
@@ -1884,7 +1601,7 @@ static int run_crba(rbd_ws* w, int32_t B, int layout, const void* dq, void* dM, 
   if (w->model->big) {
     int st = big_scratch(w, B);
     if (st) return st;
-    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_big_crba<decltype(t)>(w->big, B, dq, dM, w->d_big_scratch, Lq, Lm, w->stream); }));
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_big_crba<decltype(t)>(w->big, B, dq, dM, w->d_big_scratch.p, Lq, Lm, w->stream); }));
     return RBD_OK;
   }
   if (B >= w->mass_min_batch && layout == RBD_LAYOUT_AOS && Lm.sk == 1 && ((Lm.sb * (long)esize(w)) & 15) == 0 && (reinterpret_cast<uintptr_t>(dM) & 15) == 0 &&
@@ -1896,9 +1613,9 @@ static int run_crba(rbd_ws* w, int32_t B, int layout, const void* dq, void* dM, 
     int st = stage_m(w, B, perm);
     if (st) return st;
     const Layout Ls{16, -(long)w->model->nv * w->model->nv};
-    HIP_TRY(launch_crba_spec(w, perm ? w->spec_crba_perm : w->spec_crba, B, dq, w->d_Msoa, Lq, Ls, 0));
+    HIP_TRY(launch_crba_spec(w, perm ? w->spec_crba_perm : w->spec_crba, B, dq, w->d_Msoa.p, Lq, Ls, 0));
     long Bl = B;
-    void* args[] = {&Bl, &w->d_Msoa, &dM, &Lm};
+    void* args[] = {&Bl, &w->d_Msoa.p, &dM, &Lm};
     HIP_TRY(hipModuleLaunchKernel(w->spec_emit, (unsigned)((B + 15) / 16), 1, 1, 64, 1, 1, 0, w->stream, args, nullptr));
     w->last_kernel = perm ? "crba_spec_perm_f32 + emit_spec_f32 (compiled for the mechanism at run time)" : "crba_spec_f64 + emit_spec_f64 (compiled for the mechanism at run time)";
     return RBD_OK;
@@ -1923,7 +1640,7 @@ static int check_solve(rbd_ws* w, long B, const void* dq, const void* dtau, cons
   const FirstUseCheck c{"first_use_check_solve", "crba_kernel + the dense Cholesky kernel", "solution component", "programs are", 1e-30, 2e-2};
   return first_use_check(w, c, B, dx, Lv, esize(w) * (size_t)nv * nv * std::min<long>(B, 256), [&](long n, void* xt, void* Mt) {
     const hipError_t e = launch_crba<float>(w->dm, n, dq, Mt, Lq, Lm, 1, w->stream);
-    return e != hipSuccess ? e : launch_chol_solve<float>(nv, n, Mt, dtau, dc, xt, nullptr, Lm, Lv, w->d_notpd, w->stream);
+    return e != hipSuccess ? e : launch_chol_solve<float>(nv, n, Mt, dtau, dc, xt, nullptr, Lm, Lv, (int*)w->d_notpd.p, w->stream);
   }, same);
 }
 
@@ -1937,8 +1654,8 @@ static int run_crba_chol(rbd_ws* w, int32_t B, int layout, const void* dq, void*
   int st;
   if (m->big) {  // any-size fallback: M into dM (never null here), then one thread per state factors a COPY (the reference's result.L, :763-764) and solves
     if ((st = run_crba(w, B, layout, dq, dM, Lq, Lm))) return st;
-    if ((st = ensure(&w->d_big_L, &w->d_big_L_bytes, es * (size_t)m->nv * m->nv * B))) return st;
-    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_big_chol_solve<decltype(t)>(m->nv, B, dM, w->d_big_L, dtau, dc, dx, Lm, Lv, w->d_notpd, w->stream); }));
+    if ((st = ensure(w->d_big_L, es * (size_t)m->nv * m->nv * B))) return st;
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_big_chol_solve<decltype(t)>(m->nv, B, dM, w->d_big_L.p, dtau, dc, dx, Lm, Lv, (int*)w->d_notpd.p, w->stream); }));
     return RBD_OK;
   }
   const bool state = B >= w->mass_solve_min_batch;  // (below state_min_batch: only with both kernels compiled for the mechanism — spec_route)
@@ -1956,10 +1673,10 @@ static int run_crba_chol(rbd_ws* w, int32_t B, int layout, const void* dq, void*
     if (spec_route) {
       // both kernels compiled for the mechanism: M in the factorisation's own order (children before parents: no fill-in), only the tiles
       // that hold non-zeros are factored; the same launch writes the caller's M
-      HIP_TRY(launch_crba_spec(w, w->spec_crba_perm, B, dq, w->d_Msoa, Lq, Ls, 0));
+      HIP_TRY(launch_crba_spec(w, w->spec_crba_perm, B, dq, w->d_Msoa.p, Lq, Ls, 0));
       // (the emission of M as a launch of its own on a second stream beside the factorisation — emit_spec beside chol_spec without M — was measured: 145 us
       //  against 120 for the pair in one launch; what pays is the staggered order inside chol_spec, rbd_spec.hpp)
-      HIP_TRY(launch_chol_spec(w, B, w->d_Msoa, dtau, dc, dx, Lv, dM, Lm));
+      HIP_TRY(launch_chol_spec(w, B, w->d_Msoa.p, dtau, dc, dx, Lv, dM, Lm));
       w->last_kernel = "crba_spec_perm_f32 + chol_spec_f32 (compiled for the mechanism at run time)";
       bool same = true;
       if (first_use(w, dM ? w->spec_chol : w->spec_chol_nom, dx) && (st = check_solve(w, B, dq, dtau, dc, dx, Lq, Lm, Lv, &same))) return st;
@@ -1967,19 +1684,19 @@ static int run_crba_chol(rbd_ws* w, int32_t B, int layout, const void* dq, void*
       w->spec_chol.f = w->spec_chol_nom.f = w->spec_chol_packed.f = nullptr;  // (the pair's second kernel in its three forms: every route that needs one falls back)
       goto lanes;
     }
-    if (spec) HIP_TRY(launch_crba_spec(w, spec, B, dq, w->d_Msoa, Lq, Ls, 0));
-    else HIP_TRY(launch_crba_state<float>(w->sm, B, dq, w->d_Msoa, Lq, Ls, 0, w->stream));
-    HIP_TRY(launch_chol_solve<float>(m->nv, B, w->d_Msoa, dtau, dc, dx, nullptr, Ls, Lv, w->d_notpd, w->stream, dM, Lm));
+    if (spec) HIP_TRY(launch_crba_spec(w, spec, B, dq, w->d_Msoa.p, Lq, Ls, 0));
+    else HIP_TRY(launch_crba_state<float>(w->sm, B, dq, w->d_Msoa.p, Lq, Ls, 0, w->stream));
+    HIP_TRY(launch_chol_solve<float>(m->nv, B, w->d_Msoa.p, dtau, dc, dx, nullptr, Ls, Lv, (int*)w->d_notpd.p, w->stream, dM, Lm));
     w->last_kernel = spec ? "crba_spec_f32 (compiled for the mechanism at run time) + chol_mfma_kernel" : "crba_state_kernel + chol_mfma_kernel";
     return RBD_OK;
   }
 lanes:
   if (!dM) {  // (the caller left M out counting on the staged route)
-    if ((st = ensure(&w->d_M, &w->d_M_bytes, es * (size_t)m->nv * m->nv * B))) return st;
-    dM = w->d_M;
+    if ((st = ensure(w->d_M, es * (size_t)m->nv * m->nv * B))) return st;
+    dM = w->d_M.p;
   }
   if ((st = run_crba(w, B, layout, dq, dM, Lq, Lm))) return st;
-  HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_chol_solve<decltype(t)>(m->nv, B, dM, dtau, dc, dx, nullptr, Lm, Lv, w->d_notpd, w->stream); }));
+  HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_chol_solve<decltype(t)>(m->nv, B, dM, dtau, dc, dx, nullptr, Lm, Lv, (int*)w->d_notpd.p, w->stream); }));
   w->last_kernel = strstr(w->last_kernel, "crba_spec") ? "crba_spec (compiled for the mechanism at run time) + chol kernel"
                    : strstr(w->last_kernel, "crba_state") ? "crba_state_kernel + chol kernel" : "crba_kernel + chol kernel";
   return RBD_OK;
@@ -2003,10 +1720,10 @@ static int run_dynamics(rbd_ws* w, int32_t B, const Opts& o, const void* dq, con
     // (bound buffers are laid out like the DEVICE buffers of the call: a host-memory call — its q, v are staged copies — keeps the workspace's)
     void* const bM = o.memory == RBD_MEM_HOST ? nullptr : w->bound_M;
     void* const bc = o.memory == RBD_MEM_HOST ? nullptr : w->bound_c;
-    if (!bM && (st = ensure(&w->d_M, &w->d_M_bytes, es * (size_t)m->nv * m->nv * B))) return st;
-    if (!bc && (st = ensure(&w->d_c, &w->d_c_bytes, es * (size_t)m->nv * B))) return st;
-    void* const Md = bM ? bM : w->d_M;
-    void* const cd = bc ? bc : w->d_c;
+    if (!bM && (st = ensure(w->d_M, es * (size_t)m->nv * m->nv * B))) return st;
+    if (!bc && (st = ensure(w->d_c, es * (size_t)m->nv * B))) return st;
+    void* const Md = bM ? bM : w->d_M.p;
+    void* const cd = bc ? bc : w->d_c.p;
     w->result_layout = o.layout; w->result_B = B;
     Timed t(w);
     if ((st = run_rnea(w, B, RBD_ALGO_ABA, dq, dv, nullptr, df, cd, dqd, Lq, Lv, Lf))) return st;
@@ -2131,8 +1848,8 @@ int rbd_mass_matrix_solve(rbd_ws_t* w, int32_t B, const void* q, const void* rhs
   const bool crba_route = o.algorithm == RBD_ALGO_CRBA_CHOLESKY || m->big;
   const bool state_route = !m->big && B >= w->mass_solve_min_batch && o.layout == RBD_LAYOUT_AOS && chol_copies_m((int)es, m->nv);
   if (!dM && crba_route && !state_route) {
-    if ((st = ensure(&w->d_M, &w->d_M_bytes, mbytes))) return st;
-    dM = w->d_M;
+    if ((st = ensure(w->d_M, mbytes))) return st;
+    dM = w->d_M.p;
   }
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B), Lm = layout_of(o.layout, (long)m->nv * m->nv, B);
   if (crba_route) {
@@ -2179,8 +1896,8 @@ int rbd_mass_matrix_solve_packed(rbd_ws_t* w, int32_t B, const void* q, const vo
     if (fast) {
       if ((st = stage_m(w, B, true))) return st;
       const Layout Ls{16, -(long)m->nv * m->nv};
-      HIP_TRY(launch_crba_spec(w, w->spec_crba_perm, B, dq, w->d_Msoa, Lq, Ls, 0));
-      HIP_TRY(launch_chol_spec(w, B, w->d_Msoa, dr, nullptr, dx, Lv, dP, Lp, true));
+      HIP_TRY(launch_crba_spec(w, w->spec_crba_perm, B, dq, w->d_Msoa.p, Lq, Ls, 0));
+      HIP_TRY(launch_chol_spec(w, B, w->d_Msoa.p, dr, nullptr, dx, Lv, dP, Lp, true));
       w->last_kernel = "crba_spec_perm_f32 + chol_spec_packed_f32 (compiled for the mechanism at run time)";
       bool same = true;
       if (first_use(w, w->spec_chol_packed, dx) && (st = check_solve(w, B, dq, dr, nullptr, dx, Lq, Lm, Lv, &same))) return st;
@@ -2190,9 +1907,9 @@ int rbd_mass_matrix_solve_packed(rbd_ws_t* w, int32_t B, const void* q, const vo
       }
     }
     if (!fast || fast_failed) {
-      if ((st = ensure(&w->d_M, &w->d_M_bytes, es * (size_t)m->nv * m->nv * B))) return st;
-      if ((st = run_crba_chol(w, B, o.layout, dq, w->d_M, dr, nullptr, dx, Lq, Lm, Lv))) return st;
-      HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_pack_lower<decltype(t)>(m->nv, B, w->d_M, dP, Lm, Lp, w->stream); }));
+      if ((st = ensure(w->d_M, es * (size_t)m->nv * m->nv * B))) return st;
+      if ((st = run_crba_chol(w, B, o.layout, dq, w->d_M.p, dr, nullptr, dx, Lq, Lm, Lv))) return st;
+      HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_pack_lower<decltype(t)>(m->nv, B, w->d_M.p, dP, Lm, Lp, w->stream); }));
     }
   }
   return io.finish();
@@ -2208,10 +1925,10 @@ int rbd_dynamics_result(rbd_ws_t* w, int32_t B, void* M, void* c, void* K, void*
   const hipMemcpyKind kind = (o.memory == RBD_MEM_HOST) ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
   // (a buffer bound with rbd_workspace_bind_result already holds its field: the tree-mechanism route wrote it in place)
   const bool tree = m->nloops == 0;
-  if (M && !(tree && M == w->bound_M)) { if (!w->d_M) return RBD_ERR_INVALID_ARGUMENT; HIP_TRY(hipMemcpyAsync(M, w->d_M, es * (size_t)m->nv * m->nv * B, kind, w->stream)); }
-  if (c && !(tree && c == w->bound_c)) { if (!w->d_c) return RBD_ERR_INVALID_ARGUMENT; HIP_TRY(hipMemcpyAsync(c, w->d_c, es * (size_t)m->nv * B, kind, w->stream)); }
-  if (K && m->nc > 0) { if (!w->d_K) return RBD_ERR_INVALID_ARGUMENT; HIP_TRY(hipMemcpyAsync(K, w->d_K, es * (size_t)m->nc * m->nv * B, kind, w->stream)); }
-  if (k && m->nc > 0) { if (!w->d_k) return RBD_ERR_INVALID_ARGUMENT; HIP_TRY(hipMemcpyAsync(k, w->d_k, es * (size_t)m->nc * B, kind, w->stream)); }
+  if (M && !(tree && M == w->bound_M)) { if (!w->d_M.p) return RBD_ERR_INVALID_ARGUMENT; HIP_TRY(hipMemcpyAsync(M, w->d_M.p, es * (size_t)m->nv * m->nv * B, kind, w->stream)); }
+  if (c && !(tree && c == w->bound_c)) { if (!w->d_c.p) return RBD_ERR_INVALID_ARGUMENT; HIP_TRY(hipMemcpyAsync(c, w->d_c.p, es * (size_t)m->nv * B, kind, w->stream)); }
+  if (K && m->nc > 0) { if (!w->d_K.p) return RBD_ERR_INVALID_ARGUMENT; HIP_TRY(hipMemcpyAsync(K, w->d_K.p, es * (size_t)m->nc * m->nv * B, kind, w->stream)); }
+  if (k && m->nc > 0) { if (!w->d_k.p) return RBD_ERR_INVALID_ARGUMENT; HIP_TRY(hipMemcpyAsync(k, w->d_k.p, es * (size_t)m->nc * B, kind, w->stream)); }
   return RBD_OK;
 }
 
@@ -2220,15 +1937,15 @@ static int mk_ensure(rbd_ws* w, int32_t B) {
   const rbd_model* m = w->model;
   const size_t es = esize(w);
   if (w->mk_elems >= (size_t)B) return RBD_OK;
-  void** ptrs[] = {&w->mk.q0, &w->mk.v0, &w->mk.phid[0], &w->mk.phid[1], &w->mk.phid[2], &w->mk.phid[3], &w->mk.vd[0], &w->mk.vd[1], &w->mk.vd[2],
-                   &w->mk.vd[3], &w->d_vdwork};
-  for (void** p : ptrs) { if (*p) HIP_TRY(hipFree(*p)); *p = nullptr; }
   w->mk_elems = 0;
   const size_t nq = (size_t)(m->nq > 0 ? m->nq : 1), nv = (size_t)(m->nv > 0 ? m->nv : 1);
-  HIP_TRY(hipMalloc(&w->mk.q0, es * nq * B));
-  HIP_TRY(hipMalloc(&w->mk.v0, es * nv * B));
-  for (int k = 0; k < 4; ++k) { HIP_TRY(hipMalloc(&w->mk.phid[k], es * nv * B)); HIP_TRY(hipMalloc(&w->mk.vd[k], es * nv * B)); }
-  HIP_TRY(hipMalloc(&w->d_vdwork, es * nv * B));
+  int st;
+  if ((st = ensure(w->d_mk_q0, es * nq * B)) || (st = ensure(w->d_mk_v0, es * nv * B))) return st;
+  for (int k = 0; k < 4; ++k)
+    if ((st = ensure(w->d_mk_phid[k], es * nv * B)) || (st = ensure(w->d_mk_vd[k], es * nv * B))) return st;
+  if ((st = ensure(w->d_vdwork, es * nv * B))) return st;
+  const DevBuf *ph = w->d_mk_phid, *vd = w->d_mk_vd;
+  w->mk = MkBuffers{w->d_mk_q0.p, w->d_mk_v0.p, {ph[0].p, ph[1].p, ph[2].p, ph[3].p}, {vd[0].p, vd[1].p, vd[2].p, vd[3].p}};
   w->mk_elems = (size_t)B;
   return RBD_OK;
 }
@@ -2368,24 +2085,24 @@ static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_con
     }
     if (step == nsteps - 1) HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_mk_stage<decltype(t)>(w->dm, B, 4, dt, dq, dv, nullptr, w->mk, Lq, Lv, w->stream); }));
   }
-  if (!fused && pd && (st = ensure(&w->d_tauwork, &w->d_tauwork_bytes, entry))) return st;
+  if (!fused && pd && (st = ensure(w->d_tauwork, entry))) return st;
   for (int step = 0; !fused && step < nsteps; ++step) {
     // the closing stage of a step rides in the stage-0 launch of the next one (as in the fused kernels); only the last step closes on its own
     for (int stage = 0; stage < 4; ++stage) {
       const int close_prev = (stage == 0 && step > 0) ? 1 : 0;
-      HIP_TRY(stage_launch(w, B, stage, dt, dq, dv, w->d_vdwork, Lq, Lv, close_prev));
+      HIP_TRY(stage_launch(w, B, stage, dt, dq, dv, w->d_vdwork.p, Lq, Lv, close_prev));
       const void* ts = tau_at(step, stage);
       if (pd) {  // the PD law on the stage state the launch above left in (q, v): one element-wise launch, no host round trip
         HIP_TRY(by_dtype(w->dtype, [&](auto t) {
           using T = decltype(t);
-          if (m->big) return launch_big_pd_control<T>(w->big, B, dq, dv, ts, ctl.q_des, ctl.kp, ctl.kd, w->d_tauwork, Lq, Lv, w->stream);  // (trees of more than 64 bodies: the same law over the any-size tables, round 6)
-          return launch_pd_control<T>(w->dm, B, dq, dv, ts, ctl.q_des, ctl.kp, ctl.kd, w->d_tauwork, Lq, Lv, w->stream);
+          if (m->big) return launch_big_pd_control<T>(w->big, B, dq, dv, ts, ctl.q_des, ctl.kp, ctl.kd, w->d_tauwork.p, Lq, Lv, w->stream);  // (trees of more than 64 bodies: the same law over the any-size tables, round 6)
+          return launch_pd_control<T>(w->dm, B, dq, dv, ts, ctl.q_des, ctl.kp, ctl.kd, w->d_tauwork.p, Lq, Lv, w->stream);
         }));
-        ts = w->d_tauwork;
+        ts = w->d_tauwork.p;
       }
-      if ((st = run_dynamics(w, B, od, dq, dv, ts, df, w->d_vdwork, nullptr, nullptr))) return st;
+      if ((st = run_dynamics(w, B, od, dq, dv, ts, df, w->d_vdwork.p, nullptr, nullptr))) return st;
     }
-    if (step == nsteps - 1) HIP_TRY(stage_launch(w, B, 4, dt, dq, dv, w->d_vdwork, Lq, Lv));
+    if (step == nsteps - 1) HIP_TRY(stage_launch(w, B, 4, dt, dq, dv, w->d_vdwork.p, Lq, Lv));
   }
   return io.finish();
 }
@@ -2412,33 +2129,33 @@ int rbd_model_contact_dims(const rbd_model_t* m, int32_t* n_contact_points, int3
 }
 
 // the per-body kinematics [state][body][24] of (q, v) into w->d_body (the RNEA launch exports them; its bias torques go to the workspace)
-static int run_contact_kinematics(rbd_ws* w, int32_t B, const Opts& o, const void* dq, const void* dv) {
+int run_contact_kinematics(rbd_ws* w, int32_t B, const Opts& o, const void* dq, const void* dv) {
   const rbd_model* m = w->model;
   const size_t es = esize(w);
   int st;
-  if ((st = ensure(&w->d_body, &w->d_body_bytes, es * (size_t)m->nb * 24 * B)) || (st = ensure(&w->d_c, &w->d_c_bytes, es * (size_t)m->nv * B))) return st;
+  if ((st = ensure(w->d_body, es * (size_t)m->nb * 24 * B)) || (st = ensure(w->d_c, es * (size_t)m->nv * B))) return st;
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B), Lf = layout_of(o.layout, 6L * m->nb, B);
   if (m->big && (st = big_scratch(w, B))) return st;
   return by_dtype(w->dtype, [&](auto t) -> int {
     using T = decltype(t);
     if (m->big) {  // more than 64 bodies: the per-body kinematics from the any-size kernels
-      HIP_TRY(launch_big_rnea<T>(w->big, B, dq, dv, nullptr, nullptr, w->d_c, nullptr, w->d_big_scratch, nullptr, nullptr, Lq, Lv, Lf, w->stream));
-      HIP_TRY(launch_big_export_body<T>(w->big, B, w->d_big_scratch, w->d_body, w->stream));
+      HIP_TRY(launch_big_rnea<T>(w->big, B, dq, dv, nullptr, nullptr, w->d_c.p, nullptr, w->d_big_scratch.p, nullptr, nullptr, Lq, Lv, Lf, w->stream));
+      HIP_TRY(launch_big_export_body<T>(w->big, B, w->d_big_scratch.p, w->d_body.p, w->stream));
     } else {
-      HIP_TRY(launch_rnea<T>(w->dm, B, dq, dv, nullptr, nullptr, w->d_c, nullptr, w->d_body, Lq, Lv, Lf, w->stream));
+      HIP_TRY(launch_rnea<T>(w->dm, B, dq, dv, nullptr, nullptr, w->d_c.p, nullptr, w->d_body.p, Lq, Lv, Lf, w->stream));
     }
     return RBD_OK;
   });
 }
 
 // contact_dynamics! on device pointers: per-body kinematics, then the contact kernel.  dcw / dtw nullable.
-static int run_contact(rbd_ws* w, int32_t B, const Opts& o, const void* dq, const void* dv, void* ds, void* dsd, const void* df, void* dcw, void* dtw) {
+int run_contact(rbd_ws* w, int32_t B, const Opts& o, const void* dq, const void* dv, void* ds, void* dsd, const void* df, void* dcw, void* dtw) {
   const rbd_model* m = w->model;
   if (int st = run_contact_kinematics(w, B, o, dq, dv)) return st;
   const Layout Lf = layout_of(o.layout, 6L * m->nb, B), Ls = layout_of(o.layout, 3L * m->ncp * m->nhs, B);
   return by_dtype(w->dtype, [&](auto t) -> int {
     using T = decltype(t);
-    HIP_TRY(launch_contact<T>(w->ctm, B, w->d_body, ds, dsd, df, dcw, dtw, Ls, Lf, w->stream));
+    HIP_TRY(launch_contact<T>(w->ctm, B, w->d_body.p, ds, dsd, df, dcw, dtw, Ls, Lf, w->stream));
     return RBD_OK;
   });
 }
@@ -2473,8 +2190,8 @@ int rbd_dynamics_contact(rbd_ws_t* w, int32_t B, const void* q, const void* v, v
   const rbd_model* m = w->model;
   void* dtw = totalwrenches;
   if (!dtw) {
-    if ((st = ensure(&w->d_tw, &w->d_tw_bytes, esize(w) * (size_t)6 * m->nb * B))) return st;
-    dtw = w->d_tw;
+    if ((st = ensure(w->d_tw, esize(w) * (size_t)6 * m->nb * B))) return st;
+    dtw = w->d_tw.p;
   }
   if ((st = run_contact(w, B, o, q, v, s, sdot, fext, contactwrenches, dtw))) return st;
   return run_dynamics(w, B, o, q, v, tau, dtw, vdot, qdot, nullptr);
@@ -2492,8 +2209,8 @@ int rbd_simulate_contact(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, cons
   const rbd_model* m = w->model;
   const size_t es = esize(w);
   const long ns = 3L * m->ncp * m->nhs * B;
-  if ((st = mk_ensure(w, B)) || (st = ensure(&w->d_tw, &w->d_tw_bytes, es * (size_t)6 * m->nb * B)) || (st = ensure(&w->d_s0, &w->d_s0_bytes, es * (size_t)ns)) ||
-      (st = ensure(&w->d_sacc, &w->d_sacc_bytes, es * (size_t)ns)) || (st = ensure(&w->d_sdot, &w->d_sdot_bytes, es * (size_t)ns)))
+  if ((st = mk_ensure(w, B)) || (st = ensure(w->d_tw, es * (size_t)6 * m->nb * B)) || (st = ensure(w->d_s0, es * (size_t)ns)) ||
+      (st = ensure(w->d_sacc, es * (size_t)ns)) || (st = ensure(w->d_sdot, es * (size_t)ns)))
     return st;
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B);
   for (int step = 0; step < nsteps; ++step) {
@@ -2501,14 +2218,14 @@ int rbd_simulate_contact(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, cons
     for (int stage = 0; stage <= 4; ++stage) {
       if ((st = by_dtype(w->dtype, [&](auto t) -> int {
              using T = decltype(t);
-             HIP_TRY(launch_mk_stage<T>(w->dm, B, stage, dt, q, v, w->d_vdwork, w->mk, Lq, Lv, w->stream));
-             HIP_TRY(launch_contact_stage<T>(ns, stage, dt, s, w->d_sdot, w->d_s0, w->d_sacc, w->stream));
+             HIP_TRY(launch_mk_stage<T>(w->dm, B, stage, dt, q, v, w->d_vdwork.p, w->mk, Lq, Lv, w->stream));
+             HIP_TRY(launch_contact_stage<T>(ns, stage, dt, s, w->d_sdot.p, w->d_s0.p, w->d_sacc.p, w->stream));
              return RBD_OK;
            })))
         return st;
       if (stage < 4) {
-        if ((st = run_contact(w, B, o, q, v, s, w->d_sdot, fext, nullptr, w->d_tw))) return st;
-        if ((st = run_dynamics(w, B, o, q, v, tau, w->d_tw, w->d_vdwork, nullptr, nullptr))) return st;
+        if ((st = run_contact(w, B, o, q, v, s, w->d_sdot.p, fext, nullptr, w->d_tw.p))) return st;
+        if ((st = run_dynamics(w, B, o, q, v, tau, w->d_tw.p, w->d_vdwork.p, nullptr, nullptr))) return st;
       }
     }
   }
@@ -2524,7 +2241,7 @@ int rbd_cholesky_solve(rbd_ws_t* w, int32_t B, const void* M, const void* rhs, v
   const rbd_model* m = w->model;
   const Layout Lv = layout_of(o.layout, m->nv, B), Lm = layout_of(o.layout, (long)m->nv * m->nv, B);
   Timed t(w);
-  HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_chol_solve<decltype(t)>(m->nv, B, M, rhs, nullptr, x, L_out, Lm, Lv, w->d_notpd, w->stream); }));
+  HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_chol_solve<decltype(t)>(m->nv, B, M, rhs, nullptr, x, L_out, Lm, Lv, (int*)w->d_notpd.p, w->stream); }));
   return RBD_OK;
 }
 
@@ -2563,7 +2280,7 @@ int rbd_kinematics(rbd_ws_t* w, int32_t B, const void* q, const void* v, void* m
     Timed t(w);
     w->last_kernel = "big_kin_kernel";
     HIP_TRY(by_dtype(w->dtype, [&](auto t) {
-      return launch_big_kin<decltype(t)>(w->big, B, dq, dv, dA, dcom, den, nullptr, -1, -1, nullptr, w->d_big_scratch, Lq, Lv, La, L3, L2, L2, w->stream);
+      return launch_big_kin<decltype(t)>(w->big, B, dq, dv, dA, dcom, den, nullptr, -1, -1, nullptr, w->d_big_scratch.p, Lq, Lv, La, L3, L2, L2, w->stream);
     }));
   } else {
     Timed t(w);
@@ -2609,7 +2326,7 @@ int rbd_geometric_jacobian(rbd_ws_t* w, int32_t B, const void* q, int32_t base_b
     Timed t(w);
     w->last_kernel = "big_kin_kernel";
     HIP_TRY(by_dtype(w->dtype, [&](auto t) {
-      return launch_big_kin<decltype(t)>(w->big, B, dq, nullptr, nullptr, nullptr, nullptr, dJ, base_body, target_body, nullptr, w->d_big_scratch, Lq, Lv, La, L3, L2, L2, w->stream);
+      return launch_big_kin<decltype(t)>(w->big, B, dq, nullptr, nullptr, nullptr, nullptr, dJ, base_body, target_body, nullptr, w->d_big_scratch.p, Lq, Lv, La, L3, L2, L2, w->stream);
     }));
   } else {
     Timed t(w);
@@ -2645,1024 +2362,13 @@ int rbd_momentum(rbd_ws_t* w, int32_t B, const void* q, const void* v, void* out
     Timed t(w);
     w->last_kernel = "big_kin_kernel";
     HIP_TRY(by_dtype(w->dtype, [&](auto t) {
-      return launch_big_kin<decltype(t)>(w->big, B, dq, dv, nullptr, nullptr, nullptr, nullptr, -1, -1, dout, w->d_big_scratch, Lq, Lv, Lq, Lq, Lq, L12, w->stream);
+      return launch_big_kin<decltype(t)>(w->big, B, dq, dv, nullptr, nullptr, nullptr, nullptr, -1, -1, dout, w->d_big_scratch.p, Lq, Lv, Lq, Lq, Lq, L12, w->stream);
     }));
   } else {
     Timed t(w);
     HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_momentum<decltype(t)>(w->dm, B, dq, dv, dout, Lq, Lv, L12, w->stream); }));
   }
   return io.finish();
-}
-
-}  // extern "C"
-
-// ---- forward-mode derivatives of inverse_dynamics! and dynamics! (header 700; kernels: rbd_tangent_kernels.hip) --------------------------------------------
-namespace rbd {
-size_t tangent_scratch_elems_per_thread(const BigModel& M, int es);
-int tangent_chunk(int es);
-template <typename T> hipError_t launch_tangent_rnea(const BigModel& M, const TanArgs<T>& A, void* scratch, long max_threads, hipStream_t s);
-template <typename T>
-hipError_t launch_tangent_solve(int nv, long B, int c0, int ncol, const void* L, Layout Ll, const void* rhs, int identity, const ColOut<T>& out, void* xmem, hipStream_t s);
-template <typename T> hipError_t launch_symmetrize(int nv, long B, void* M, Layout Lm, hipStream_t s);
-template <typename T> hipError_t launch_tangent_mk_stage(const MkTanArgs<T>& A, hipStream_t s);
-size_t adjoint_scratch_elems_per_state(const BigModel& M);
-template <typename T> hipError_t launch_adjoint_rnea(const BigModel& M, const AdjArgs<T>& A, void* scratch, long max_states, hipStream_t s);
-template <typename T> hipError_t launch_stage_rows(int n, long B, const void* x, Layout L, void* out, hipStream_t s);
-template <typename T> hipError_t launch_point_kin(const BigModel& M, const PointPlan& P, const PointArgs<T>& A, hipStream_t s);  // rbd_point_kernels.hip
-template <typename T>
-hipError_t launch_point_adjoint(const BigModel& M, const PointPlan& P, const AdjArgs<T>& A, const PointAdjArgs<T>& C, void* scratch, long max_states, hipStream_t s);
-template <typename T> hipError_t launch_mk_stage_classes(MkAdjArgs<T> A, const int32_t* jn, int nn, const int32_t* jw, int nw, int adjoint, hipStream_t s);
-template <typename T>
-hipError_t launch_tangent_mk_load(long B, int ncol, int nq, int nv, int col0, int unit, const ColOut<T>& sq, const ColOut<T>& sv, const ColOut<T>& sd,
-                                  const ColOut<T>& dq, const ColOut<T>& dv, const ColOut<T>& dd, hipStream_t s);
-}  // namespace rbd
-
-namespace {
-enum : long { TAN_SCRATCH_CAP = 1L << 30 };  // bytes of tangent scratch at most: larger calls run in slabs of (state, chunk) threads
-
-// the tree in the reference's order (BigModel tables) for every mechanism: built by the first derivative call or by rbd_workspace_set_points
-int tan_tables(rbd_ws* w) {
-  const rbd_model* m = w->model;
-  int st;
-  if (w->tan_tbl_ready) return RBD_OK;
-  if (m->big) {
-    w->tan = w->big;
-  } else {  // the slot-ordered tables back in the reference's order (parents first: rbd_model_create checks it)
-    const int nb = m->nb;
-    std::vector<int32_t> tbl(4 * (size_t)nb);
-    std::vector<double> rb((size_t)nb * RB_STRIDE);
-    for (int i = 0; i < nb; ++i) {
-      const int s = m->slot_of[i];
-      const int32_t* ib = &m->ib[(size_t)s * IB_STRIDE];
-      tbl[4 * i] = ib[IB_PARENT] < 0 ? -1 : m->order[ib[IB_PARENT]];
-      tbl[4 * i + 1] = ib[IB_JTYPE]; tbl[4 * i + 2] = ib[IB_QOFF]; tbl[4 * i + 3] = ib[IB_VOFF];
-      memcpy(&rb[(size_t)i * RB_STRIDE], &m->rb[(size_t)s * RB_STRIDE], sizeof(double) * RB_STRIDE);
-    }
-    if ((st = upload_real(&w->d_tan_rb, rb, w->dtype))) return st;
-    w->tan.nb = nb; w->tan.nq = m->nq; w->tan.nv = m->nv; w->tan.rb = w->d_tan_rb;
-    memcpy(w->tan.gravity, m->gravity, sizeof w->tan.gravity);
-    if ((st = upload(&w->d_tan_tbl, tbl.data(), tbl.size() * sizeof(int32_t)))) return st;
-    w->tan.tbl = (const int32_t*)w->d_tan_tbl;
-  }
-  w->tan_tbl_ready = true;
-  return RBD_OK;
-}
-
-// the tables of np points (point k on reference body body[k] at r[3k … 3k + 2]) on the device: rbd_workspace_set_points, and the model's contact points for
-// the contact VJPs.  *d_i, *d_r: the two buffers (NULL on entry)
-int point_plan_upload(rbd_ws* w, int np, const int32_t* body, const double* r, void** d_i, void** d_r, PointPlan* out) {
-  const rbd_model* m = w->model;
-  int st;
-  const PointPlanTables T = point_plan(m->nb, m->parent_ref.data(), np, body);
-  const std::vector<int32_t>&poff = T.poff, &path = T.path, &uni = T.uni, &ubeg = T.ubeg, &upts = T.upts;
-  std::vector<int32_t> all;
-  const size_t o_path = poff.size(), o_uni = o_path + path.size(), o_ubeg = o_uni + uni.size(), o_upts = o_ubeg + ubeg.size();
-  for (const std::vector<int32_t>* v : {&poff, &path, &uni, &ubeg, &upts}) all.insert(all.end(), v->begin(), v->end());
-  if ((st = upload(d_i, all.data(), all.size() * sizeof(int32_t)))) return st;
-  if ((st = upload_real(d_r, std::vector<double>(r, r + 3 * (size_t)np), w->dtype))) return st;
-  const int32_t* d = (const int32_t*)*d_i;
-  *out = PointPlan{np, (int32_t)uni.size(), d, d + o_path, d + o_uni, d + o_ubeg, d + o_upts, *d_r};
-  return RBD_OK;
-}
-
-// what every derivative entry point shares, allocated by the first one: the tables in the reference's order, M, its factor, c and v̇
-int tan_base(rbd_ws* w) {
-  const rbd_model* m = w->model;
-  const size_t es = esize(w);
-  const long B = w->max_batch;
-  int st;
-  if (!w->tan_ready) {
-    if ((st = tan_tables(w))) return st;
-    if (m->big && (st = big_scratch(w, w->max_batch))) return st;
-    const size_t nv = (size_t)m->nv;
-    if ((st = ensure(&w->d_tan_M, &w->d_tan_M_bytes, es * nv * nv * B)) || (st = ensure(&w->d_tan_L, &w->d_tan_L_bytes, es * nv * nv * B)) ||
-        (st = ensure(&w->d_tan_c, &w->d_tan_c_bytes, es * nv * B)) || (st = ensure(&w->d_tan_vd, &w->d_tan_vd_bytes, es * nv * B)))
-      return st;
-    w->tan_ready = true;
-  }
-  return RBD_OK;
-}
-
-// the first derivative call of a workspace (and one with more directions than before) allocates; every later call only launches
-int tan_ensure(rbd_ws* w, int ntan) {
-  const rbd_model* m = w->model;
-  const size_t es = esize(w);
-  const long B = w->max_batch;
-  int st;
-  if ((st = tan_base(w))) return st;
-  ntan = std::max(ntan, m->nq + m->nv);  // (the Jacobians' directions: a JVP call after a derivatives call allocates nothing)
-  if (ntan > w->tan_ntan) {
-    const int N = tangent_chunk((int)es);
-    const size_t per = std::max<size_t>(1, tangent_scratch_elems_per_thread(w->tan, (int)es) * es);
-    const long want = B * ((ntan + N - 1) / N);
-    const long cap = std::max<long>(64, (long)(TAN_SCRATCH_CAP / per) / 64 * 64);
-    const long threads = std::min(want, cap);
-    if ((st = ensure(&w->d_tan_scratch, &w->d_tan_scratch_bytes, per * threads))) return st;
-    w->tan_threads = threads;
-    if ((st = ensure(&w->d_tan_rhs, &w->d_tan_rhs_bytes, es * std::max<size_t>(1, (size_t)m->nv * ntan * B)))) return st;
-    if (m->nv > 64 && (st = ensure(&w->d_tan_x, &w->d_tan_x_bytes, es * (size_t)m->nv * ntan * B))) return st;
-    w->tan_ntan = ntan;
-  }
-  return RBD_OK;
-}
-
-// the checks every derivative call shares (every model size: the tangent kernels walk the tree in the reference's order, rbd_tangent_kernels.hip)
-int tan_check(rbd_ws* w, int32_t B, const rbd_opts_t* opts, Opts* o) {
-  if (int st = begin_call(w, B, opts, kAnySize, o)) return st;
-  if (w->model->nloops > 0) return RBD_ERR_HAS_LOOPS;  // (inverse_dynamics!: src/mechanism_algorithms.jl:549)
-  if (w->model->ncp > 0 && w->model->nhs > 0) return RBD_ERR_UNSUPPORTED;  // (as rbd_dynamics: the contact wrenches need the additional state)
-  if (o->memory != RBD_MEM_DEVICE) return RBD_ERR_UNSUPPORTED;
-  return RBD_OK;
-}
-
-template <typename T> TanArgs<T> tan_args(rbd_ws* w, int32_t B, int layout, int ntan, const void* q, const void* v, const void* vdot, const void* fext) {
-  const rbd_model* m = w->model;
-  TanArgs<T> A{};
-  A.B = B; A.ntan = ntan; A.unit = 0; A.g0 = 0;
-  A.q = (const T*)q; A.v = (const T*)v; A.vdot = (const T*)vdot; A.fext = (const T*)fext;
-  A.Lq = layout_of(layout, m->nq, B); A.Lv = layout_of(layout, m->nv, B); A.Lf = layout_of(layout, 6L * m->nb, B);
-  A.Ldq = layout_of(layout, (long)m->nq * ntan, B); A.Ldv = layout_of(layout, (long)m->nv * ntan, B); A.Ldf = layout_of(layout, 6L * m->nb * ntan, B);
-  A.sign = T(1);
-  A.out = ColOut<T>{nullptr, Layout{0, 0}, nullptr, Layout{0, 0}, INT32_MAX, m->nv};
-  return A;
-}
-
-// dynamics!'s value the reference's way (dynamics_solve! :764, :819): c = dynamics_bias!, M = mass_matrix!, L = chol(M) into the workspace, v̇ = L⁻ᵀ L⁻¹ (τ − c)
-template <typename T> int tan_dynamics_value(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, const void* tau, const void* fext, void* vd) {
-  const rbd_model* m = w->model;
-  const Layout Lq = layout_of(layout, m->nq, B), Lv = layout_of(layout, m->nv, B), Lf = layout_of(layout, 6L * m->nb, B), Lm{B, 1};
-  if (m->big) {
-    HIP_TRY(launch_big_rnea<T>(w->big, B, q, v, nullptr, fext, w->d_tan_c, nullptr, w->d_big_scratch, nullptr, nullptr, Lq, Lv, Lf, w->stream));
-    HIP_TRY(launch_big_crba<T>(w->big, B, q, w->d_tan_M, w->d_big_scratch, Lq, Lm, w->stream));
-  } else {
-    HIP_TRY(launch_rnea<T>(w->dm, B, q, v, nullptr, fext, w->d_tan_c, nullptr, nullptr, Lq, Lv, Lf, w->stream));
-    HIP_TRY(launch_crba<T>(w->dm, B, q, w->d_tan_M, Lq, Lm, 1, w->stream));
-  }
-  // (the wavefront Cholesky kernels hold one row per lane: beyond 64 coordinates the one-thread-per-state factorisation of the any-size route)
-  if (m->nv > 64) HIP_TRY(launch_big_chol_solve<T>(m->nv, B, w->d_tan_M, w->d_tan_L, tau, w->d_tan_c, vd, Lm, Lv, w->d_notpd, w->stream));
-  else HIP_TRY(launch_chol_solve<T>(m->nv, B, w->d_tan_M, tau, w->d_tan_c, vd, w->d_tan_L, Lm, Lv, w->d_notpd, w->stream));
-  return RBD_OK;
-}
-
-template <typename T>
-int tan_id_jvp(rbd_ws* w, int32_t B, int32_t ntan, int layout, const void* q, const void* v, const void* vdot, const void* fext, const void* dq, const void* dv,
-               const void* dvdot, const void* dfext, void* tau_out, void* dtau_out) {
-  TanArgs<T> A = tan_args<T>(w, B, layout, ntan, q, v, vdot, fext);
-  A.dq = (const T*)dq; A.dv = (const T*)dv; A.dvdot = (const T*)dvdot; A.dfext = (const T*)dfext;
-  A.tau = (T*)tau_out;
-  A.out.a = (T*)dtau_out; A.out.La = A.Ldv;
-  HIP_TRY(launch_tangent_rnea<T>(w->tan, A, w->d_tan_scratch, w->tan_threads, w->stream));
-  return RBD_OK;
-}
-
-template <typename T>
-int tan_dyn_jvp(rbd_ws* w, int32_t B, int32_t ntan, int layout, const void* q, const void* v, const void* tau, const void* fext, const void* dq, const void* dv,
-                const void* dtau, const void* dfext, void* vdot_out, void* dvdot_out) {
-  const rbd_model* m = w->model;
-  void* vd = vdot_out ? vdot_out : w->d_tan_vd;
-  int st;
-  if ((st = tan_dynamics_value<T>(w, B, layout, q, v, tau, fext, vd))) return st;
-  if (!dvdot_out) return RBD_OK;
-  // M dv̇ = dτ − ∂ID(q, v, v̇)·(dq, dv, 0, dfext): the right-hand sides (batch-innermost) in one tangent pass, then ntan solves against the one factor
-  TanArgs<T> A = tan_args<T>(w, B, layout, ntan, q, v, vd, fext);
-  A.dq = (const T*)dq; A.dv = (const T*)dv; A.dfext = (const T*)dfext;
-  A.out.a = (T*)w->d_tan_rhs; A.out.La = Layout{B, 1};
-  A.sign = T(-1); A.dadd = (const T*)dtau;
-  HIP_TRY(launch_tangent_rnea<T>(w->tan, A, w->d_tan_scratch, w->tan_threads, w->stream));
-  const ColOut<T> out{(T*)dvdot_out, A.Ldv, nullptr, Layout{0, 0}, INT32_MAX, m->nv};
-  HIP_TRY(launch_tangent_solve<T>(m->nv, B, 0, ntan, w->d_tan_L, Layout{B, 1}, w->d_tan_rhs, 0, out, w->d_tan_x, w->stream));
-  return RBD_OK;
-}
-
-template <typename T>
-int tan_id_derivs(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, const void* vdot, const void* fext, void* tau_out, void* dtau_dq, void* dtau_dv,
-                  void* M_out) {
-  const rbd_model* m = w->model;
-  // the directions asked for: the columns of ∂/∂q (e_0 … e_nq−1 of (q; v)), then those of ∂/∂v
-  const int g0 = dtau_dq ? 0 : m->nq, g1 = dtau_dv ? m->nq + m->nv : m->nq;
-  if (g1 > g0 || tau_out) {
-    TanArgs<T> A = tan_args<T>(w, B, layout, std::max(1, g1 - g0), q, v, vdot, fext);
-    A.unit = 1; A.g0 = g0;
-    A.tau = (T*)tau_out;
-    A.out = ColOut<T>{(T*)dtau_dq, layout_of(layout, (long)m->nv * m->nq, B), (T*)dtau_dv, layout_of(layout, (long)m->nv * m->nv, B), m->nq, m->nv};
-    if (g1 <= g0) A.out.a = A.out.b = nullptr;  // (τ alone)
-    HIP_TRY(launch_tangent_rnea<T>(w->tan, A, w->d_tan_scratch, w->tan_threads, w->stream));
-  }
-  if (M_out) {  // ∂τ/∂v̇ = M (mass_matrix! :248-272), the full square
-    const Layout Lq = layout_of(layout, m->nq, B), Lm = layout_of(layout, (long)m->nv * m->nv, B);
-    if (m->big) HIP_TRY(launch_big_crba<T>(w->big, B, q, M_out, w->d_big_scratch, Lq, Lm, w->stream));
-    else HIP_TRY(launch_crba<T>(w->dm, B, q, M_out, Lq, Lm, 1, w->stream));
-    HIP_TRY(launch_symmetrize<T>(m->nv, B, M_out, Lm, w->stream));
-  }
-  return RBD_OK;
-}
-
-template <typename T>
-int tan_dyn_derivs(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, const void* tau, const void* fext, void* vdot_out, void* dvdot_dq, void* dvdot_dv,
-                   void* dvdot_dtau) {
-  const rbd_model* m = w->model;
-  void* vd = vdot_out ? vdot_out : w->d_tan_vd;
-  int st;
-  if ((st = tan_dynamics_value<T>(w, B, layout, q, v, tau, fext, vd))) return st;
-  const int g0 = dvdot_dq ? 0 : m->nq, g1 = dvdot_dv ? m->nq + m->nv : m->nq;
-  if (g1 > g0) {  // −∂ID/∂(q, v) at the computed v̇, column g of the right-hand sides at g; then M⁻¹ of each
-    TanArgs<T> A = tan_args<T>(w, B, layout, g1 - g0, q, v, vd, fext);
-    A.unit = 1; A.g0 = g0;
-    A.out.a = (T*)w->d_tan_rhs; A.out.La = Layout{B, 1};
-    A.sign = T(-1);
-    HIP_TRY(launch_tangent_rnea<T>(w->tan, A, w->d_tan_scratch, w->tan_threads, w->stream));
-    const ColOut<T> out{(T*)dvdot_dq, layout_of(layout, (long)m->nv * m->nq, B), (T*)dvdot_dv, layout_of(layout, (long)m->nv * m->nv, B), m->nq, m->nv};
-    HIP_TRY(launch_tangent_solve<T>(m->nv, B, g0, g1 - g0, w->d_tan_L, Layout{B, 1}, w->d_tan_rhs, 0, out, w->d_tan_x, w->stream));
-  }
-  if (dvdot_dtau) {  // ∂v̇/∂τ = M⁻¹: the solve against the identity, generated in the kernel
-    const ColOut<T> out{(T*)dvdot_dtau, layout_of(layout, (long)m->nv * m->nv, B), nullptr, Layout{0, 0}, INT32_MAX, m->nv};
-    HIP_TRY(launch_tangent_solve<T>(m->nv, B, 0, m->nv, w->d_tan_L, Layout{B, 1}, nullptr, 1, out, w->d_tan_x, w->stream));
-  }
-  return RBD_OK;
-}
-
-// ---- derivatives of simulate steps (header 700 additions) -----------------------------------------------------------------------------------------------
-enum : long { SIM_TAN_CAP = 1L << 31 };  // bytes of the simulate tangent buffers at most: more directions run as several passes
-
-// tangents per (direction, state) of one pass: initial dq, dv, dτ; the stage state's dq, dv; the running sums' two; dv̇
-size_t sim_tan_per_dir(const rbd_model* m) { return 2 * (size_t)m->nq + 6 * (size_t)m->nv; }
-int sim_pass_width(rbd_ws* w, int ndir) {
-  const long per = (long)(esize(w) * sim_tan_per_dir(w->model) * (size_t)w->max_batch);
-  const int N = tangent_chunk((int)esize(w));
-  const long cap = std::max<long>(N, SIM_TAN_CAP / std::max<long>(1, per) / N * N);
-  return (int)std::min<long>(ndir, cap);
-}
-// the first call of a workspace allocates, and one whose pass is wider than any before; nothing else allocates
-int sim_ensure(rbd_ws* w, int width) {
-  const rbd_model* m = w->model;
-  const size_t es = esize(w), B = (size_t)w->max_batch;
-  int st;
-  if ((st = tan_ensure(w, width))) return st;
-  if ((st = ensure(&w->d_sim_val, &w->d_sim_val_bytes, es * B * (4 * (size_t)m->nq + 6 * (size_t)m->nv)))) return st;
-  if (width > w->sim_tan_w) {
-    if ((st = ensure(&w->d_sim_tan, &w->d_sim_tan_bytes, es * B * sim_tan_per_dir(m) * (size_t)width))) return st;
-    w->sim_tan_w = width;
-  }
-  return RBD_OK;
-}
-
-// nsteps steps of the RK4 integrator with ndir directions carried along, in passes of at most sim_tan_w directions.  JVP (jac == false): the caller's
-// dq, dv (in/out), dτ, dfext, ndir directions in the call's layout.  Jacobians (jac): the columns g0 … g0 + ndir − 1 of [∂x⁺/∂x  ∂x⁺/∂τ], unit directions
-// made on the device, written to dxdx (columns < nx) and dxdtau.  Each stage: dynamics! at the stage state (CRBA + Cholesky, the factor in the workspace),
-// the tangent RNEA (sign −1, dadd = dτ), the solve for dv̇, the stage kernel.
-template <typename T>
-int sim_tan_run(rbd_ws* w, int32_t B, int layout, void* q, void* v, const void* tau, const void* fext, double dt, int nsteps, int ndir, bool jac, int g0,
-                void* dq, void* dv, const void* dtau, const void* dfext, void* dxdx, void* dxdtau) {
-  const rbd_model* m = w->model;
-  const int nq = m->nq, nv = m->nv, nx = nq + nv, W = w->sim_tan_w;
-  const long Bm = w->max_batch;
-  const size_t es = sizeof(T);
-  const Layout Lq = layout_of(layout, nq, B), Lv = layout_of(layout, nv, B), Li{B, 1};
-  const Layout Ldq = layout_of(layout, (long)nq * ndir, B), Ldv = layout_of(layout, (long)nv * ndir, B), Ldf = layout_of(layout, 6L * m->nb * ndir, B);
-  // values (the call's layout): q0, the two stage-state buffers, the saved initial state; v0, two stage states, the running sum, the saved state
-  T* val = (T*)w->d_sim_val;
-  T *q0 = val, *qa = q0 + nq * Bm, *qb = qa + nq * Bm, *qi = qb + nq * Bm, *v0 = qi + nq * Bm, *va = v0 + nv * Bm, *vb = va + nv * Bm;
-  T *accp = vb + nv * Bm, *accv = accp + nv * Bm, *vi = accv + nv * Bm;
-  // tangents of one pass, batch-innermost
-  T* tb = (T*)w->d_sim_tan;
-  const long tw = (long)W * Bm;
-  T *dq0 = tb, *dv0 = dq0 + nq * tw, *dd0 = dv0 + nv * tw, *dqs = dd0 + nv * tw, *dvs = dqs + nq * tw, *dap = dvs + nv * tw, *dav = dap + nv * tw,
-    *dvd = dav + nv * tw;
-  auto col = [&](T* p, int n) { return ColOut<T>{p, Li, nullptr, Layout{0, 0}, INT32_MAX, n}; };
-  auto user = [&](const void* p, Layout L, int n) { return ColOut<T>{(T*)p, L, nullptr, Layout{0, 0}, INT32_MAX, n}; };
-  const int npass = (ndir + W - 1) / W;
-  if (npass > 1) {
-    HIP_TRY(hipMemcpyAsync(qi, q, es * nq * B, hipMemcpyDeviceToDevice, w->stream));
-    HIP_TRY(hipMemcpyAsync(vi, v, es * nv * B, hipMemcpyDeviceToDevice, w->stream));
-  }
-  for (int p = 0; p < npass; ++p) {
-    const int e0 = p * W, nw = std::min(W, ndir - e0);
-    if (p > 0) {  // every pass starts from the caller's state (each one writes the same state after the step)
-      HIP_TRY(hipMemcpyAsync(q, qi, es * nq * B, hipMemcpyDeviceToDevice, w->stream));
-      HIP_TRY(hipMemcpyAsync(v, vi, es * nv * B, hipMemcpyDeviceToDevice, w->stream));
-    }
-    HIP_TRY(launch_tangent_mk_load<T>(B, nw, nq, nv, jac ? g0 + e0 : e0, jac ? 1 : 0, user(dq, Ldq, nq), user(dv, Ldv, nv), user(dtau, Ldv, nv), col(dq0, nq),
-                                      col(dv0, nv), col(dd0, nv), w->stream));
-    for (int step = 0; step < nsteps; ++step) {
-      HIP_TRY(hipMemcpyAsync(q0, q, es * nq * B, hipMemcpyDeviceToDevice, w->stream));
-      HIP_TRY(hipMemcpyAsync(v0, v, es * nv * B, hipMemcpyDeviceToDevice, w->stream));
-      for (int stage = 0; stage < 4; ++stage) {
-        // the stage state: (q, v) at stage 0, then qa/va, qb/vb, qa/va; stage 3 writes the state after the step over (q, v)
-        T* qs = stage == 0 ? (T*)q : (stage == 2 ? qb : qa);
-        T* vs = stage == 0 ? (T*)v : (stage == 2 ? vb : va);
-        int st;
-        if ((st = tan_dynamics_value<T>(w, B, layout, qs, vs, tau, fext, w->d_tan_vd))) return st;
-        TanArgs<T> A = tan_args<T>(w, B, layout, nw, qs, vs, w->d_tan_vd, fext);
-        A.dq = stage == 0 ? dq0 : dqs; A.dv = stage == 0 ? dv0 : dvs; A.Ldq = Li; A.Ldv = Li;
-        A.dfext = (!jac && dfext) ? (const T*)dfext + (long)e0 * 6 * m->nb * Ldf.sk : nullptr; A.Ldf = Ldf;
-        A.out.a = (T*)w->d_tan_rhs; A.out.La = Li;
-        A.sign = T(-1); A.dadd = dd0;
-        HIP_TRY(launch_tangent_rnea<T>(w->tan, A, w->d_tan_scratch, w->tan_threads, w->stream));
-        HIP_TRY(launch_tangent_solve<T>(nv, B, 0, nw, w->d_tan_L, Li, w->d_tan_rhs, 0, col(dvd, nv), w->d_tan_x, w->stream));
-        MkTanArgs<T> S{};
-        S.B = B; S.ntan = nw; S.nb = w->tan.nb; S.stage = stage; S.dt = (T)dt; S.tbl = w->tan.tbl;
-        S.q0 = q0; S.v0 = v0; S.qs = qs; S.vs = vs; S.vd = (const T*)w->d_tan_vd; S.accp = accp; S.accv = accv;
-        S.qn = stage == 3 ? (T*)q : (stage == 1 ? qb : qa);
-        S.vn = stage == 3 ? (T*)v : (stage == 1 ? vb : va);
-        S.Lq = Lq; S.Lv = Lv;
-        S.dq0 = col(dq0, nq); S.dv0 = col(dv0, nv); S.dqs = stage == 0 ? S.dq0 : col(dqs, nq); S.dvs = stage == 0 ? S.dv0 : col(dvs, nv);
-        S.dvd = col(dvd, nv); S.daccp = col(dap, nv); S.daccv = col(dav, nv);
-        S.ocol = 0; S.ovrow = 0;
-        if (stage < 3) {
-          S.oq = col(dqs, nq); S.ov = col(dvs, nv);
-        } else if (step < nsteps - 1) {  // (the next step's base point, in place)
-          S.oq = S.dq0; S.ov = S.dv0;
-        } else if (jac) {
-          S.oq = S.ov = ColOut<T>{(T*)dxdx, layout_of(layout, (long)nx * nx, B), (T*)dxdtau, layout_of(layout, (long)nx * nv, B), nx, nx};
-          S.ocol = g0 + e0; S.ovrow = nq;
-        } else {
-          S.oq = user(dq, Ldq, nq); S.ov = user(dv, Ldv, nv); S.ocol = e0;
-        }
-        HIP_TRY(launch_tangent_mk_stage<T>(S, w->stream));
-      }
-    }
-  }
-  return RBD_OK;
-}
-
-// ---- reverse mode (header 700 additions): the adjoint RNEA, one thread per state -------------------------------------------------------------------------
-enum : long { ADJ_SCRATCH_CAP = TAN_SCRATCH_CAP };  // bytes of adjoint scratch at most: larger calls run in slabs of states
-
-// the adjoint scratch for max_batch states, in slabs beyond the cap (needs the tables of `tan`): also all that rbd_point_kinematics_vjp allocates
-int adj_scratch_ensure(rbd_ws* w) {
-  if (w->adj_states > 0) return RBD_OK;
-  const size_t per = std::max<size_t>(1, adjoint_scratch_elems_per_state(w->tan) * esize(w));
-  const long states = std::min<long>(w->max_batch, std::max<long>(64, (long)(ADJ_SCRATCH_CAP / per) / 64 * 64));
-  if (int st = ensure(&w->d_adj_scratch, &w->d_adj_scratch_bytes, per * std::max<long>(1, states))) return st;
-  w->adj_states = std::max<long>(1, states);
-  return RBD_OK;
-}
-
-// the first reverse-mode call of a workspace allocates (for max_batch states); every later call only launches
-int adj_ensure(rbd_ws* w) {
-  const rbd_model* m = w->model;
-  const size_t es = esize(w), nv = (size_t)m->nv;
-  const long B = w->max_batch;
-  int st;
-  if ((st = tan_base(w))) return st;
-  if (w->adj_ready) return RBD_OK;
-  if ((st = adj_scratch_ensure(w))) return st;
-  if ((st = ensure(&w->d_adj_rhs, &w->d_adj_rhs_bytes, es * std::max<size_t>(1, nv * B))) || (st = ensure(&w->d_adj_lam, &w->d_adj_lam_bytes, es * std::max<size_t>(1, nv * B))))
-    return st;
-  if (m->nv > 64 && (st = ensure(&w->d_adj_x, &w->d_adj_x_bytes, es * nv * B))) return st;
-  w->adj_ready = true;
-  return RBD_OK;
-}
-
-template <typename T> AdjArgs<T> adj_args(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, const void* vdot, const void* fext) {
-  const rbd_model* m = w->model;
-  AdjArgs<T> A{};
-  A.B = B;
-  A.q = (const T*)q; A.v = (const T*)v; A.vdot = (const T*)vdot; A.fext = (const T*)fext;
-  A.Lq = layout_of(layout, m->nq, B); A.Lv = layout_of(layout, m->nv, B); A.Lf = layout_of(layout, 6L * m->nb, B); A.Llam = A.Lv;
-  A.sign = T(1);
-  return A;
-}
-
-template <typename T>
-int adj_id_vjp(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, const void* vdot, const void* fext, const void* tau_bar, void* tau_out,
-               void* q_bar, void* v_bar, void* vdot_bar, void* fext_bar) {
-  AdjArgs<T> A = adj_args<T>(w, B, layout, q, v, vdot, fext);
-  A.lam = (const T*)tau_bar;
-  A.tau = (T*)tau_out; A.qbar = (T*)q_bar; A.vbar = (T*)v_bar; A.vdbar = (T*)vdot_bar; A.fbar = (T*)fext_bar;
-  HIP_TRY(launch_adjoint_rnea<T>(w->tan, A, w->d_adj_scratch, w->adj_states, w->stream));
-  return RBD_OK;
-}
-
-// v̇ = M⁻¹(τ − c) the reference's way (as rbd_dynamics_jvp), λ = M⁻¹ v̇̄ against the same factor, τ̄ = λ, (q̄, v̄, f̄ext) = −(adjoint RNEA at (q, v, v̇), λ)
-template <typename T>
-int adj_dyn_vjp(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, const void* tau, const void* fext, const void* vdot_bar, void* vdot_out,
-                void* q_bar, void* v_bar, void* tau_bar, void* fext_bar) {
-  const rbd_model* m = w->model;
-  void* vd = vdot_out ? vdot_out : w->d_tan_vd;
-  int st;
-  if ((st = tan_dynamics_value<T>(w, B, layout, q, v, tau, fext, vd))) return st;
-  if (!q_bar && !v_bar && !tau_bar && !fext_bar) return RBD_OK;
-  const Layout Lv = layout_of(layout, m->nv, B), Li{B, 1};
-  const void* rhs = vdot_bar;
-  if (layout != RBD_LAYOUT_SOA) {  // (tri_solve_col reads its right-hand side batch-innermost: SOA as it stands)
-    HIP_TRY(launch_stage_rows<T>(m->nv, B, vdot_bar, Lv, w->d_adj_rhs, w->stream));
-    rhs = w->d_adj_rhs;
-  }
-  // λ straight into τ̄ when the caller asks for it (the adjoint pass reads it from there)
-  const ColOut<T> lam = tau_bar ? ColOut<T>{(T*)tau_bar, Lv, nullptr, Layout{0, 0}, INT32_MAX, m->nv} : ColOut<T>{(T*)w->d_adj_lam, Li, nullptr, Layout{0, 0}, INT32_MAX, m->nv};
-  HIP_TRY(launch_tangent_solve<T>(m->nv, B, 0, 1, w->d_tan_L, Li, rhs, 0, lam, w->d_adj_x, w->stream));
-  if (!q_bar && !v_bar && !fext_bar) return RBD_OK;
-  AdjArgs<T> A = adj_args<T>(w, B, layout, q, v, vd, fext);
-  A.lam = lam.a; A.Llam = lam.La;
-  A.qbar = (T*)q_bar; A.vbar = (T*)v_bar; A.fbar = (T*)fext_bar;
-  A.sign = T(-1);
-  HIP_TRY(launch_adjoint_rnea<T>(w->tan, A, w->d_adj_scratch, w->adj_states, w->stream));
-  return RBD_OK;
-}
-
-// ---- reverse mode through soft contact (header 700 addition): rbd_contact_dynamics_vjp, rbd_dynamics_contact_vjp --------------------------------------------
-// the first contact VJP of a workspace allocates, for max_batch states: what every reverse-mode call shares, the model's contact points as a PointPlan of
-// their own, the per-point cotangents, the total wrenches and their cotangent, the copy of s, and what the forward contact launch writes; no later call does
-int ct_ensure(rbd_ws* w) {
-  const rbd_model* m = w->model;
-  const size_t es = esize(w), B = (size_t)w->max_batch;
-  int st;
-  if ((st = adj_ensure(w))) return st;
-  if (w->ct_ready) return RBD_OK;
-  if (w->ct_pts.np == 0) {
-    for (void** p : {&w->d_ct_i, &w->d_ct_r})  // (left by a call that ran out of memory half way)
-      if (*p) { (void)hipFree(*p); *p = nullptr; }
-    std::vector<double> r(3 * (size_t)m->ncp);
-    for (int i = 0; i < m->ncp; ++i)
-      for (int j = 0; j < 3; ++j) r[3 * (size_t)i + j] = m->cp_r[(size_t)i * CP_STRIDE + CP_LOC + j];
-    if ((st = point_plan_upload(w, m->ncp, m->cp_body.data(), r.data(), &w->d_ct_i, &w->d_ct_r, &w->ct_pts))) return st;
-  }
-  const size_t sizes[4] = {es * 3 * m->ncp * B, es * 3 * m->ncp * B, es * 6 * m->nb * B, es * 3 * m->ncp * m->nhs * B};
-  void** bufs[4] = {&w->d_ct_pbar, &w->d_ct_vbar, &w->d_ct_wbar, &w->d_ct_s};
-  for (int k = 0; k < 4; ++k)
-    if (!*bufs[k]) HIP_TRY(hipMalloc(bufs[k], sizes[k]));
-  if ((st = ensure(&w->d_body, &w->d_body_bytes, es * (size_t)m->nb * 24 * B)) || (st = ensure(&w->d_c, &w->d_c_bytes, es * (size_t)m->nv * B)) ||
-      (st = ensure(&w->d_tw, &w->d_tw_bytes, es * (size_t)6 * m->nb * B)))
-    return st;
-  w->ct_ready = true;
-  return RBD_OK;
-}
-
-// contact_adjoint_kernel at the per-body kinematics in w->d_body, then point_adjoint_kernel over the contact points: the cotangents of the bodies' wrenches
-// (wbar), of ṡ and of s after the resets -> s_bar and (q_bar, v_bar) — ADDED to what these hold with accum (the adjoint RNEA pass wrote its share before)
-template <typename T>
-int ct_adjoint(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, const void* s, const void* wbar, const void* sdot_bar, const void* s_out_bar,
-               void* q_bar, void* v_bar, void* s_bar, int accum) {
-  const rbd_model* m = w->model;
-  if (!q_bar && !v_bar && !s_bar) return RBD_OK;
-  const Layout Ls = layout_of(layout, 3L * m->ncp * m->nhs, B), Lf = layout_of(layout, 6L * m->nb, B), L3 = layout_of(layout, 3L * m->ncp, B);
-  HIP_TRY(launch_contact_adjoint<T>(w->ctm, B, w->d_body, s, wbar, sdot_bar, s_out_bar, s_bar, w->d_ct_pbar, w->d_ct_vbar, Ls, Lf, L3, w->stream));
-  if (!q_bar && !v_bar) return RBD_OK;
-  AdjArgs<T> A = adj_args<T>(w, B, layout, q, v, nullptr, nullptr);
-  A.qbar = (T*)q_bar; A.vbar = (T*)v_bar; A.accum = accum;
-  PointAdjArgs<T> C{(const T*)w->d_ct_pbar, (const T*)w->d_ct_vbar, L3};
-  HIP_TRY(launch_point_adjoint<T>(w->tan, w->ct_pts, A, C, w->d_adj_scratch, w->adj_states, w->stream));
-  return RBD_OK;
-}
-
-// ---- reverse mode through simulate steps (header 700 addition): rbd_simulate_vjp ----------------------------------------------------------------------
-enum : long { SAV_CKPT_CAP = 1L << 30 };  // bytes of step starts kept while every step's fits; beyond that two-level (√n) checkpointing
-
-// the first call of a workspace allocates the joint lists, one step's stage states and the backward pass's cotangents (for max_batch states)
-int sav_ensure(rbd_ws* w) {
-  const rbd_model* m = w->model;
-  const size_t es = esize(w), B = (size_t)w->max_batch;
-  int st;
-  if ((st = adj_ensure(w))) return st;
-  if (w->sav_ready) return RBD_OK;
-  std::vector<int32_t> jl;  // the 1-coordinate joints first (adjoint_mk_stage_kernel<T, false>), then the rest
-  int nn = 0, nw = 0;
-  for (int wide = 0; wide < 2; ++wide)
-    for (int i = 0; i < m->nb; ++i) {
-      const int jt = m->jt_ref[i];
-      if (jt == RBD_JOINT_FIXED || mk_narrow_joint(jt) == (wide == 1)) continue;
-      jl.insert(jl.end(), {jt, m->qoff_ref[i], m->voff_ref[i]});
-      ++(wide ? nw : nn);
-    }
-  if ((st = upload(&w->d_sav_joints, jl.data(), jl.size() * sizeof(int32_t)))) return st;
-  // stage states 1-3 (q, v), the running sums (2 nv), the base point's cotangent (nq + nv), v̇̄ and the sums' cotangents (3 nv)
-  if ((st = ensure(&w->d_sav, &w->d_sav_bytes, es * B * (4 * (size_t)m->nq + 9 * (size_t)m->nv)))) return st;
-  w->sav_nn = nn; w->sav_nw = nw;
-  w->sav_ready = true;
-  return RBD_OK;
-}
-
-// which step starts are kept: all (S = 1, K = nsteps slots), or every S-th in slots 0 … K − 1 and one segment's others, recomputed, in K … K + S − 2.
-// RBD_TUNE sim_vjp_ckpt_steps=<k>: room for k starts instead of the byte cap (tests reach the recompute path at small sizes).
-struct SavPlan { int S, K, slots; };
-SavPlan sav_plan(size_t slot_bytes, int nsteps) {
-  bool has;
-  const long knob = tune("sim_vjp_ckpt_steps", 0, &has);
-  const long room = has ? std::max(1L, knob) : std::max<long>(1, (long)(SAV_CKPT_CAP / std::max<size_t>(1, slot_bytes)));
-  if (nsteps <= room) return {1, nsteps, nsteps};
-  const int S = (int)std::ceil(std::sqrt((double)nsteps)), K = (nsteps + S - 1) / S;
-  return {S, K, K + S - 1};
-}
-
-template <typename T> struct SavBufs {
-  T *qs[3], *vs[3], *accp, *accv, *q0b, *v0b, *vdb, *apb, *avb;
-};
-template <typename T> SavBufs<T> sav_bufs(rbd_ws* w) {
-  const long nq = w->model->nq, nv = w->model->nv, Bm = w->max_batch;
-  T* p = (T*)w->d_sav;
-  SavBufs<T> b;
-  for (int i = 0; i < 3; ++i) { b.qs[i] = p; p += nq * Bm; b.vs[i] = p; p += nv * Bm; }
-  b.accp = p; p += nv * Bm; b.accv = p; p += nv * Bm;
-  b.q0b = p; p += nq * Bm; b.v0b = p; p += nv * Bm;
-  b.vdb = p; p += nv * Bm; b.apb = p; p += nv * Bm; b.avb = p;
-  return b;
-}
-
-template <typename T> MkAdjArgs<T> sav_args(rbd_ws* w, int32_t B, int layout, double dt, int stage) {
-  MkAdjArgs<T> A{};
-  A.B = B; A.stage = stage; A.dt = (T)dt;
-  A.Lq = layout_of(layout, w->model->nq, B); A.Lv = layout_of(layout, w->model->nv, B);
-  A.Lqb = A.Lq; A.Lvb = A.Lv;
-  return A;
-}
-
-// ---- the friction state beside (q, v) (rbd_simulate_contact_vjp): the optional contact argument of the sav_* templates -----------------------------------------
-// the first call of a workspace allocates what rbd_simulate_vjp and the contact VJPs do, and the friction state's buffers (for max_batch states)
-int sct_ensure(rbd_ws* w) {
-  const rbd_model* m = w->model;
-  int st;
-  if ((st = sav_ensure(w)) || (st = ct_ensure(w))) return st;
-  if (w->sct_ready) return RBD_OK;
-  if ((st = ensure(&w->d_sct, &w->d_sct_bytes, esize(w) * 7 * 3 * (size_t)m->ncp * m->nhs * w->max_batch))) return st;
-  w->sct_ready = true;
-  return RBD_OK;
-}
-
-template <typename T> struct SctBufs {
-  T *ss[3], *acc, *sdot, *s0b, *accb;
-};
-template <typename T> SctBufs<T> sct_bufs(rbd_ws* w) {
-  const long n = 3L * w->model->ncp * w->model->nhs * w->max_batch;
-  T* p = (T*)w->d_sct;
-  SctBufs<T> b;
-  for (int i = 0; i < 3; ++i) { b.ss[i] = p; p += n; }
-  b.acc = p; p += n; b.sdot = p; p += n; b.s0b = p; p += n; b.accb = p;
-  return b;
-}
-
-// one step's friction state: s0 its start (a checkpoint slot or the caller's s: only read), sn the state after the step (the value pass; may be s0), s_bar
-// the cotangent (the backward pass).  NULL for a mechanism without contact: rbd_simulate_vjp's launches as they were.
-struct SavContact { const Opts* o; const void* s0; void* sn; void* s_bar; };
-
-// the friction state at stage state `stage`: stage 0 a COPY of s0 (the forward contact launch resets the pairs outside — never a step's start), else the
-// workspace's stage buffer
-template <typename T> T* sct_stage_state(rbd_ws* w, int stage) { return stage == 0 ? (T*)w->d_ct_s : sct_bufs<T>(w).ss[stage - 1]; }
-
-// contact_dynamics! at a stage state: the per-body kinematics into w->d_body, ṡ into the workspace, the total wrenches fext + contact into w->d_tw
-template <typename T> int sct_contact(rbd_ws* w, int32_t B, const SavContact& C, int stage, const T* qs, const T* vs, const void* fext) {
-  const rbd_model* m = w->model;
-  T* ss = sct_stage_state<T>(w, stage);
-  if (stage == 0) HIP_TRY(hipMemcpyAsync(ss, C.s0, sizeof(T) * 3 * m->ncp * m->nhs * B, hipMemcpyDeviceToDevice, w->stream));
-  return run_contact(w, B, *C.o, qs, vs, ss, sct_bufs<T>(w).sdot, fext, nullptr, w->d_tw);
-}
-
-// the friction state's value stage map (contact_stage_value_kernel), after sct_contact left ṡ of the stage state
-template <typename T> int sct_value_step(rbd_ws* w, int32_t B, const SavContact& C, int stage, double dt) {
-  const rbd_model* m = w->model;
-  const SctBufs<T> b = sct_bufs<T>(w);
-  HIP_TRY(launch_contact_stage_value<T>(3L * m->ncp * m->nhs * B, stage, dt, C.s0, b.sdot, b.acc, stage == 3 ? C.sn : (void*)b.ss[stage], w->stream));
-  return RBD_OK;
-}
-
-// the friction state's and the contact model's share of one stage pulled back, after the adjoint RNEA pass wrote THIS stage's cotangent of the total wrenches
-// to w->d_ct_wbar: contact_stage_adjoint_kernel (the tableau, the pairs, s̄, f̄ext += the stage's, the per-point cotangents), then point_adjoint_kernel ADDING the
-// contact points' kinematic pullback to the stage state's q̄, v̄
-template <typename T>
-int sct_backward_step(rbd_ws* w, int32_t B, int layout, const SavContact& C, int stage, double dt, const T* qs, const T* vs, void* q_bar, void* v_bar, void* fext_bar) {
-  const rbd_model* m = w->model;
-  const SctBufs<T> b = sct_bufs<T>(w);
-  const Layout Ls = layout_of(layout, 3L * m->ncp * m->nhs, B), Lf = layout_of(layout, 6L * m->nb, B), L3 = layout_of(layout, 3L * m->ncp, B);
-  HIP_TRY(launch_contact_stage_adjoint<T>(w->ctm, B, stage, dt, w->d_body, sct_stage_state<T>(w, stage), w->d_ct_wbar, fext_bar, C.s_bar, b.s0b, b.accb, w->d_ct_pbar,
-                                          w->d_ct_vbar, Ls, Lf, L3, w->stream));
-  AdjArgs<T> A = adj_args<T>(w, B, layout, qs, vs, nullptr, nullptr);
-  A.qbar = (T*)q_bar; A.vbar = (T*)v_bar; A.accum = 1;
-  PointAdjArgs<T> P{(const T*)w->d_ct_pbar, (const T*)w->d_ct_vbar, L3};
-  HIP_TRY(launch_point_adjoint<T>(w->tan, w->ct_pts, A, P, w->d_adj_scratch, w->adj_states, w->stream));
-  return RBD_OK;
-}
-
-// stages 0 … last of one step from (q0, v0), values only (the route of sim_tan_run: dynamics! by CRBA + Cholesky at every stage state, then the stage
-// map): the stage states 1-3 and the running sums into the workspace, the state after the step (last = 3) into (qout, vout), which may be (q0, v0).
-// With contact (C): dynamics! at the total wrenches of the stage state, and the friction state through the same tableau.
-template <typename T>
-int sav_value_step(rbd_ws* w, int32_t B, int layout, const T* q0, const T* v0, const void* tau, const void* fext, double dt, int last, T* qout, T* vout,
-                   const SavContact* C = nullptr) {
-  const SavBufs<T> b = sav_bufs<T>(w);
-  const int32_t* jl = (const int32_t*)w->d_sav_joints;
-  for (int stage = 0; stage <= last; ++stage) {
-    const T* qs = stage == 0 ? q0 : b.qs[stage - 1];
-    const T* vs = stage == 0 ? v0 : b.vs[stage - 1];
-    int st;
-    if (C && (st = sct_contact<T>(w, B, *C, stage, qs, vs, fext))) return st;
-    if ((st = tan_dynamics_value<T>(w, B, layout, qs, vs, tau, C ? w->d_tw : fext, w->d_tan_vd))) return st;
-    MkAdjArgs<T> A = sav_args<T>(w, B, layout, dt, stage);
-    A.q0 = q0; A.v0 = v0; A.qs = qs; A.vs = vs; A.vd = (const T*)w->d_tan_vd; A.accp = b.accp; A.accv = b.accv;
-    A.qn = stage == 3 ? qout : b.qs[stage]; A.vn = stage == 3 ? vout : b.vs[stage];
-    HIP_TRY(launch_mk_stage_classes<T>(A, jl, w->sav_nn, jl + 3 * w->sav_nn, w->sav_nw, 0, w->stream));
-    if (C && (st = sct_value_step<T>(w, B, *C, stage, dt))) return st;
-  }
-  return RBD_OK;
-}
-
-// One step pulled back: (q_bar, v_bar) hold the cotangent of the state after the step on entry and that of (q0, v0) on return; τ̄ and f̄ext accumulate.
-// Stages 3 … 0: the stage map's pullback (v̇̄_i, the stage state's cotangent, the base point's), λ_i = M_i⁻¹ v̇̄_i, then the adjoint RNEA at the stage state
-// with sign −1 ADDING −(∂ID)ᵀλ_i to the stage state's cotangent and f̄ext, and λ_i to τ̄.  `fresh`: the stage states, the sums and stage 3's factor and v̇
-// are this step's already (the forward pass's last step).  With contact (C): the values at the stage's total wrenches, whose cotangent of THIS stage alone the
-// adjoint RNEA pass writes to w->d_ct_wbar (f̄ext is a sum over stages; the contact pullback must not see the sum), then sct_backward_step.
-template <typename T>
-int sav_backward_step(rbd_ws* w, int32_t B, int layout, const T* q0, const T* v0, const void* tau, const void* fext, double dt, bool fresh, void* q_bar,
-                      void* v_bar, void* tau_bar, void* fext_bar, const SavContact* C = nullptr) {
-  const rbd_model* m = w->model;
-  const SavBufs<T> b = sav_bufs<T>(w);
-  const int32_t* jl = (const int32_t*)w->d_sav_joints;
-  const Layout Li{B, 1};
-  int st;
-  if (!fresh && (st = sav_value_step<T>(w, B, layout, q0, v0, tau, fext, dt, 2, nullptr, nullptr, C))) return st;
-  for (int stage = 3; stage >= 0; --stage) {
-    const T* qs = stage == 0 ? q0 : b.qs[stage - 1];
-    const T* vs = stage == 0 ? v0 : b.vs[stage - 1];
-    if (C && !(fresh && stage == 3) && (st = sct_contact<T>(w, B, *C, stage, qs, vs, fext))) return st;
-    if (!(fresh && stage == 3) && (st = tan_dynamics_value<T>(w, B, layout, qs, vs, tau, C ? w->d_tw : fext, w->d_tan_vd))) return st;
-    MkAdjArgs<T> S = sav_args<T>(w, B, layout, dt, stage);
-    S.q0 = q0; S.qs = qs; S.vs = vs; S.accp = b.accp;
-    S.qsb = (T*)q_bar; S.vsb = (T*)v_bar; S.q0b = b.q0b; S.v0b = b.v0b; S.vdb = b.vdb; S.apb = b.apb; S.avb = b.avb;
-    HIP_TRY(launch_mk_stage_classes<T>(S, jl, w->sav_nn, jl + 3 * w->sav_nn, w->sav_nw, 1, w->stream));
-    const ColOut<T> lam{(T*)w->d_adj_lam, Li, nullptr, Layout{0, 0}, INT32_MAX, m->nv};
-    HIP_TRY(launch_tangent_solve<T>(m->nv, B, 0, 1, w->d_tan_L, Li, b.vdb, 0, lam, w->d_adj_x, w->stream));
-    AdjArgs<T> A = adj_args<T>(w, B, layout, qs, vs, w->d_tan_vd, C ? w->d_tw : fext);
-    A.lam = lam.a; A.Llam = Li;
-    A.qbar = (T*)q_bar; A.vbar = (T*)v_bar; A.fbar = (T*)(C ? w->d_ct_wbar : fext_bar); A.lbar = (T*)tau_bar;
-    A.sign = T(-1); A.accum = 1; A.fset = C ? 1 : 0;
-    HIP_TRY(launch_adjoint_rnea<T>(w->tan, A, w->d_adj_scratch, w->adj_states, w->stream));
-    if (C && (st = sct_backward_step<T>(w, B, layout, *C, stage, dt, qs, vs, q_bar, v_bar, fext_bar))) return st;
-  }
-  return RBD_OK;
-}
-
-// nsteps steps forward (the step starts kept as `P` says; q, v advanced in place), then backward from the last step to the first.  co: the options of a call with
-// contact (rbd_simulate_contact_vjp), whose slots hold (q, v, s) and whose friction state sx and cotangent sx_bar travel beside (q, v); NULL without.
-template <typename T>
-int sav_run(rbd_ws* w, int32_t B, int layout, void* q, void* v, const void* tau, const void* fext, double dt, int nsteps, SavPlan P, void* q_bar, void* v_bar,
-            void* tau_bar, void* fext_bar, const Opts* co = nullptr, void* sx = nullptr, void* sx_bar = nullptr) {
-  const rbd_model* m = w->model;
-  const long nq = m->nq, nv = m->nv, ns = co ? 3L * m->ncp * m->nhs : 0, slot = (nq + nv + ns) * B;
-  const size_t es = sizeof(T);
-  T* ck = (T*)w->d_sav_ckpt;
-  auto cq = [&](int i) { return ck + i * slot; };
-  auto cv = [&](int i) { return ck + i * slot + nq * B; };
-  auto cs = [&](int i) { return ck + i * slot + (nq + nv) * B; };
-  auto keep = [&](int i, const void* qf, const void* vf) -> hipError_t {
-    hipError_t e = hipMemcpyAsync(cq(i), qf, es * nq * B, hipMemcpyDeviceToDevice, w->stream);
-    if (e == hipSuccess && co) e = hipMemcpyAsync(cs(i), sx, es * ns * B, hipMemcpyDeviceToDevice, w->stream);
-    return e != hipSuccess ? e : hipMemcpyAsync(cv(i), vf, es * nv * B, hipMemcpyDeviceToDevice, w->stream);
-  };
-  SavContact ct{co, nullptr, nullptr, sx_bar};
-  auto contact = [&](const void* s0, void* sn) -> const SavContact* {  // (one step's friction state: from s0 to sn)
-    if (!co) return nullptr;
-    ct.s0 = s0; ct.sn = sn;
-    return &ct;
-  };
-  int st;
-  if (P.S == 1) {  // every start kept: step s from slot s into slot s + 1 (the last into (q, v))
-    HIP_TRY(keep(0, q, v));
-    for (int s = 0; s < nsteps; ++s) {
-      const bool last = s == nsteps - 1;
-      if ((st = sav_value_step<T>(w, B, layout, cq(s), cv(s), tau, fext, dt, 3, last ? (T*)q : cq(s + 1), last ? (T*)v : cv(s + 1),
-                                  contact(cs(s), last ? (T*)sx : cs(s + 1)))))
-        return st;
-    }
-  } else {  // every S-th start kept, (q, v) stepped in place
-    for (int s = 0; s < nsteps; ++s) {
-      if (s % P.S == 0) HIP_TRY(keep(s / P.S, q, v));
-      if ((st = sav_value_step<T>(w, B, layout, (T*)q, (T*)v, tau, fext, dt, 3, (T*)q, (T*)v, contact(sx, sx)))) return st;
-    }
-  }
-  bool fresh = P.S == 1;  // (the forward pass's last step left its stage states, sums and stage-3 factor)
-  for (int g = P.K - 1; g >= 0; --g) {
-    const int s0 = g * P.S, n = std::min(P.S, nsteps - s0);
-    auto start = [&](int j) { return j == 0 ? g : P.K + j - 1; };  // (the slot of step s0 + j's start)
-    for (int j = 1; j < n; ++j)  // the segment's starts recomputed from its kept one
-      if ((st = sav_value_step<T>(w, B, layout, cq(start(j - 1)), cv(start(j - 1)), tau, fext, dt, 3, cq(start(j)), cv(start(j)),
-                                  contact(cs(start(j - 1)), cs(start(j))))))
-        return st;
-    for (int j = n - 1; j >= 0; --j) {
-      if ((st = sav_backward_step<T>(w, B, layout, cq(start(j)), cv(start(j)), tau, fext, dt, fresh, q_bar, v_bar, tau_bar, fext_bar, contact(cs(start(j)), nullptr))))
-        return st;
-      fresh = false;
-    }
-  }
-  return RBD_OK;
-}
-
-// rbd_simulate_contact_vjp's run: sav_run with the friction state beside (q, v)
-template <typename T>
-int sct_run(rbd_ws* w, int32_t B, const Opts& o, void* q, void* v, void* s, const void* tau, const void* fext, double dt, int nsteps, SavPlan P, void* q_bar,
-            void* v_bar, void* s_bar, void* tau_bar, void* fext_bar) {
-  return sav_run<T>(w, B, o.layout, q, v, tau, fext, dt, nsteps, P, q_bar, v_bar, tau_bar, fext_bar, &o, s, s_bar);
-}
-}  // namespace
-
-extern "C" {
-
-int rbd_inverse_dynamics_jvp(rbd_ws_t* w, int32_t B, int32_t ntan, const void* q, const void* v, const void* vdot, const void* fext, const void* dq,
-                             const void* dv, const void* dvdot, const void* dfext, void* tau_out, void* dtau_out, const rbd_opts_t* opts) {
-  Opts o;
-  int st = tan_check(w, B, opts, &o);
-  if (st != RBD_OK) return st;
-  const rbd_model* m = w->model;
-  if (ntan <= 0 || missing(q, m->nq) || missing(v, m->nv) || missing(vdot, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
-  if (B == 0 || m->nv == 0) return RBD_OK;
-  HIP_TRY(hipSetDevice(w->device));
-  if ((st = tan_ensure(w, ntan))) return st;
-  Timed t(w);
-  w->last_kernel = "tangent_rnea_kernel";
-  return by_dtype(w->dtype, [&](auto t) { return tan_id_jvp<decltype(t)>(w, B, ntan, o.layout, q, v, vdot, fext, dq, dv, dvdot, dfext, tau_out, dtau_out); });
-}
-
-int rbd_dynamics_jvp(rbd_ws_t* w, int32_t B, int32_t ntan, const void* q, const void* v, const void* tau, const void* fext, const void* dq, const void* dv,
-                     const void* dtau, const void* dfext, void* vdot_out, void* dvdot_out, const rbd_opts_t* opts) {
-  Opts o;
-  int st = tan_check(w, B, opts, &o);
-  if (st != RBD_OK) return st;
-  const rbd_model* m = w->model;
-  if (ntan <= 0 || missing(q, m->nq) || missing(v, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
-  if (B == 0 || m->nv == 0) return RBD_OK;
-  HIP_TRY(hipSetDevice(w->device));
-  if ((st = tan_ensure(w, ntan))) return st;
-  Timed t(w);
-  w->last_kernel = "tangent_rnea_kernel + tangent_solve_kernel";
-  return by_dtype(w->dtype, [&](auto t) { return tan_dyn_jvp<decltype(t)>(w, B, ntan, o.layout, q, v, tau, fext, dq, dv, dtau, dfext, vdot_out, dvdot_out); });
-}
-
-int rbd_inverse_dynamics_derivatives(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* vdot, const void* fext, void* tau_out, void* dtau_dq,
-                                     void* dtau_dv, void* M_out, const rbd_opts_t* opts) {
-  Opts o;
-  int st = tan_check(w, B, opts, &o);
-  if (st != RBD_OK) return st;
-  const rbd_model* m = w->model;
-  if (missing(q, m->nq) || missing(v, m->nv) || missing(vdot, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
-  if (B == 0 || m->nv == 0) return RBD_OK;
-  HIP_TRY(hipSetDevice(w->device));
-  if ((st = tan_ensure(w, m->nq + m->nv))) return st;
-  Timed t(w);
-  w->last_kernel = "tangent_rnea_kernel";
-  return by_dtype(w->dtype, [&](auto t) { return tan_id_derivs<decltype(t)>(w, B, o.layout, q, v, vdot, fext, tau_out, dtau_dq, dtau_dv, M_out); });
-}
-
-int rbd_dynamics_derivatives(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* tau, const void* fext, void* vdot_out, void* dvdot_dq,
-                             void* dvdot_dv, void* dvdot_dtau, const rbd_opts_t* opts) {
-  Opts o;
-  int st = tan_check(w, B, opts, &o);
-  if (st != RBD_OK) return st;
-  const rbd_model* m = w->model;
-  if (missing(q, m->nq) || missing(v, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
-  if (B == 0 || m->nv == 0) return RBD_OK;
-  HIP_TRY(hipSetDevice(w->device));
-  if ((st = tan_ensure(w, m->nq + m->nv))) return st;
-  Timed t(w);
-  w->last_kernel = "tangent_rnea_kernel + tangent_solve_kernel";
-  return by_dtype(w->dtype, [&](auto t) { return tan_dyn_derivs<decltype(t)>(w, B, o.layout, q, v, tau, fext, vdot_out, dvdot_dq, dvdot_dv, dvdot_dtau); });
-}
-
-int rbd_simulate_jvp(rbd_ws_t* w, int32_t B, int32_t ntan, void* q, void* v, const void* tau, const void* fext, double dt, int32_t nsteps, void* dq,
-                     void* dv, const void* dtau, const void* dfext, const rbd_opts_t* opts) {
-  Opts o;
-  int st = tan_check(w, B, opts, &o);
-  if (st != RBD_OK) return st;
-  if (ntan <= 0 || !(dt > 0) || nsteps < 0 || !q || !v || !dq || !dv) return RBD_ERR_INVALID_ARGUMENT;
-  if (B == 0 || nsteps == 0 || w->model->nv == 0) return RBD_OK;
-  HIP_TRY(hipSetDevice(w->device));
-  const int width = sim_pass_width(w, ntan);
-  if ((st = sim_ensure(w, width))) return st;
-  Timed t(w);
-  w->last_kernel = "tangent_rnea_kernel + tangent_solve_kernel + tangent_mk_stage_kernel";
-  return by_dtype(w->dtype, [&](auto t) {
-    return sim_tan_run<decltype(t)>(w, B, o.layout, q, v, tau, fext, dt, nsteps, ntan, false, 0, dq, dv, dtau, dfext, nullptr, nullptr);
-  });
-}
-
-int rbd_simulate_step_derivatives(rbd_ws_t* w, int32_t B, void* q, void* v, const void* tau, const void* fext, double dt, void* dx_dx, void* dx_dtau,
-                                  const rbd_opts_t* opts) {
-  Opts o;
-  int st = tan_check(w, B, opts, &o);
-  if (st != RBD_OK) return st;
-  const rbd_model* m = w->model;
-  if (!(dt > 0) || !q || !v) return RBD_ERR_INVALID_ARGUMENT;
-  if (B == 0 || m->nv == 0) return RBD_OK;
-  HIP_TRY(hipSetDevice(w->device));
-  // the columns asked for: those of ∂x⁺/∂x (0 … nx − 1), then those of ∂x⁺/∂τ (a pass of one column that writes nowhere when neither is)
-  const int nx = m->nq + m->nv, g0 = dx_dx ? 0 : nx, g1 = dx_dtau ? nx + m->nv : nx, ncol = std::max(1, g1 - g0);
-  const int width = sim_pass_width(w, std::max(ncol, nx + m->nv));  // (allocated for every column: a call with the other output allocates nothing)
-  if ((st = sim_ensure(w, width))) return st;
-  Timed t(w);
-  w->last_kernel = "tangent_rnea_kernel + tangent_solve_kernel + tangent_mk_stage_kernel";
-  return by_dtype(w->dtype, [&](auto t) {
-    return sim_tan_run<decltype(t)>(w, B, o.layout, q, v, tau, fext, dt, 1, ncol, true, g0, nullptr, nullptr, nullptr, nullptr, dx_dx, dx_dtau);
-  });
-}
-
-int rbd_inverse_dynamics_vjp(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* vdot, const void* fext, const void* tau_bar, void* tau_out,
-                             void* q_bar, void* v_bar, void* vdot_bar, void* fext_bar, const rbd_opts_t* opts) {
-  Opts o;
-  int st = tan_check(w, B, opts, &o);
-  if (st != RBD_OK) return st;
-  const rbd_model* m = w->model;
-  if (missing(q, m->nq) || missing(v, m->nv) || missing(vdot, m->nv) || missing(tau_bar, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
-  if (B == 0 || m->nv == 0) return RBD_OK;
-  HIP_TRY(hipSetDevice(w->device));
-  if ((st = adj_ensure(w))) return st;
-  Timed t(w);
-  w->last_kernel = "adjoint_rnea_kernel";
-  return by_dtype(w->dtype, [&](auto t) { return adj_id_vjp<decltype(t)>(w, B, o.layout, q, v, vdot, fext, tau_bar, tau_out, q_bar, v_bar, vdot_bar, fext_bar); });
-}
-
-int rbd_dynamics_vjp(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* tau, const void* fext, const void* vdot_bar, void* vdot_out,
-                     void* q_bar, void* v_bar, void* tau_bar, void* fext_bar, const rbd_opts_t* opts) {
-  Opts o;
-  int st = tan_check(w, B, opts, &o);
-  if (st != RBD_OK) return st;
-  const rbd_model* m = w->model;
-  if (missing(q, m->nq) || missing(v, m->nv) || missing(vdot_bar, m->nv)) return RBD_ERR_INVALID_ARGUMENT;
-  if (B == 0 || m->nv == 0) return RBD_OK;
-  HIP_TRY(hipSetDevice(w->device));
-  if ((st = adj_ensure(w))) return st;
-  Timed t(w);
-  w->last_kernel = "tangent_solve_kernel + adjoint_rnea_kernel";
-  return by_dtype(w->dtype, [&](auto t) { return adj_dyn_vjp<decltype(t)>(w, B, o.layout, q, v, tau, fext, vdot_bar, vdot_out, q_bar, v_bar, tau_bar, fext_bar); });
-}
-
-int rbd_simulate_vjp(rbd_ws_t* w, int32_t B, void* q, void* v, const void* tau, const void* fext, double dt, int32_t nsteps, void* q_bar, void* v_bar,
-                     void* tau_bar, void* fext_bar, const rbd_opts_t* opts) {
-  Opts o;
-  int st = tan_check(w, B, opts, &o);
-  if (st != RBD_OK) return st;
-  if (!(dt > 0) || nsteps < 0 || !q || !v || !q_bar || !v_bar) return RBD_ERR_INVALID_ARGUMENT;
-  if (B == 0) return RBD_OK;
-  const rbd_model* m = w->model;
-  const size_t es = esize(w);
-  HIP_TRY(hipSetDevice(w->device));
-  // τ̄ and f̄ext are sums over every stage of every step: zero first (all of them when nothing moves)
-  if (tau_bar) HIP_TRY(hipMemsetAsync(tau_bar, 0, es * m->nv * B, w->stream));
-  if (fext_bar) HIP_TRY(hipMemsetAsync(fext_bar, 0, es * 6 * m->nb * B, w->stream));
-  if (nsteps == 0 || m->nv == 0) return RBD_OK;
-  if ((st = sav_ensure(w))) return st;
-  const size_t slot_bytes = es * (size_t)(m->nq + m->nv) * B;
-  const SavPlan P = sav_plan(slot_bytes, nsteps);
-  if ((st = ensure(&w->d_sav_ckpt, &w->d_sav_ckpt_bytes, slot_bytes * P.slots))) return st;  // (only a call that needs more room than any before)
-  Timed t(w);
-  w->last_kernel = "value_mk_stage_kernel + adjoint_mk_stage_kernel + tangent_solve_kernel + adjoint_rnea_kernel";
-  return by_dtype(w->dtype, [&](auto t) { return sav_run<decltype(t)>(w, B, o.layout, q, v, tau, fext, dt, nsteps, P, q_bar, v_bar, tau_bar, fext_bar); });
-}
-
-// ---- point kinematics (rbd_point.hpp): rbd_workspace_set_points, rbd_point_kinematics, rbd_point_kinematics_vjp -------------------------------------------------
-int rbd_workspace_set_points(rbd_ws_t* w, int32_t npoints, const int32_t* body, const double* r) {
-  if (!w || npoints < 0 || (npoints > 0 && (!body || !r))) return RBD_ERR_INVALID_ARGUMENT;
-  const rbd_model* m = w->model;
-  if (m->nloops > 0) return RBD_ERR_HAS_LOOPS;
-  for (int k = 0; k < npoints; ++k)
-    if (body[k] < 0 || body[k] >= m->nb) return RBD_ERR_INVALID_ARGUMENT;
-  HIP_TRY(hipSetDevice(w->device));
-  HIP_TRY(hipStreamSynchronize(w->stream));  // (a call still running reads the tables replaced here)
-  if (w->d_pt_i) { HIP_TRY(hipFree(w->d_pt_i)); w->d_pt_i = nullptr; }
-  if (w->d_pt_r) { HIP_TRY(hipFree(w->d_pt_r)); w->d_pt_r = nullptr; }
-  w->pts = PointPlan{};
-  if (npoints == 0) return RBD_OK;
-  int st;
-  if ((st = tan_tables(w))) return st;
-  return point_plan_upload(w, npoints, body, r, &w->d_pt_i, &w->d_pt_r, &w->pts);
-}
-
-int rbd_point_kinematics(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* vdot, void* pos, void* vel, void* acc, void* jac,
-                         const rbd_opts_t* opts) {
-  Opts o;
-  int st = begin_call(w, B, opts, kAnySize, &o);
-  if (st != RBD_OK) return st;
-  const rbd_model* m = w->model;
-  if (m->nloops > 0) return RBD_ERR_HAS_LOOPS;
-  if (w->pts.np == 0 || !q || ((vel || acc) && missing(v, m->nv))) return RBD_ERR_INVALID_ARGUMENT;
-  if (B == 0) return RBD_OK;
-  HIP_TRY(hipSetDevice(w->device));
-  const long P = w->pts.np;
-  const size_t row = esize(w) * B;
-  HostIO io(w, o.memory);
-  const void *dq, *dv, *dvd;
-  void *dpos, *dvel, *dacc, *djac;
-  if ((st = io.in(q, row * m->nq, &dq)) || (st = io.in(v, row * m->nv, &dv)) || (st = io.in(vdot, row * m->nv, &dvd)) || (st = io.out(pos, row * 3 * P, &dpos)) ||
-      (st = io.out(vel, row * 3 * P, &dvel)) || (st = io.out(acc, row * 3 * P, &dacc)) || (st = io.out(jac, row * 3 * P * m->nv, &djac)))
-    return st;
-  w->last_kernel = "point_kin_kernel";
-  {
-    Timed t(w);
-    HIP_TRY(by_dtype(w->dtype, [&](auto t) {
-      using T = decltype(t);
-      PointArgs<T> A{};
-      A.B = B; A.q = (const T*)dq; A.v = (const T*)dv; A.vdot = (const T*)dvd;
-      A.Lq = layout_of(o.layout, m->nq, B); A.Lv = layout_of(o.layout, m->nv, B); A.L3 = layout_of(o.layout, 3 * P, B); A.Lj = layout_of(o.layout, 3 * P * m->nv, B);
-      A.pos = (T*)dpos; A.vel = (T*)dvel; A.acc = (T*)dacc; A.jac = (T*)djac;
-      return launch_point_kin<T>(w->tan, w->pts, A, w->stream);
-    }));
-  }
-  return io.finish();
-}
-
-int rbd_point_kinematics_vjp(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* pos_bar, const void* vel_bar, void* q_bar, void* v_bar,
-                             const rbd_opts_t* opts) {
-  Opts o;
-  int st = tan_check(w, B, opts, &o);
-  if (st != RBD_OK) return st;
-  const rbd_model* m = w->model;
-  if (w->pts.np == 0 || missing(q, m->nq) || missing(v, m->nv) || (!pos_bar && !vel_bar)) return RBD_ERR_INVALID_ARGUMENT;
-  if (B == 0 || (!q_bar && !v_bar)) return RBD_OK;
-  HIP_TRY(hipSetDevice(w->device));
-  if ((st = adj_scratch_ensure(w))) return st;
-  Timed t(w);
-  w->last_kernel = "point_adjoint_kernel";
-  HIP_TRY(by_dtype(w->dtype, [&](auto t) {
-    using T = decltype(t);
-    AdjArgs<T> A = adj_args<T>(w, B, o.layout, q, v, nullptr, nullptr);
-    A.qbar = (T*)q_bar; A.vbar = (T*)v_bar;
-    PointAdjArgs<T> C{(const T*)pos_bar, (const T*)vel_bar, layout_of(o.layout, 3L * w->pts.np, B)};
-    return launch_point_adjoint<T>(w->tan, w->pts, A, C, w->d_adj_scratch, w->adj_states, w->stream);
-  }));
-  return RBD_OK;
-}
-
-// ---- reverse mode through soft contact (rbd_contact.hpp): rbd_contact_dynamics_vjp, rbd_dynamics_contact_vjp ----------------------------------------------------
-static int contact_vjp_scope(rbd_ws* w, int32_t B, const rbd_opts_t* opts, Opts* o) {
-  if (int st = begin_call(w, B, opts, kAnySize, o)) return st;
-  if (w->model->nloops > 0) return RBD_ERR_HAS_LOOPS;
-  if (w->model->ncp == 0 || w->model->nhs == 0) return RBD_ERR_INVALID_ARGUMENT;  // (as rbd_contact_dynamics: use rbd_dynamics_vjp)
-  if (o->memory != RBD_MEM_DEVICE) return RBD_ERR_UNSUPPORTED;
-  return RBD_OK;
-}
-
-int rbd_contact_dynamics_vjp(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* s, const void* cw_bar, const void* sdot_bar, const void* s_out_bar,
-                             void* q_bar, void* v_bar, void* s_bar, const rbd_opts_t* opts) {
-  Opts o;
-  int st = contact_vjp_scope(w, B, opts, &o);
-  if (st != RBD_OK) return st;
-  if (!q || !v || !s || (!cw_bar && !sdot_bar && !s_out_bar)) return RBD_ERR_INVALID_ARGUMENT;
-  if (B == 0) return RBD_OK;
-  HIP_TRY(hipSetDevice(w->device));
-  if ((st = ct_ensure(w))) return st;
-  Timed t(w);
-  w->last_kernel = "contact_adjoint_kernel + point_adjoint_kernel";
-  if ((st = run_contact_kinematics(w, B, o, q, v))) return st;
-  return by_dtype(w->dtype, [&](auto t) { return ct_adjoint<decltype(t)>(w, B, o.layout, q, v, s, cw_bar, sdot_bar, s_out_bar, q_bar, v_bar, s_bar, 0); });
-}
-
-int rbd_dynamics_contact_vjp(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* s, const void* tau, const void* fext, const void* vdot_bar,
-                             const void* sdot_bar, const void* s_out_bar, void* vdot_out, void* sdot_out, void* q_bar, void* v_bar, void* s_bar, void* tau_bar,
-                             void* fext_bar, const rbd_opts_t* opts) {
-  Opts o;
-  int st = contact_vjp_scope(w, B, opts, &o);
-  if (st != RBD_OK) return st;
-  if (!q || !v || !s || (!vdot_bar && !sdot_bar && !s_out_bar)) return RBD_ERR_INVALID_ARGUMENT;
-  if (B == 0) return RBD_OK;
-  HIP_TRY(hipSetDevice(w->device));
-  if ((st = ct_ensure(w))) return st;
-  const rbd_model* m = w->model;
-  const size_t es = esize(w);
-  Timed t(w);
-  w->last_kernel = "tangent_solve_kernel + adjoint_rnea_kernel + contact_adjoint_kernel + point_adjoint_kernel";
-  // the forward contact launch resets the friction state of the points outside: on a copy (s is the caller's, const); total wrenches into the workspace
-  HIP_TRY(hipMemcpyAsync(w->d_ct_s, s, es * 3 * m->ncp * m->nhs * B, hipMemcpyDeviceToDevice, w->stream));
-  if ((st = run_contact(w, B, o, q, v, w->d_ct_s, sdot_out, fext, nullptr, w->d_tw))) return st;
-  return by_dtype(w->dtype, [&](auto t) -> int {
-    using T = decltype(t);
-    int st;
-    const void* wbar = nullptr;
-    if (vdot_bar) {
-      // v̇ as a function of the total wrenches: its f̄ext is their cotangent — the caller's fext_bar (totalwrenches = fext + contactwrenches) and the contact
-      // wrenches' — and q̄, v̄ are the dynamics' share, which the contact points' is added to
-      void* wb = fext_bar ? fext_bar : ((q_bar || v_bar || s_bar) ? w->d_ct_wbar : nullptr);
-      if ((st = adj_dyn_vjp<T>(w, B, o.layout, q, v, tau, w->d_tw, vdot_bar, vdot_out, q_bar, v_bar, tau_bar, wb))) return st;
-      wbar = wb;
-    } else {  // no cotangent of v̇: τ and fext reach ṡ and s_out through nothing
-      if (vdot_out && (st = tan_dynamics_value<T>(w, B, o.layout, q, v, tau, w->d_tw, vdot_out))) return st;
-      if (tau_bar) HIP_TRY(hipMemsetAsync(tau_bar, 0, es * m->nv * B, w->stream));
-      if (fext_bar) HIP_TRY(hipMemsetAsync(fext_bar, 0, es * 6 * m->nb * B, w->stream));
-    }
-    return ct_adjoint<T>(w, B, o.layout, q, v, s, wbar, sdot_bar, s_out_bar, q_bar, v_bar, s_bar, vdot_bar ? 1 : 0);
-  });
-}
-
-int rbd_simulate_contact_vjp(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, const void* tau, const void* fext, double dt, int32_t nsteps, void* q_bar,
-                             void* v_bar, void* s_bar, void* tau_bar, void* fext_bar, const rbd_opts_t* opts) {
-  Opts o;
-  int st = contact_vjp_scope(w, B, opts, &o);
-  if (st != RBD_OK) return st;
-  if (!(dt > 0) || nsteps < 0 || !q || !v || !s || !q_bar || !v_bar || !s_bar) return RBD_ERR_INVALID_ARGUMENT;
-  if (B == 0) return RBD_OK;
-  const rbd_model* m = w->model;
-  if (m->nv == 0) return RBD_ERR_UNSUPPORTED;  // (contact points on a mechanism that cannot move: nothing to differentiate)
-  const size_t es = esize(w);
-  HIP_TRY(hipSetDevice(w->device));
-  // τ̄ and f̄ext are sums over every stage of every step: zero first (all of them when nothing moves)
-  if (tau_bar) HIP_TRY(hipMemsetAsync(tau_bar, 0, es * m->nv * B, w->stream));
-  if (fext_bar) HIP_TRY(hipMemsetAsync(fext_bar, 0, es * 6 * m->nb * B, w->stream));
-  if (nsteps == 0) return RBD_OK;
-  if ((st = sct_ensure(w))) return st;
-  const size_t slot_bytes = es * (size_t)(m->nq + m->nv + 3 * m->ncp * m->nhs) * B;
-  const SavPlan P = sav_plan(slot_bytes, nsteps);
-  if ((st = ensure(&w->d_sav_ckpt, &w->d_sav_ckpt_bytes, slot_bytes * P.slots))) return st;  // (only a call that needs more room than any before)
-  Timed t(w);
-  w->last_kernel = "value_mk_stage_kernel + contact_kernel + contact_stage_value_kernel + adjoint_mk_stage_kernel + tangent_solve_kernel + adjoint_rnea_kernel + "
-                   "contact_stage_adjoint_kernel + point_adjoint_kernel";
-  return by_dtype(w->dtype, [&](auto t) {
-    return sct_run<decltype(t)>(w, B, o, q, v, s, tau, fext, dt, nsteps, P, q_bar, v_bar, s_bar, tau_bar, fext_bar);
-  });
 }
 
 }  // extern "C"

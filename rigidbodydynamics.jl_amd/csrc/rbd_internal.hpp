@@ -1,4 +1,5 @@
-// rbd_internal.hpp — host-side declarations shared by rbd_kernels.hip and rbd_capi.hip.
+// rbd_internal.hpp — host-side declarations of the launchers: shared by the *_kernels.hip files that define them and the two files of the C ABI that call
+// them (rbd_capi.hip, rbd_capi_derivatives.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rbd_device.hpp"
@@ -119,4 +120,25 @@ hipError_t launch_big_pd_control(const BigModel& M, long B, const void* q, const
                                  void* tau_out, Layout Lq, Layout Lv, hipStream_t s);
 template <typename T>
 hipError_t launch_big_chol_solve(int nv, long B, const void* Mg, void* Lg, const void* rhs, const void* c, void* x, Layout Lm, Layout Lv, int* notpd, hipStream_t s);
+// rbd_tangent_kernels.hip, rbd_point_kernels.hip: the derivative kernels (arguments: rbd_tangent.hpp, rbd_tangent_mk.hpp, rbd_adjoint.hpp, rbd_adjoint_mk.hpp,
+// rbd_point.hpp — their callers include those)
+template <typename T> struct ColOut; template <typename T> struct TanArgs; template <typename T> struct MkTanArgs; template <typename T> struct AdjArgs;
+template <typename T> struct MkAdjArgs; template <typename T> struct PointArgs; template <typename T> struct PointAdjArgs; struct PointPlan;
+size_t tangent_scratch_elems_per_thread(const BigModel& M, int es);
+int tangent_chunk(int es);
+template <typename T> hipError_t launch_tangent_rnea(const BigModel& M, const TanArgs<T>& A, void* scratch, long max_threads, hipStream_t s);
+template <typename T>
+hipError_t launch_tangent_solve(int nv, long B, int c0, int ncol, const void* L, Layout Ll, const void* rhs, int identity, const ColOut<T>& out, void* xmem, hipStream_t s);
+template <typename T> hipError_t launch_symmetrize(int nv, long B, void* M, Layout Lm, hipStream_t s);
+template <typename T> hipError_t launch_tangent_mk_stage(const MkTanArgs<T>& A, hipStream_t s);
+size_t adjoint_scratch_elems_per_state(const BigModel& M);
+template <typename T> hipError_t launch_adjoint_rnea(const BigModel& M, const AdjArgs<T>& A, void* scratch, long max_states, hipStream_t s);
+template <typename T> hipError_t launch_stage_rows(int n, long B, const void* x, Layout L, void* out, hipStream_t s);
+template <typename T> hipError_t launch_point_kin(const BigModel& M, const PointPlan& P, const PointArgs<T>& A, hipStream_t s);  // rbd_point_kernels.hip
+template <typename T>
+hipError_t launch_point_adjoint(const BigModel& M, const PointPlan& P, const AdjArgs<T>& A, const PointAdjArgs<T>& C, void* scratch, long max_states, hipStream_t s);
+template <typename T> hipError_t launch_mk_stage_classes(MkAdjArgs<T> A, const int32_t* jn, int nn, const int32_t* jw, int nw, int adjoint, hipStream_t s);
+template <typename T>
+hipError_t launch_tangent_mk_load(long B, int ncol, int nq, int nv, int col0, int unit, const ColOut<T>& sq, const ColOut<T>& sv, const ColOut<T>& sd,
+                                  const ColOut<T>& dq, const ColOut<T>& dv, const ColOut<T>& dd, hipStream_t s);
 }

@@ -2,6 +2,7 @@
 // (coalesced across the batch in SOA, as tangent_mk_stage_kernel).  Everything a thread carries lives in registers: no scratch, no LDS.  The pullback's kernel
 // (point_adjoint_kernel) is with the adjoint pass it reuses, in rbd_tangent_kernels.hip.
 #include "rbd_point.hpp"
+#include "rbd_internal.hpp"
 
 namespace rbd {
 
