@@ -4,8 +4,8 @@
 // as two coordinates), every tree joint type, any tree size.
 //
 // Four sweeps over BigModel's tables (the reference's order, parents first):
-//   1. parents first: forward kinematics and newton_euler! values, K = (R, p, twist, acceleration) and the body wrench w per body (as tangent_rnea_state
-//      without tangents);
+//   1. parents first: forward kinematics and newton_euler! values, K = (R, p, twist, acceleration) and the body wrench w per body (the arithmetic of
+//      tree_kin_step, newton_euler_wrench and joint_torque of rbd_tree_step.hpp, written out here: calling them moved the fp32 kernel off the parent's time);
 //   2. children first: the subtree wrenches W_i = w_i + Σ W_child and τ_i = S_iᵀ W_i;
 //   3. parents first: W̄_i = S_i λ_i + W̄_parent (f̄ext_i = −W̄_i), and K̄_i from τ_i = ⟨S_i(K_i) λ_i, W_i⟩ and from newton_euler!;
 //   4. children first (K̄_i complete: the children have added theirs): the kinematic step pulled back to q̄_i, v̄_i, v̇̄_i and K̄_parent.
@@ -183,12 +183,7 @@ template <typename T, int N> RBD_HD void local_transform_pullback(int jt, const 
   }
 }
 
-// what the sweeps share: the world's entry (identity, at rest, a = −g) and a joint's coordinates of state `st` (zero past the joint's own, or without the buffer)
-template <typename T> RBD_HD void adj_root_k(const BigModel& M, T* pk) {
-#pragma unroll
-  for (int k = 0; k < 24; ++k) pk[k] = (k < 9 && k % 4 == 0) ? T(1) : T(0);
-  pk[21] = T(-M.gravity[0]); pk[22] = T(-M.gravity[1]); pk[23] = T(-M.gravity[2]);
-}
+// a joint's coordinates of state `st` (zero past the joint's own, or without the buffer)
 template <typename T> RBD_HD void adj_load_q(const AdjArgs<T>& A, long st, int qoff, int nqi, T* qj) {
 #pragma unroll
   for (int k = 0; k < 7; ++k) qj[k] = k < nqi ? A.q[(long)(qoff + k) * A.Lq.sk + layout_base(A.Lq, st)] : T(0);
@@ -219,7 +214,7 @@ template <typename T, typename At> RBD_HD void adjoint_kinematic_step(const BigM
 #pragma unroll
     for (int k = 0; k < 24; ++k) pk[k] = at(ADJ_K + k, b.parent);
   } else {
-    adj_root_k(M, pk);
+    tree_world_k(M, pk);
   }
 #pragma unroll
   for (int k = 0; k < 24; ++k) { K[k] = at(ADJ_K + k, i); Kb[k] = at(ADJ_KB + k, i); pkb[k] = T(0); }
@@ -282,10 +277,9 @@ template <typename T, typename At> RBD_HD void adjoint_kinematic_step(const BigM
 template <typename T> RBD_HD void adjoint_rnea_state(const BigModel& M, const AdjArgs<T>& A, long st, T* sc, long ld, long slot) {
   auto at = [&](int f, int i) -> T& { return sc[((long)f * M.nb + i) * ld + slot]; };
   const T* rbase = reinterpret_cast<const T*>(M.rb);
-  auto root_k = [&](T* pk) { adj_root_k(M, pk); };
   auto load_q = [&](int qoff, int nqi, T* qj) { adj_load_q(A, st, qoff, nqi, qj); };
   auto load_v = [&](const T* x, Layout L, int voff, int nvi, T* xj) { adj_load_v(x, L, st, voff, nvi, xj); };
-  // 1. forward kinematics and newton_euler! (as tangent_rnea_state)
+  // 1. forward kinematics and newton_euler! (as tree_kin_step and newton_euler_wrench)
   for (int i = 0; i < M.nb; ++i) {
     Body<T> b{};
     b.parent = M.tbl[4 * i]; b.jtype = M.tbl[4 * i + 1]; b.qoff = M.tbl[4 * i + 2]; b.voff = M.tbl[4 * i + 3];
@@ -304,7 +298,7 @@ template <typename T> RBD_HD void adjoint_rnea_state(const BigModel& M, const Ad
 #pragma unroll
       for (int k = 0; k < 24; ++k) pk[k] = at(ADJ_K + k, b.parent);
     } else {
-      root_k(pk);
+      tree_world_k(M, pk);
     }
     matmul3(pk, XR, K);
     matvec3(pk, Xp, K + 9);

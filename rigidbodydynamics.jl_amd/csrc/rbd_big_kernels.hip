@@ -5,7 +5,7 @@
 // with ONE THREAD PER STATE and the per-body quantities in an HBM scratch laid out [field][body][state] (coalesced across the wavefront).
 // Correct at any size, no speed claim: every per-body value makes a round trip through memory.  Bodies are visited in the reference's order
 // (parents before children).  Tree mechanisms, every tree joint type.
-#include "rbd_lane.hpp"
+#include "rbd_tree_step.hpp"
 #include "rbd_internal.hpp"
 
 namespace rbd {
@@ -20,40 +20,16 @@ template <typename T> struct BigCtx {
   RBD_DEV T& at(int field, int body) const { return sc[((long)field * M.nb + body) * B + st]; }
 };
 
-template <typename T> RBD_DEV Body<T> big_body(const BigModel& M, int i, long st) {
-  Body<T> b{};
-  b.parent = M.tbl[4 * i]; b.jtype = M.tbl[4 * i + 1]; b.qoff = M.tbl[4 * i + 2]; b.voff = M.tbl[4 * i + 3];
-  b.state = st; b.valid = true; b.orig = i;
-  return b;
-}
-
-// forward kinematics of body i from its parent's scratch entry (the world: identity, at rest, a = -g): K = (R, p, T, a); WITH_ACC adds the
-// joint acceleration X S_local v̇ (spatial_accelerations! :387-417)
+// forward kinematics of body i from its parent's scratch entry (the world's for a root body): tree_kin_step (rbd_tree_step.hpp) over this file's scratch
 template <typename T> RBD_DEV void big_fk(const BigCtx<T>& C, const Body<T>& b, const T* rb, const T* qj, const T* vj, const T* aj, T* K) {
-  T XR[9], Xp[3], tl[6], al[6], pk[24];
-  local_transform(b, rb, qj, XR, Xp);
-  local_joint_motion(b, rb, vj, tl);
-  local_joint_motion(b, rb, aj, al);
-  if (b.parent >= 0) {
+  tree_kin_step(b, rb, qj, vj, aj, [&](T* pk) {
+    if (b.parent >= 0) {
 #pragma unroll
-    for (int k = 0; k < 24; ++k) pk[k] = C.at(BIG_K + k, b.parent);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 24; ++k) pk[k] = (k < 9 && k % 4 == 0) ? T(1) : T(0);
-    pk[21] = T(-C.M.gravity[0]); pk[22] = T(-C.M.gravity[1]); pk[23] = T(-C.M.gravity[2]);
-  }
-  matmul3(pk, XR, K);
-  matvec3(pk, Xp, K + 9);
-#pragma unroll
-  for (int k = 0; k < 3; ++k) K[9 + k] += pk[9 + k];
-  T vJ[6], nT[6], cr[6], ajw[6];
-  xmotion(K, K + 9, tl, vJ);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) { K[12 + k] = pk[12 + k] + vJ[k]; nT[k] = -K[12 + k]; }
-  se3_comm(nT, pk + 12, cr);
-  xmotion(K, K + 9, al, ajw);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) K[18 + k] = pk[18 + k] + cr[k] + ajw[k];
+      for (int k = 0; k < 24; ++k) pk[k] = C.at(BIG_K + k, b.parent);
+    } else {
+      tree_world_k(C.M, pk);
+    }
+  }, K);
 }
 
 // inverse_dynamics! (vdot != nullptr) / dynamics_bias! (vdot == nullptr); acc_out / jw_out as in rnea_kernel
@@ -66,7 +42,7 @@ __global__ __launch_bounds__(64) void big_rnea_kernel(BigModel M, long B, const 
   const BigCtx<T> C{M, B, st, scratch};
   const T* rbase = reinterpret_cast<const T*>(M.rb);
   for (int i = 0; i < M.nb; ++i) {
-    const Body<T> b = big_body<T>(M, i, st);
+    const Body<T> b = tree_body<T>(M, i, st);
     const T* rb = rbase + (long)i * RB_STRIDE;
     T qj[7], vj[6], aj[6], K[24];
     load_joint_q(b, q, Lq, qj);
@@ -76,24 +52,17 @@ __global__ __launch_bounds__(64) void big_rnea_kernel(BigModel M, long B, const 
     big_fk(C, b, rb, qj, vj, aj, K);
 #pragma unroll
     for (int k = 0; k < 24; ++k) C.at(BIG_K + k, i) = K[k];
-    RInertia<T> I;
-    T Jb[6], mc[3], Ia[6], x[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) Jb[k] = rb[RB_J + k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) mc[k] = rb[RB_MC + k];
-    inertia_to_root(Jb, mc, rb[RB_M], K, K + 9, I);
-    mul_inertia(I, K + 18, Ia);
-    momentum_cross(I, K + 12, x);
+    T w[6];
+    newton_euler_wrench(rb, K, w);
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
       const T fe = fext ? fext[(long)(6 * i + k) * Lf.sk + st * Lf.sb] : T(0);
-      C.at(BIG_W + k, i) = Ia[k] + x[k] - fe;
+      C.at(BIG_W + k, i) = w[k] - fe;
       if (acc_out) acc_out[(long)(6 * i + k) * Lf.sk + st * Lf.sb] = K[18 + k];
     }
   }
   for (int i = M.nb - 1; i >= 0; --i) {  // joint_wrenches_and_torques! (:442-459)
-    const Body<T> b = big_body<T>(M, i, st);
+    const Body<T> b = tree_body<T>(M, i, st);
     const T* rb = rbase + (long)i * RB_STRIDE;
     T w[6], K[12];
 #pragma unroll
@@ -104,19 +73,8 @@ __global__ __launch_bounds__(64) void big_rnea_kernel(BigModel M, long B, const 
 #pragma unroll
       for (int k = 0; k < 6; ++k) jw_out[(long)(6 * i + k) * Lf.sk + st * Lf.sb] = w[k];
     }
-    T out[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
-    if (b.jtype == RBD_JOINT_QUAT_FLOATING) {
-      xforce_inv(K, K + 9, w, out);
-    } else {
-      const T ax[3] = {rb[RB_AXIS], rb[RB_AXIS + 1], rb[RB_AXIS + 2]}, ay[3] = {rb[RB_AXIS2], rb[RB_AXIS2 + 1], rb[RB_AXIS2 + 2]};
-      for (int k = 0; k < joint_nv(b.jtype); ++k) {
-        T sl[6], S[6];
-        subspace_col(b.jtype, ax, ay, k, sl);
-        xmotion(K, K + 9, sl, S);
-        const T d = dot6(S, w);
-        if (k == 0) out[0] = d; else if (k == 1) out[1] = d; else out[2] = d;
-      }
-    }
+    T out[6];
+    joint_torque(b.jtype, rb, K, w, out);
     store_joint_v(b, tau, Lv, out);
     if (b.parent >= 0) {
 #pragma unroll
@@ -138,7 +96,7 @@ __global__ __launch_bounds__(64) void big_crba_kernel(BigModel M, long B, const 
     for (int r = c2; r < nv; ++r) Mout[((long)c2 * nv + r) * Lm.sk + st * Lm.sb] = T(0);
   const T z6[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
   for (int i = 0; i < M.nb; ++i) {
-    const Body<T> b = big_body<T>(M, i, st);
+    const Body<T> b = tree_body<T>(M, i, st);
     const T* rb = rbase + (long)i * RB_STRIDE;
     T qj[7], K[24];
     load_joint_q(b, q, Lq, qj);
@@ -260,7 +218,7 @@ __global__ __launch_bounds__(64) void big_kin_kernel(BigModel M, long B, const T
 #pragma unroll
   for (int k = 0; k < 6; ++k) hs[k] = ws[k] = T(0);
   for (int i = 0; i < M.nb; ++i) {  // parents first: transforms, twists, bias accelerations (the world's -g inside), inertias in the root frame
-    const Body<T> b = big_body<T>(M, i, st);
+    const Body<T> b = tree_body<T>(M, i, st);
     const T* rb = rbase + (long)i * RB_STRIDE;
     T qj[7], vj[6], K[24];
     load_joint_q(b, q, Lq, qj);

@@ -110,7 +110,7 @@ template <typename T> TanArgs<T> tan_args(rbd_ws* w, int32_t B, int layout, int 
   A.Lq = layout_of(layout, m->nq, B); A.Lv = layout_of(layout, m->nv, B); A.Lf = layout_of(layout, 6L * m->nb, B);
   A.Ldq = layout_of(layout, (long)m->nq * ntan, B); A.Ldv = layout_of(layout, (long)m->nv * ntan, B); A.Ldf = layout_of(layout, 6L * m->nb * ntan, B);
   A.sign = T(1);
-  A.out = ColOut<T>{nullptr, Layout{0, 0}, nullptr, Layout{0, 0}, INT32_MAX, m->nv};
+  A.out = ColOut<T>::single(nullptr, Layout{0, 0}, m->nv);
   return A;
 }
 
@@ -156,7 +156,7 @@ int tan_dyn_jvp(rbd_ws* w, int32_t B, int32_t ntan, int layout, const void* q, c
   A.out.a = (T*)w->d_tan_rhs.p; A.out.La = Layout{B, 1};
   A.sign = T(-1); A.dadd = (const T*)dtau;
   HIP_TRY(launch_tangent_rnea<T>(w->tan, A, w->d_tan_scratch.p, w->tan_threads, w->stream));
-  const ColOut<T> out{(T*)dvdot_out, A.Ldv, nullptr, Layout{0, 0}, INT32_MAX, m->nv};
+  const ColOut<T> out = ColOut<T>::single((T*)dvdot_out, A.Ldv, m->nv);
   HIP_TRY(launch_tangent_solve<T>(m->nv, B, 0, ntan, w->d_tan_L.p, Layout{B, 1}, w->d_tan_rhs.p, 0, out, w->d_tan_x.p, w->stream));
   return RBD_OK;
 }
@@ -202,7 +202,7 @@ int tan_dyn_derivs(rbd_ws* w, int32_t B, int layout, const void* q, const void* 
     HIP_TRY(launch_tangent_solve<T>(m->nv, B, g0, g1 - g0, w->d_tan_L.p, Layout{B, 1}, w->d_tan_rhs.p, 0, out, w->d_tan_x.p, w->stream));
   }
   if (dvdot_dtau) {  // ∂v̇/∂τ = M⁻¹: the solve against the identity, generated in the kernel
-    const ColOut<T> out{(T*)dvdot_dtau, layout_of(layout, (long)m->nv * m->nv, B), nullptr, Layout{0, 0}, INT32_MAX, m->nv};
+    const ColOut<T> out = ColOut<T>::single((T*)dvdot_dtau, layout_of(layout, (long)m->nv * m->nv, B), m->nv);
     HIP_TRY(launch_tangent_solve<T>(m->nv, B, 0, m->nv, w->d_tan_L.p, Layout{B, 1}, nullptr, 1, out, w->d_tan_x.p, w->stream));
   }
   return RBD_OK;
@@ -255,8 +255,8 @@ int sim_tan_run(rbd_ws* w, int32_t B, int layout, void* q, void* v, const void* 
   const long tw = (long)W * Bm;
   T *dq0 = tb, *dv0 = dq0 + nq * tw, *dd0 = dv0 + nv * tw, *dqs = dd0 + nv * tw, *dvs = dqs + nq * tw, *dap = dvs + nv * tw, *dav = dap + nv * tw,
     *dvd = dav + nv * tw;
-  auto col = [&](T* p, int n) { return ColOut<T>{p, Li, nullptr, Layout{0, 0}, INT32_MAX, n}; };
-  auto user = [&](const void* p, Layout L, int n) { return ColOut<T>{(T*)p, L, nullptr, Layout{0, 0}, INT32_MAX, n}; };
+  auto col = [&](T* p, int n) { return ColOut<T>::single(p, Li, n); };
+  auto user = [&](const void* p, Layout L, int n) { return ColOut<T>::single((T*)p, L, n); };
   const int npass = (ndir + W - 1) / W;
   if (npass > 1) {
     HIP_TRY(hipMemcpyAsync(qi, q, es * nq * B, hipMemcpyDeviceToDevice, w->stream));
@@ -377,7 +377,7 @@ int adj_dyn_vjp(rbd_ws* w, int32_t B, int layout, const void* q, const void* v, 
     rhs = w->d_adj_rhs.p;
   }
   // λ straight into τ̄ when the caller asks for it (the adjoint pass reads it from there)
-  const ColOut<T> lam = tau_bar ? ColOut<T>{(T*)tau_bar, Lv, nullptr, Layout{0, 0}, INT32_MAX, m->nv} : ColOut<T>{(T*)w->d_adj_lam.p, Li, nullptr, Layout{0, 0}, INT32_MAX, m->nv};
+  const ColOut<T> lam = tau_bar ? ColOut<T>::single((T*)tau_bar, Lv, m->nv) : ColOut<T>::single((T*)w->d_adj_lam.p, Li, m->nv);
   HIP_TRY(launch_tangent_solve<T>(m->nv, B, 0, 1, w->d_tan_L.p, Li, rhs, 0, lam, w->d_adj_x.p, w->stream));
   if (!q_bar && !v_bar && !fext_bar) return RBD_OK;
   AdjArgs<T> A = adj_args<T>(w, B, layout, q, v, vd, fext);
@@ -600,7 +600,7 @@ int sav_backward_step(rbd_ws* w, int32_t B, int layout, const T* q0, const T* v0
     S.q0 = q0; S.qs = qs; S.vs = vs; S.accp = b.accp;
     S.qsb = (T*)q_bar; S.vsb = (T*)v_bar; S.q0b = b.q0b; S.v0b = b.v0b; S.vdb = b.vdb; S.apb = b.apb; S.avb = b.avb;
     HIP_TRY(launch_mk_stage_classes<T>(S, jl, w->sav_nn, jl + 3 * w->sav_nn, w->sav_nw, 1, w->stream));
-    const ColOut<T> lam{(T*)w->d_adj_lam.p, Li, nullptr, Layout{0, 0}, INT32_MAX, m->nv};
+    const ColOut<T> lam = ColOut<T>::single((T*)w->d_adj_lam.p, Li, m->nv);
     HIP_TRY(launch_tangent_solve<T>(m->nv, B, 0, 1, w->d_tan_L.p, Li, b.vdb, 0, lam, w->d_adj_x.p, w->stream));
     AdjArgs<T> A = adj_args<T>(w, B, layout, qs, vs, w->d_tan_vd.p, C ? w->d_tw.p : fext);
     A.lam = lam.a; A.Llam = Li;

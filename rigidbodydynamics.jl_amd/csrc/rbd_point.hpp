@@ -7,12 +7,12 @@
 // and the pullback of (pos, vel) to the RAW coordinates q (as rbd_adjoint.hpp defines them) and v.
 //
 // Forward (point_kin_state; kernel: rbd_point_kernels.hip point_kin_kernel): one thread per (point, state) walks the point's path root-first with
-// (R, p, twist, acceleration) in registers — the kinematic step of sweep 1 of adjoint_rnea_state —, and, when the Jacobian is asked for, walks it a second time
+// (R, p, twist, acceleration) in registers — point_body_step, the in-place form of tree_kin_step (rbd_tree_step.hpp) —, and, when the Jacobian is asked for, walks it a second time
 // recomputing (R, p) per body and writing the joint's columns.  No scratch, no LDS.  The routine is templated on the scalar, so that it also instantiates on
 // Dual<double, 1>: tests/test_point_kinematics_cpu.py takes J·d from that instantiation and checks the pullback against it.
 //
-// Reverse (point_adjoint_state; kernel: point_adjoint_kernel): one thread per state over the parents-first union of the paths.  Sweep A is the kinematic half of
-// sweep 1 (K = (R, p, twist) into the adjoint scratch) and seeds K̄ from the cotangents of the points on each body; sweep B is sweep 4 of adjoint_rnea_state
+// Reverse (point_adjoint_state; kernel: point_adjoint_kernel): one thread per state over the parents-first union of the paths.  Sweep A is tree_kin_step<false>
+// (K = (R, p, twist) into the adjoint scratch) and seeds K̄ from the cotangents of the points on each body; sweep B is sweep 4 of adjoint_rnea_state
 // (adjoint_kinematic_step), children first.
 #pragma once
 #include "rbd_adjoint.hpp"
@@ -96,7 +96,7 @@ RBD_HD void point_kin_state(const BigModel& M, const int32_t* path, int n, const
     }
   };
   S R[9], p[3], Tw[6], a[6];
-  auto world = [&]() {
+  auto world = [&]() {  // (as tree_world_k, without its −g: the accelerations here are relative to the world)
 #pragma unroll
     for (int k = 0; k < 9; ++k) R[k] = S(k % 4 == 0 ? T(1) : T(0));
 #pragma unroll
@@ -155,32 +155,22 @@ template <typename T> RBD_HD void point_adjoint_state(const BigModel& M, const P
     for (int k = 0; k < M.nq; ++k) A.qbar[(long)k * A.Lq.sk + layout_base(A.Lq, st)] = T(0);
   if (A.vbar && !A.accum)
     for (int k = 0; k < M.nv; ++k) A.vbar[(long)k * A.Lv.sk + layout_base(A.Lv, st)] = T(0);
-  // A. parents first: K = (R, p, twist) (the kinematic half of sweep 1 of adjoint_rnea_state), and K̄ seeded by the points on the body
+  // A. parents first: K = (R, p, twist) (tree_kin_step<false>, rbd_tree_step.hpp), and K̄ seeded by the points on the body
   for (int u = 0; u < P.nu; ++u) {
     const int i = P.uni[u];
-    Body<T> b{};
-    b.parent = M.tbl[4 * i]; b.jtype = M.tbl[4 * i + 1]; b.qoff = M.tbl[4 * i + 2]; b.voff = M.tbl[4 * i + 3];
+    const Body<T> b = tree_body<T>(M, i, st);
     const T* rb = rbase + (long)i * RB_STRIDE;
-    const int nqi = joint_nq<T>(b.jtype), nvi = joint_nv(b.jtype);
-    T qj[7], vj[6];
-    adj_load_q(A, st, b.qoff, nqi, qj);
-    adj_load_v(A.v, A.Lv, st, b.voff, nvi, vj);
-    T XR[9], Xp[3], tl[6], pk[24], K[18], vJ[6];
-    local_transform(b, rb, qj, XR, Xp);
-    local_joint_motion(b, rb, vj, tl);
-    if (b.parent >= 0) {
+    T qj[7], vj[6], K[18];
+    adj_load_q(A, st, b.qoff, joint_nq<T>(b.jtype), qj);
+    adj_load_v(A.v, A.Lv, st, b.voff, joint_nv(b.jtype), vj);
+    tree_kin_step<false>(b, rb, qj, vj, (const T*)nullptr, [&](T* pk) {
+      if (b.parent >= 0) {
 #pragma unroll
-      for (int k = 0; k < 18; ++k) pk[k] = at(ADJ_K + k, b.parent);
-    } else {
-      adj_root_k(M, pk);
-    }
-    matmul3(pk, XR, K);
-    matvec3(pk, Xp, K + 9);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) K[9 + k] += pk[9 + k];
-    xmotion(K, K + 9, tl, vJ);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) K[12 + k] = pk[12 + k] + vJ[k];
+        for (int k = 0; k < 18; ++k) pk[k] = at(ADJ_K + k, b.parent);
+      } else {
+        tree_world_k(M, pk);
+      }
+    }, K);
 #pragma unroll
     for (int k = 0; k < 18; ++k) at(ADJ_K + k, i) = K[k];
     T Kb[24];

@@ -11,7 +11,7 @@
 // out [field][component][body][thread] (coalesced across the wavefront, as in rbd_big_kernels.hip).  Bodies in the reference's order (parents first):
 // the tables are BigModel's, built for every tree mechanism.
 #pragma once
-#include "rbd_lane.hpp"
+#include "rbd_tree_step.hpp"
 
 namespace rbd {
 
@@ -87,6 +87,8 @@ template <typename T> struct ColOut {
   T* a; Layout La;
   T* b; Layout Lb;
   int split, n;
+  // every column to one buffer
+  static RBD_HD ColOut single(T* p, Layout L, int n) { return ColOut{p, L, nullptr, Layout{0, 0}, INT32_MAX, n}; }
   RBD_HD T* at(int col, int row, long st) const {
     if (col < split) return a ? a + ((long)col * n + row) * La.sk + layout_base(La, st) : nullptr;
     return b ? b + ((long)(col - split) * n + row) * Lb.sk + layout_base(Lb, st) : nullptr;
@@ -135,9 +137,7 @@ RBD_HD void tangent_rnea_state(const BigModel& M, const TanArgs<T>& A, long st, 
   };
   auto unit_hit = [&](int g, int j) -> T { return (A.unit && e0 + j < A.ntan && A.g0 + e0 + j == g) ? T(1) : T(0); };
   for (int i = 0; i < M.nb; ++i) {
-    Body<D> b{};
-    b.parent = M.tbl[4 * i]; b.jtype = M.tbl[4 * i + 1]; b.qoff = M.tbl[4 * i + 2]; b.voff = M.tbl[4 * i + 3];
-    b.state = st; b.valid = true; b.orig = i;
+    const Body<D> b = tree_body<D>(M, i, st);
     const T* rbt = rbase + (long)i * RB_STRIDE;
     D rb[RB_STRIDE];
 #pragma unroll
@@ -161,45 +161,25 @@ RBD_HD void tangent_rnea_state(const BigModel& M, const TanArgs<T>& A, long st, 
         aj[k].d[j] = (in && !A.unit) ? tan_in(A.dvdot, A.Ldv, M.nv, b.voff + k, j) : T(0);
       }
     }
-    // forward kinematics from the parent's entry (the world: identity, at rest, a = -g), as big_fk
-    D XR[9], Xp[3], tl[6], al[6], pk[24], K[24];
-    local_transform(b, rb, qj, XR, Xp);
-    local_joint_motion(b, rb, vj, tl);
-    local_joint_motion(b, rb, aj, al);
-    if (b.parent >= 0) {
+    // forward kinematics from the parent's entry (tree_kin_step, rbd_tree_step.hpp)
+    D K[24], w[6];
+    tree_kin_step(b, rb, qj, vj, aj, [&](D* pk) {
+      if (b.parent >= 0) {
 #pragma unroll
-      for (int k = 0; k < 24; ++k) pk[k] = get(TAN_K + k, b.parent);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 24; ++k) pk[k] = D((k < 9 && k % 4 == 0) ? T(1) : T(0));
-      pk[21] = D(T(-M.gravity[0])); pk[22] = D(T(-M.gravity[1])); pk[23] = D(T(-M.gravity[2]));
-    }
-    matmul3(pk, XR, K);
-    matvec3(pk, Xp, K + 9);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) K[9 + k] += pk[9 + k];
-    D vJ[6], nT[6], cr[6], ajw[6];
-    xmotion(K, K + 9, tl, vJ);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) { K[12 + k] = pk[12 + k] + vJ[k]; nT[k] = -K[12 + k]; }
-    se3_comm(nT, pk + 12, cr);
-    xmotion(K, K + 9, al, ajw);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) K[18 + k] = pk[18 + k] + cr[k] + ajw[k];
+        for (int k = 0; k < 24; ++k) pk[k] = get(TAN_K + k, b.parent);
+      } else {
+        tree_world_k(M, pk);
+      }
+    }, K);
 #pragma unroll
     for (int k = 0; k < 24; ++k) put(TAN_K + k, i, K[k]);
-    // newton_euler!: I a + T ×* I T − f_ext in the root frame
-    RInertia<D> I;
-    D Ia[6], x[6];
-    inertia_to_root(rb + RB_J, rb + RB_MC, rb[RB_M], K, K + 9, I);
-    mul_inertia(I, K + 18, Ia);
-    momentum_cross(I, K + 12, x);
+    newton_euler_wrench(rb, K, w);  // − f_ext below
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
       D fe = D(A.fext ? A.fext[(long)(6 * i + k) * A.Lf.sk + layout_base(A.Lf, st)] : T(0));
 #pragma unroll
       for (int j = 0; j < N; ++j) fe.d[j] = A.unit ? T(0) : tan_in(A.dfext, A.Ldf, 6 * M.nb, 6 * i + k, j);
-      put(TAN_W + k, i, Ia[k] + x[k] - fe);
+      put(TAN_W + k, i, w[k] - fe);
     }
   }
   for (int i = M.nb - 1; i >= 0; --i) {  // joint_wrenches_and_torques!: τ = Sᵀ w, w added to the parent's
@@ -210,19 +190,8 @@ RBD_HD void tangent_rnea_state(const BigModel& M, const TanArgs<T>& A, long st, 
     for (int k = 0; k < 6; ++k) w[k] = get(TAN_W + k, i);
 #pragma unroll
     for (int k = 0; k < 12; ++k) K[k] = get(TAN_K + k, i);
-    D out[6] = {D(T(0)), D(T(0)), D(T(0)), D(T(0)), D(T(0)), D(T(0))};
-    if (jt == RBD_JOINT_QUAT_FLOATING) {
-      xforce_inv(K, K + 9, w, out);
-    } else {
-      const D ax[3] = {D(rbt[RB_AXIS]), D(rbt[RB_AXIS + 1]), D(rbt[RB_AXIS + 2])}, ay[3] = {D(rbt[RB_AXIS2]), D(rbt[RB_AXIS2 + 1]), D(rbt[RB_AXIS2 + 2])};
-      for (int k = 0; k < joint_nv(jt); ++k) {
-        D sl[6], S[6];
-        subspace_col(jt, ax, ay, k, sl);
-        xmotion(K, K + 9, sl, S);
-        const D dd = dot6(S, w);
-        if (k == 0) out[0] = dd; else if (k == 1) out[1] = dd; else out[2] = dd;
-      }
-    }
+    D out[6];
+    joint_torque(jt, rbt, K, w, out);
     const int nvi = joint_nv(jt);
     for (int k = 0; k < nvi; ++k) {
       if (A.tau && chunk == 0) A.tau[(long)(voff + k) * A.Lv.sk + layout_base(A.Lv, st)] = out[k].v;

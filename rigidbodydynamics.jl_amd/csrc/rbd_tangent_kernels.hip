@@ -24,6 +24,16 @@ size_t tangent_scratch_elems_per_thread(const BigModel& M, int es) {
 }
 int tangent_chunk(int es) { return es == 8 ? (int)TanChunk<double>::N : (int)TanChunk<float>::N; }
 
+// `total` threads in slabs of the scratch's size (at most `max` each): launch(first, count) per slab
+template <typename F> hipError_t launch_slabs(long total, long max, F launch) {
+  for (long i0 = 0; i0 < total; i0 += max) {
+    launch(i0, total - i0 < max ? total - i0 : max);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 // threads t0 … t0 + nt − 1 of the B · nchunks (state, chunk) pairs; the scratch holds nt threads
 template <typename T, int N>
 __global__ __launch_bounds__(64) void tangent_rnea_kernel(BigModel M, TanArgs<T> A, long t0, long nt, T* __restrict__ scratch) {
@@ -38,14 +48,10 @@ __global__ __launch_bounds__(64) void tangent_rnea_kernel(BigModel M, TanArgs<T>
 template <typename T>
 hipError_t launch_tangent_rnea(const BigModel& M, const TanArgs<T>& A, void* scratch, long max_threads, hipStream_t s) {
   constexpr int N = TanChunk<T>::N;
-  const long nchunks = (A.ntan + N - 1) / N, total = nchunks * A.B;
-  for (long t0 = 0; t0 < total; t0 += max_threads) {  // slabs of the scratch's size
-    const long nt = total - t0 < max_threads ? total - t0 : max_threads;
+  const long nchunks = (A.ntan + N - 1) / N;
+  return launch_slabs(nchunks * A.B, max_threads, [&](long t0, long nt) {
     hipLaunchKernelGGL((tangent_rnea_kernel<T, N>), dim3((unsigned)((nt + 63) / 64)), dim3(64), 0, s, M, A, t0, nt, (T*)scratch);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
 // columns c0 … c0 + ncol − 1 of every state, thread = (c − c0) · B + state: x = M⁻¹ rhs_c (identity: e_c) with the factor L (layout Ll)
@@ -205,13 +211,9 @@ __global__ __launch_bounds__(64) void adjoint_rnea_kernel(BigModel M, AdjArgs<T>
 }
 
 template <typename T> hipError_t launch_adjoint_rnea(const BigModel& M, const AdjArgs<T>& A, void* scratch, long max_states, hipStream_t s) {
-  for (long s0 = 0; s0 < A.B; s0 += max_states) {  // slabs of the scratch's size
-    const long ns = A.B - s0 < max_states ? A.B - s0 : max_states;
+  return launch_slabs(A.B, max_states, [&](long s0, long ns) {
     hipLaunchKernelGGL((adjoint_rnea_kernel<T>), dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, s, M, A, s0, ns, (T*)scratch);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
 // the pullback of rbd_point_kinematics (rbd_point.hpp point_adjoint_state): one thread per state over the union of the points' paths, the same scratch and slabs
@@ -224,13 +226,9 @@ __global__ __launch_bounds__(64) void point_adjoint_kernel(BigModel M, PointPlan
 
 template <typename T>
 hipError_t launch_point_adjoint(const BigModel& M, const PointPlan& P, const AdjArgs<T>& A, const PointAdjArgs<T>& C, void* scratch, long max_states, hipStream_t s) {
-  for (long s0 = 0; s0 < A.B; s0 += max_states) {
-    const long ns = A.B - s0 < max_states ? A.B - s0 : max_states;
+  return launch_slabs(A.B, max_states, [&](long s0, long ns) {
     hipLaunchKernelGGL((point_adjoint_kernel<T>), dim3((unsigned)((ns + 63) / 64)), dim3(64), 0, s, M, P, A, C, s0, ns, (T*)scratch);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  });
 }
 
 // an n × B batch buffer of layout L copied batch-innermost (row r of state b at r B + b: the right-hand side tri_solve_col reads)

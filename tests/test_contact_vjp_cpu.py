@@ -3,21 +3,16 @@ model and its hand-written pullback (csrc/rbd_contact.hpp contact_pair_force, co
 tests/test_point_kinematics_cpu.py does, against exact references — the torch fp64 model of tests/contact_model_ref.py (itself pinned to the oracle's
 contact_dynamics!), torch.autograd of it, and J·d from the Dual<double, 1> instantiation of the forward routine.  No difference quotients."""
 import ctypes
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 import torch
 
 import contact_model_ref as cm
+from host_harness import CLANG, ROOT, build
 from point_kinematics_ref import reference
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rigidbodydynamics.jl_amd", "csrc")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 NEW = ("rbd_contact_dynamics_vjp", "rbd_dynamics_contact_vjp")
 N = 2000
 
@@ -53,21 +48,10 @@ extern "C" void emu_pair_jvp(long n, const double* pos, const double* vel, const
   }
 }
 """
-HEADERS = ("rbd_contact.hpp", "rbd_point.hpp", "rbd_adjoint.hpp", "rbd_tangent.hpp", "rbd_lane.hpp", "rbd_device.hpp")
 
 
 def build_harness():
-    key = hashlib.sha256((HARNESS + "".join(open(os.path.join(CSRC, f)).read() for f in HEADERS)).encode()).hexdigest()[:16]
-    d = os.path.join(tempfile.gettempdir(), "rbd_contact_emu")
-    os.makedirs(d, exist_ok=True)
-    so = os.path.join(d, "emu_%s.so" % key)
-    if not os.path.exists(so):
-        src = os.path.join(d, "emu_%s.cpp" % key)
-        open(src, "w").write(HARNESS)
-        subprocess.check_call([CLANG, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=fast", "-Wno-everything",
-                               "-I", os.path.join(ROOT, "tests", "emu", "spec_shim"), "-I", CSRC, "-I", os.path.join(ROOT, "include"), src, "-o", so + ".tmp"])
-        os.replace(so + ".tmp", so)
-    return ctypes.CDLL(so)
+    return build(HARNESS, "rbd_contact_emu")
 
 
 @pytest.fixture(scope="module")

@@ -3,17 +3,13 @@ routine of the derivative kernels (csrc/rbd_tangent.hpp tangent_rnea_state), com
 directional derivative of the quad-precision oracle (oracle.jvp: exact to double rounding) at the project's fp64 parity number 1e-10 — every joint type, random
 directions, quaternion directions off the unit sphere included."""
 import ctypes
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rigidbodydynamics.jl_amd", "csrc")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+from host_harness import CLANG, ROOT, build
+
 NEW = ("rbd_inverse_dynamics_jvp", "rbd_dynamics_jvp", "rbd_inverse_dynamics_derivatives", "rbd_dynamics_derivatives")
 
 HARNESS = r"""
@@ -32,7 +28,7 @@ extern "C" void emu_tangent_rnea(int nb, int nq, int nv, const int* tbl, const d
   A.Lq = rbd::Layout{1, nq}; A.Lv = rbd::Layout{1, nv}; A.Lf = rbd::Layout{1, 6L * nb};
   A.Ldq = rbd::Layout{1, (long)nq * ntan}; A.Ldv = rbd::Layout{1, (long)nv * ntan}; A.Ldf = rbd::Layout{1, 6L * nb * ntan};
   A.tau = tau; A.sign = 1.0; A.dadd = nullptr;
-  A.out = rbd::ColOut<double>{dtau, A.Ldv, nullptr, rbd::Layout{0, 0}, 1 << 30, nv};
+  A.out = rbd::ColOut<double>::single(dtau, A.Ldv, nv);
   double* sc = new double[(size_t)rbd::TAN_FIELDS * (N + 1) * nb];
   for (int c = 0; c < (ntan + N - 1) / N; ++c)
     for (long st = 0; st < B; ++st) rbd::tangent_rnea_state<double, N>(M, A, st, c, sc, 1, 0);
@@ -42,18 +38,7 @@ extern "C" void emu_tangent_rnea(int nb, int nq, int nv, const int* tbl, const d
 
 
 def build_harness():
-    text = HARNESS
-    key = hashlib.sha256((text + "".join(open(os.path.join(CSRC, f)).read() for f in ("rbd_tangent.hpp", "rbd_lane.hpp", "rbd_device.hpp"))).encode()).hexdigest()[:16]
-    d = os.path.join(tempfile.gettempdir(), "rbd_tangent_emu")
-    os.makedirs(d, exist_ok=True)
-    so = os.path.join(d, "emu_%s.so" % key)
-    if not os.path.exists(so):
-        src = os.path.join(d, "emu_%s.cpp" % key)
-        open(src, "w").write(text)
-        subprocess.check_call([CLANG, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=fast", "-Wno-everything",
-                               "-I", os.path.join(ROOT, "tests", "emu", "spec_shim"), "-I", CSRC, "-I", os.path.join(ROOT, "include"), src, "-o", so + ".tmp"])
-        os.replace(so + ".tmp", so)
-    return ctypes.CDLL(so)
+    return build(HARNESS, "rbd_tangent_emu")
 
 
 def tables(flat):

@@ -4,20 +4,15 @@ compiled as plain C++ for the host as tests/test_vjp_cpu.py does, against the nu
 from the Dual<double, 1> instantiation of the forward routine; that instantiation against a 4-point central difference of the reference in raw q; and the path
 and union tables of rbd_workspace_set_points (csrc/rbd_point_plan.hpp)."""
 import ctypes
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+from host_harness import CLANG, ROOT, build
 from point_kinematics_ref import off_path, pick_points, pos_vel_fd, reference
 from test_derivatives_cpu import tables
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rigidbodydynamics.jl_amd", "csrc")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 NEW = ("rbd_workspace_set_points", "rbd_point_kinematics", "rbd_point_kinematics_vjp")
 MODELS = ["randmech1", "randmech2", "randmech3", "inner_floating", "mixed20", "double_pendulum"]
 
@@ -82,21 +77,10 @@ extern "C" void emu_point_vjp(int nb, int nq, int nv, const int* tbl, const doub
   delete[] sc;
 }
 """
-HEADERS = ("rbd_point.hpp", "rbd_point_plan.hpp", "rbd_adjoint.hpp", "rbd_tangent.hpp", "rbd_lane.hpp", "rbd_device.hpp")
 
 
 def build_harness():
-    key = hashlib.sha256((HARNESS + "".join(open(os.path.join(CSRC, f)).read() for f in HEADERS)).encode()).hexdigest()[:16]
-    d = os.path.join(tempfile.gettempdir(), "rbd_point_emu")
-    os.makedirs(d, exist_ok=True)
-    so = os.path.join(d, "emu_%s.so" % key)
-    if not os.path.exists(so):
-        src = os.path.join(d, "emu_%s.cpp" % key)
-        open(src, "w").write(HARNESS)
-        subprocess.check_call([CLANG, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=fast", "-Wno-everything",
-                               "-I", os.path.join(ROOT, "tests", "emu", "spec_shim"), "-I", CSRC, "-I", os.path.join(ROOT, "include"), src, "-o", so + ".tmp"])
-        os.replace(so + ".tmp", so)
-    return ctypes.CDLL(so)
+    return build(HARNESS, "rbd_point_emu")
 
 
 @pytest.fixture(scope="module")

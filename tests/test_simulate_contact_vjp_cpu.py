@@ -4,10 +4,7 @@ host as tests/test_contact_vjp_cpu.py does, against J·d of the value form's Dua
 through a whole RK4 step; and the torch step of tests/simulate_contact_ref.py, the reference of the GPU tests, against oracle/simulate_np.py.  No difference
 quotients."""
 import ctypes
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -15,7 +12,8 @@ import torch
 
 import contact_model_ref as cm
 import simulate_contact_ref as sr
-from test_contact_vjp_cpu import CLANG, CSRC, HEADERS, N, ROOT, _p, random_pairs
+from host_harness import CLANG, ROOT, build
+from test_contact_vjp_cpu import N, _p, random_pairs
 
 NEW = ("rbd_simulate_contact_vjp",)
 DT = 1e-3
@@ -93,17 +91,7 @@ extern "C" void emu_step_adjoint(long n, double dt, const double* pos, const dou
 
 
 def build_harness():
-    key = hashlib.sha256((HARNESS + "".join(open(os.path.join(CSRC, f)).read() for f in HEADERS)).encode()).hexdigest()[:16]
-    d = os.path.join(tempfile.gettempdir(), "rbd_simulate_contact_emu")
-    os.makedirs(d, exist_ok=True)
-    so = os.path.join(d, "emu_%s.so" % key)
-    if not os.path.exists(so):
-        src = os.path.join(d, "emu_%s.cpp" % key)
-        open(src, "w").write(HARNESS)
-        subprocess.check_call([CLANG, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=fast", "-Wno-everything",
-                               "-I", os.path.join(ROOT, "tests", "emu", "spec_shim"), "-I", CSRC, "-I", os.path.join(ROOT, "include"), src, "-o", so + ".tmp"])
-        os.replace(so + ".tmp", so)
-    return ctypes.CDLL(so)
+    return build(HARNESS, "rbd_simulate_contact_emu")
 
 
 @pytest.fixture(scope="module")

@@ -4,18 +4,14 @@ tests/test_derivatives_cpu.py does, matches a 4th-order central difference of or
 quaternion directions off the unit sphere, and the points where the reference branches: q = q0, ϕ_rot = 0 with ϕ_trans ≠ 0, θ on either side of eps and of
 the Bortz series threshold.  Every output must be finite."""
 import ctypes
-import hashlib
 import os
-import subprocess
-import tempfile
 import types
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rigidbodydynamics.jl_amd", "csrc")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+from host_harness import CLANG, ROOT, build
+
 NEW = ("rbd_simulate_jvp", "rbd_simulate_step_derivatives")
 
 HARNESS = r"""
@@ -57,18 +53,7 @@ EPS64 = np.finfo(np.float64).eps
 
 
 def build_harness():
-    key = hashlib.sha256((HARNESS + "".join(open(os.path.join(CSRC, f)).read() for f in ("rbd_tangent_mk.hpp", "rbd_tangent.hpp", "rbd_lane.hpp",
-                                                                                          "rbd_device.hpp"))).encode()).hexdigest()[:16]
-    d = os.path.join(tempfile.gettempdir(), "rbd_tangent_mk_emu")
-    os.makedirs(d, exist_ok=True)
-    so = os.path.join(d, "emu_%s.so" % key)
-    if not os.path.exists(so):
-        src = os.path.join(d, "emu_%s.cpp" % key)
-        open(src, "w").write(HARNESS)
-        subprocess.check_call([CLANG, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=fast", "-Wno-everything",
-                               "-I", os.path.join(ROOT, "tests", "emu", "spec_shim"), "-I", CSRC, "-I", os.path.join(ROOT, "include"), src, "-o", so + ".tmp"])
-        os.replace(so + ".tmp", so)
-    return ctypes.CDLL(so)
+    return build(HARNESS, "rbd_tangent_mk_emu")
 
 
 @pytest.fixture(scope="module")

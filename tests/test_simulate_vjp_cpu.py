@@ -5,17 +5,12 @@ directions (quaternion directions off the unit sphere), at the points where the 
 of eps and of the series threshold), in fp64 and fp32, for both kernel instantiations (the 1-coordinate class without Duals, and the generic one).  The
 pullback ADDS to the inputs' cotangents, and the value stage map of the reverse pass computes tan_mk_stage_joint's values.  Every output must be finite."""
 import ctypes
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rigidbodydynamics.jl_amd", "csrc")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+from host_harness import CLANG, ROOT, build
 
 # inputs x (44): q0 7, v0 6, qs 7, vs 6, v̇ 6, the sums in 6 + 6; outputs y (25): q_n 7, v_n 6, the sums out 6 + 6 (each block zero past the joint's size)
 HARNESS = r"""
@@ -75,18 +70,7 @@ Y_BLOCKS = [(0, "q"), (7, "v"), (13, "v"), (19, "v")]
 
 
 def build_harness():
-    key = hashlib.sha256((HARNESS + "".join(open(os.path.join(CSRC, f)).read() for f in ("rbd_adjoint_mk.hpp", "rbd_tangent_mk.hpp", "rbd_tangent.hpp",
-                                                                                          "rbd_lane.hpp", "rbd_device.hpp"))).encode()).hexdigest()[:16]
-    d = os.path.join(tempfile.gettempdir(), "rbd_adjoint_mk_emu")
-    os.makedirs(d, exist_ok=True)
-    so = os.path.join(d, "emu_%s.so" % key)
-    if not os.path.exists(so):
-        src = os.path.join(d, "emu_%s.cpp" % key)
-        open(src, "w").write(HARNESS)
-        subprocess.check_call([CLANG, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=fast", "-Wno-everything",
-                               "-I", os.path.join(ROOT, "tests", "emu", "spec_shim"), "-I", CSRC, "-I", os.path.join(ROOT, "include"), src, "-o", so + ".tmp"])
-        os.replace(so + ".tmp", so)
-    return ctypes.CDLL(so)
+    return build(HARNESS, "rbd_adjoint_mk_emu")
 
 
 @pytest.fixture(scope="module")

@@ -4,19 +4,14 @@ tangent routine (csrc/rbd_tangent.hpp tangent_rnea_state), is exactly its transp
 (q, v, v̇, f_ext), quaternion directions off the unit sphere included.  q̄, v̄, v̇̄ are also checked against Jᵀλ from the quad-precision oracle's Jacobians
 (oracle.jacobians), f̄ext against its derivative along every wrench coordinate, and v̇̄ against Mλ."""
 import ctypes
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+from host_harness import CLANG, ROOT, build
 from test_derivatives_cpu import tables
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rigidbodydynamics.jl_amd", "csrc")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 NEW = ("rbd_inverse_dynamics_vjp", "rbd_dynamics_vjp")
 MODELS = ["randmech1", "randmech2", "randmech3", "inner_floating", "mixed20", "double_pendulum"]
 
@@ -35,7 +30,7 @@ extern "C" void emu_tangent_rnea(int nb, int nq, int nv, const int* tbl, const d
   A.B = B; A.ntan = 1; A.q = q; A.v = v; A.vdot = vdot; A.fext = fext; A.dq = dq; A.dv = dv; A.dvdot = dvdot; A.dfext = dfext;
   A.Lq = A.Ldq = rbd::Layout{1, nq}; A.Lv = A.Ldv = rbd::Layout{1, nv}; A.Lf = A.Ldf = rbd::Layout{1, 6L * nb};
   A.tau = nullptr; A.sign = 1.0; A.dadd = nullptr;
-  A.out = rbd::ColOut<double>{dtau, A.Ldv, nullptr, rbd::Layout{0, 0}, 1 << 30, nv};
+  A.out = rbd::ColOut<double>::single(dtau, A.Ldv, nv);
   double* sc = new double[(size_t)rbd::TAN_FIELDS * (N + 1) * nb];
   for (long st = 0; st < B; ++st) rbd::tangent_rnea_state<double, N>(M, A, st, 0, sc, 1, 0);
   delete[] sc;
@@ -56,18 +51,7 @@ extern "C" void emu_adjoint_rnea(int nb, int nq, int nv, const int* tbl, const d
 
 
 def build_harness():
-    key = hashlib.sha256((HARNESS + "".join(open(os.path.join(CSRC, f)).read() for f in ("rbd_adjoint.hpp", "rbd_tangent.hpp", "rbd_lane.hpp",
-                                                                                           "rbd_device.hpp"))).encode()).hexdigest()[:16]
-    d = os.path.join(tempfile.gettempdir(), "rbd_adjoint_emu")
-    os.makedirs(d, exist_ok=True)
-    so = os.path.join(d, "emu_%s.so" % key)
-    if not os.path.exists(so):
-        src = os.path.join(d, "emu_%s.cpp" % key)
-        open(src, "w").write(HARNESS)
-        subprocess.check_call([CLANG, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-ffp-contract=fast", "-Wno-everything",
-                               "-I", os.path.join(ROOT, "tests", "emu", "spec_shim"), "-I", CSRC, "-I", os.path.join(ROOT, "include"), src, "-o", so + ".tmp"])
-        os.replace(so + ".tmp", so)
-    return ctypes.CDLL(so)
+    return build(HARNESS, "rbd_adjoint_emu")
 
 
 def _c(a):
