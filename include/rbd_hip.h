@@ -535,6 +535,45 @@ int rbd_dynamics_contact_vjp(rbd_ws_t* ws, int32_t B, const void* q, const void*
 int rbd_simulate_contact_vjp(rbd_ws_t* ws, int32_t B, void* q, void* v, void* s, const void* tau, const void* fext, double dt, int32_t nsteps,
                              void* q_bar, void* v_bar, void* s_bar, void* tau_bar, void* fext_bar, const rbd_opts_t* opts);
 
+/* Forward mode through soft contact (700 addition): the tangents and Jacobians of rbd_contact_dynamics and of rbd_dynamics_contact for a mechanism with
+ * contact points and an environment — what ForwardDiff computes through dynamics! of such a mechanism.  One pass: the tangent RNEA of rbd_dynamics_jvp
+ * carries every body's (R, p, twist) with its tangents; between its two sweeps each (state, chunk of directions) thread forms every contact point's Dual
+ * position, velocity and friction state, evaluates the pair model on them and subtracts the tangent of the point's wrench from its body's; the existing
+ * multi-right-hand-side solve finishes dv̇.  No second walk over the tree, no per-direction wrench buffer.
+ *  - Tangents as rbd_dynamics_jvp: ntan directions, direction d of a tangent of n coordinates at rows d·n … d·n+n−1 of the state's ntan·n; every tangent
+ *    input nullable (a zero direction), every output nullable and OVERWRITTEN; ds, dsdot_out, ds_out_out have n = ns = 3·points·half-spaces; raw coordinates q.
+ *  - Contact model as rbd_dynamics_contact_vjp: the derivative of the branch each (point, half-space) pair takes — outside, clamped, sticking, slipping —, an
+ *    outside pair contributing exact zeros; the tangent of s after the resets is ds for inside pairs and 0 for outside pairs; s is const and not reset; on a
+ *    branch boundary the result is that of the branch taken.
+ *  - Values: vdot_out (nv), sdot_out (ns), nullable, equal rbd_dynamics_contact_vjp's to rounding (the forward contact launch, then CRBA + Cholesky at the
+ *    total wrenches).
+ *  - Errors: a mechanism without contact points or without an environment, ntan <= 0, a NULL q, v or s: RBD_ERR_INVALID_ARGUMENT; loop joints:
+ *    RBD_ERR_HAS_LOOPS; RBD_MEM_HOST: RBD_ERR_UNSUPPORTED; B beyond the workspace's batch: RBD_ERR_DIMENSION_MISMATCH; B == 0 is a successful no-op.
+ *  - fp32 and fp64, both layouts, trees of any size, every tree joint type.  The first call of a workspace allocates (what the forward- and reverse-mode
+ *    contact calls share, the right-hand sides for max(ntan, nq + nv + ns) directions); a JVP call with more directions than any before allocates again;
+ *    nothing else allocates or synchronises.  rbd_workspace_last_kernel names tangent_contact_rnea_kernel afterwards, among the others.
+ * rbd_contact_dynamics_jvp — tangent of contact_dynamics!: (dq, dv, ds) -> (dcw [6·n_bodies·ntan], dsdot [ns·ntan], ds_out [ns·ntan]); the tangent pass
+ * stops after the contact step (no wrench sweep). */
+int rbd_contact_dynamics_jvp(rbd_ws_t* ws, int32_t B, int32_t ntan, const void* q, const void* v, const void* s,
+                             const void* dq, const void* dv, const void* ds,
+                             void* dcw_out, void* dsdot_out, void* ds_out_out, const rbd_opts_t* opts);
+/* rbd_dynamics_contact_jvp — tangent of dynamics!(result, state, τ, wext) with contact points, the ODE form (q, v, s, τ, wext) -> (v̇, ṡ, s after the
+ * resets): M dv̇ = dτ − ∂ID(q, v, v̇)·(dq, dv, 0, dfext + d contactwrenches); dvdot_out (nv·ntan), dsdot_out, ds_out_out (ns·ntan).  Without dvdot_out there
+ * is no wrench sweep and no solve. */
+int rbd_dynamics_contact_jvp(rbd_ws_t* ws, int32_t B, int32_t ntan, const void* q, const void* v, const void* s,
+                             const void* tau, const void* fext,
+                             const void* dq, const void* dv, const void* ds, const void* dtau, const void* dfext,
+                             void* vdot_out, void* sdot_out, void* dvdot_out, void* dsdot_out, void* ds_out_out,
+                             const rbd_opts_t* opts);
+/* rbd_dynamics_contact_derivatives — the full Jacobians, column-major per state like rbd_dynamics_derivatives, fext held fixed: dvdot_dq nv×nq, dvdot_dv
+ * nv×nv, dvdot_ds nv×ns, dvdot_dtau nv×nv = M⁻¹ (the full square); dsdot_dq ns×nq, dsdot_dv ns×nv, dsdot_ds ns×ns (ṡ does not depend on τ).  Column j is
+ * the JVP along the j-th unit vector of (q; v; s): the columns of (q; v) in one tangent pass, those of s in a second.  Every output nullable; a pass none
+ * of whose outputs is asked for is not launched. */
+int rbd_dynamics_contact_derivatives(rbd_ws_t* ws, int32_t B, const void* q, const void* v, const void* s,
+                                     const void* tau, const void* fext, void* vdot_out, void* sdot_out,
+                                     void* dvdot_dq, void* dvdot_dv, void* dvdot_ds, void* dvdot_dtau,
+                                     void* dsdot_dq, void* dsdot_dv, void* dsdot_ds, const rbd_opts_t* opts);
+
 /* ---- diagnostics ------------------------------------------------------------ */
 const char* rbd_status_string(int status);
 const char* rbd_last_hip_error(void);   /* thread-local text of the last HIP failure     */
@@ -553,7 +592,8 @@ const char* rbd_workspace_last_kernel(const rbd_ws_t* ws);
  *      rbd_inverse_dynamics_vjp, rbd_dynamics_vjp (reverse mode); rbd_simulate_vjp (reverse mode through simulate steps);
  *      rbd_workspace_set_points, rbd_point_kinematics, rbd_point_kinematics_vjp (point kinematics);
  *      rbd_contact_dynamics_vjp, rbd_dynamics_contact_vjp (reverse mode through soft contact);
- *      rbd_simulate_contact_vjp (reverse mode through simulate steps with soft contact). */
+ *      rbd_simulate_contact_vjp (reverse mode through simulate steps with soft contact);
+ *      rbd_contact_dynamics_jvp, rbd_dynamics_contact_jvp, rbd_dynamics_contact_derivatives (forward mode through soft contact). */
 #define RBD_HIP_H_VERSION 700
 int rbd_version(void);
 /* Run-time specialisation.  The one-lane-per-state kernels (mass_matrix! and mass_matrix! + Cholesky at large batches) exist in a second form

@@ -31,7 +31,7 @@ using LinearAlgebra
 export BatchedMechanismState, BatchedDynamicsResult, DeviceMatrix, RbdComm, gather!, gatherv!, mass_matrix_solve_packed!, synchronize, librbd_hip, TorqueTable, PDControl,
     inverse_dynamics_jvp!, dynamics_jvp!, inverse_dynamics_derivatives!, dynamics_derivatives!, simulate_jvp!, simulate_step_derivatives!,
     inverse_dynamics_vjp!, dynamics_vjp!, simulate_vjp!, set_points!, point_kinematics!, point_jacobian!, point_velocity!, point_kinematics_vjp!,
-    contact_dynamics_vjp!, dynamics_contact_vjp!, simulate_contact_vjp!
+    contact_dynamics_vjp!, dynamics_contact_vjp!, simulate_contact_vjp!, contact_dynamics_jvp!, dynamics_contact_jvp!, dynamics_contact_derivatives!
 
 const librbd_hip = Ref("librbd_hip.so")   # set to <repo>/rigidbodydynamics.jl_amd/csrc/librbd_hip.so
 const libhip = Ref("libamdhip64.so")
@@ -863,6 +863,63 @@ function simulate_contact_vjp!(q̄::Buffer{T}, v̄::Buffer{T}, s̄::Buffer{T}, s
         nullable(τ̄), nullable(f̄ext), opts(state)), "rbd_simulate_contact_vjp")
     finish(state)
     q̄, v̄, s̄, τ̄
+end
+
+"""`contact_dynamics_jvp!(dcw, dṡ, dsout, state, ntan; dq, dv, ds)` — `contact_dynamics!` pushed forward along `ntan` directions per state on the branch each
+(point, half-space) pair takes: the tangents of the contact wrenches (6·n_bodies·ntan × B), of ṡ and of the friction state after the resets (ns·ntan × B;
+each may be `nothing`).  `state.s` is read, not reset (`rbd_contact_dynamics_jvp`)."""
+function contact_dynamics_jvp!(dcw, dṡ, dsout, state::BatchedMechanismState{T}, ntan::Integer; dq = nothing, dv = nothing, ds = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, ns, B = state.model.nq, state.model.nv, size(state.s, 1), batchsize(state)
+    ntan > 0 || throw(ArgumentError("ntan must be positive"))
+    for (x, n) in ((dṡ, ns), (dsout, ns), (dq, nq), (dv, nv), (ds, ns))
+        x === nothing || size(x) == (n * ntan, B) || throw(DimensionMismatch("tangent buffer has wrong size"))
+    end
+    check(ccall((:rbd_contact_dynamics_jvp, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, ntan, state.q, state.v, state.s, nullable(dq), nullable(dv), nullable(ds), nullable(dcw), nullable(dṡ), nullable(dsout), opts(state)),
+        "rbd_contact_dynamics_jvp")
+    finish(state)
+    dcw, dṡ, dsout
+end
+
+"""`dynamics_contact_jvp!(dv̇, dṡ, dsout, state, ntan; torques, externalwrenches, dq, dv, ds, dτ, dexternalwrenches, v̇out, ṡout)` — `dynamics!` of a mechanism
+with contact points pushed forward along `ntan` directions per state, the ODE form (q, v, s, τ, wext) -> (v̇, ṡ, s after the resets), in one pass: what
+`ForwardDiff` computes through `dynamics!` of such a mechanism (`rbd_dynamics_contact_jvp`)."""
+function dynamics_contact_jvp!(dv̇, dṡ, dsout, state::BatchedMechanismState{T}, ntan::Integer; torques = nothing, externalwrenches = nothing, dq = nothing,
+        dv = nothing, ds = nothing, dτ = nothing, dexternalwrenches = nothing, v̇out = nothing, ṡout = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, ns, B = state.model.nq, state.model.nv, size(state.s, 1), batchsize(state)
+    ntan > 0 || throw(ArgumentError("ntan must be positive"))
+    for (x, n) in ((dv̇, nv), (dṡ, ns), (dsout, ns), (dq, nq), (dv, nv), (ds, ns), (dτ, nv))
+        x === nothing || size(x) == (n * ntan, B) || throw(DimensionMismatch("tangent buffer has wrong size"))
+    end
+    check(ccall((:rbd_dynamics_contact_jvp, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, ntan, state.q, state.v, state.s, nullable(torques), nullable(densewrenches(state, externalwrenches)), nullable(dq), nullable(dv),
+        nullable(ds), nullable(dτ), nullable(dexternalwrenches), nullable(v̇out), nullable(ṡout), nullable(dv̇), nullable(dṡ), nullable(dsout), opts(state)),
+        "rbd_dynamics_contact_jvp")
+    finish(state)
+    dv̇, dṡ, dsout
+end
+
+"""`dynamics_contact_derivatives!(∂v̇∂q, ∂v̇∂v, ∂v̇∂s, ∂v̇∂τ, ∂ṡ∂q, ∂ṡ∂v, ∂ṡ∂s, state; torques, externalwrenches, v̇out, ṡout)` — the Jacobians of `dynamics!` of a
+mechanism with contact points (fext fixed), column-major per state: (nv·nq), (nv·nv), (nv·ns), (nv·nv) = M⁻¹, (ns·nq), (ns·nv), (ns·ns) × B; each may be
+`nothing` (`rbd_dynamics_contact_derivatives`)."""
+function dynamics_contact_derivatives!(dv̇dq, dv̇dv, dv̇ds, dv̇dτ, dṡdq, dṡdv, dṡds, state::BatchedMechanismState{T}; torques = nothing, externalwrenches = nothing,
+        v̇out = nothing, ṡout = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, ns, B = state.model.nq, state.model.nv, size(state.s, 1), batchsize(state)
+    for (x, n) in ((dv̇dq, nv * nq), (dv̇dv, nv * nv), (dv̇ds, nv * ns), (dv̇dτ, nv * nv), (dṡdq, ns * nq), (dṡdv, ns * nv), (dṡds, ns * ns))
+        x === nothing || size(x) == (n, B) || throw(DimensionMismatch("Jacobian buffer has wrong size"))
+    end
+    check(ccall((:rbd_dynamics_contact_derivatives, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, state.q, state.v, state.s, nullable(torques), nullable(densewrenches(state, externalwrenches)), nullable(v̇out), nullable(ṡout),
+        nullable(dv̇dq), nullable(dv̇dv), nullable(dv̇ds), nullable(dv̇dτ), nullable(dṡdq), nullable(dṡdv), nullable(dṡds), opts(state)),
+        "rbd_dynamics_contact_derivatives")
+    finish(state)
+    dv̇dq, dv̇dv, dv̇ds, dv̇dτ, dṡdq, dṡdv, dṡds
 end
 
 # ---- multi-GPU: one process per GPU, the batch sharded by state, v̇ gathered over RCCL (SURVEY.md §8 e) ------------------------------

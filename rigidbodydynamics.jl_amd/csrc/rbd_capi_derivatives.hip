@@ -2,6 +2,7 @@
 // simulate steps and soft contact, and point kinematics.  The workspace and what every entry point starts with: rbd_capi_internal.hpp; the kernels:
 // rbd_tangent_kernels.hip, rbd_point_kernels.hip, rbd_contact_kernels.hip.
 #include "rbd_capi_internal.hpp"
+#include "rbd_contact.hpp"
 
 // ---- forward-mode derivatives of inverse_dynamics! and dynamics! (header 700; kernels: rbd_tangent_kernels.hip) --------------------------------------------
 namespace {
@@ -82,7 +83,10 @@ int tan_ensure(rbd_ws* w, int ntan) {
     const int N = tangent_chunk((int)es);
     const size_t per = std::max<size_t>(1, tangent_scratch_elems_per_thread(w->tan, (int)es) * es);
     const long want = B * ((ntan + N - 1) / N);
-    const long cap = std::max<long>(64, (long)(TAN_SCRATCH_CAP / per) / 64 * 64);
+    // RBD_TUNE tan_scratch_threads=<k>: room for k (state, chunk) threads instead of the byte cap (tests reach the several-slabs path at small sizes)
+    bool has;
+    const long knob = tune("tan_scratch_threads", 0, &has);
+    const long cap = has ? std::max(1L, knob) : std::max<long>(64, (long)(TAN_SCRATCH_CAP / per) / 64 * 64);
     const long threads = std::min(want, cap);
     if ((st = ensure(w->d_tan_scratch, per * threads))) return st;
     w->tan_threads = threads;
@@ -673,6 +677,113 @@ int sav_run(rbd_ws* w, int32_t B, int layout, void* q, void* v, const void* tau,
   }
   return RBD_OK;
 }
+
+// ---- forward mode through soft contact (header 700 addition): rbd_contact_dynamics_jvp, rbd_dynamics_contact_jvp, rbd_dynamics_contact_derivatives -------------
+// the first call of a workspace allocates what tan_ensure and ct_ensure do, the right-hand sides for max(ntan, nq + nv + ns) directions (the Jacobians' columns:
+// a JVP call after a derivatives call allocates nothing); a JVP call with more directions than any before allocates again
+int ctj_ensure(rbd_ws* w, int ntan) {
+  const rbd_model* m = w->model;
+  if (int st = tan_ensure(w, std::max(ntan, m->nq + m->nv + 3 * m->ncp * m->nhs))) return st;
+  return ct_ensure(w);
+}
+
+template <typename T> TanContactArgs<T> ctj_args(rbd_ws* w, int32_t B, int layout, int ntan, const void* s, const void* ds) {
+  const rbd_model* m = w->model;
+  const long ns = 3L * m->ncp * m->nhs;
+  TanContactArgs<T> C{};
+  C.C = w->ctm;
+  C.s = (const T*)s; C.ds = (const T*)ds;
+  C.Ls = layout_of(layout, ns, B); C.Lds = layout_of(layout, ns * ntan, B);
+  C.gs0 = m->nq + m->nv;
+  C.dcw = ColOut<T>::single(nullptr, Layout{0, 0}, 6 * m->nb);
+  C.dsdot = C.dsout = ColOut<T>::single(nullptr, Layout{0, 0}, (int)ns);
+  return C;
+}
+
+// the forward contact launches on a copy of s (the caller's is const; contact_kernel resets the pairs outside): the total wrenches fext + contact into
+// w->d_tw, ṡ into sdot_out (nullable); then v̇ and the factor of M at those wrenches (tan_dynamics_value), when v̇ or a tangent of it is asked for
+template <typename T>
+int ctj_values(rbd_ws* w, int32_t B, const Opts& o, const void* q, const void* v, const void* s, const void* tau, const void* fext, void* sdot_out, void* vd) {
+  const rbd_model* m = w->model;
+  int st;
+  HIP_TRY(hipMemcpyAsync(w->d_ct_s.p, s, sizeof(T) * 3 * m->ncp * m->nhs * B, hipMemcpyDeviceToDevice, w->stream));
+  if ((st = run_contact(w, B, o, q, v, w->d_ct_s.p, sdot_out, fext, nullptr, w->d_tw.p))) return st;
+  if (vd && m->nv > 0 && (st = tan_dynamics_value<T>(w, B, o.layout, q, v, tau, w->d_tw.p, vd))) return st;
+  return RBD_OK;
+}
+
+template <typename T>
+int ctj_dyn_jvp(rbd_ws* w, int32_t B, int32_t ntan, const Opts& o, const void* q, const void* v, const void* s, const void* tau, const void* fext, const void* dq,
+                const void* dv, const void* ds, const void* dtau, const void* dfext, void* vdot_out, void* sdot_out, void* dvdot_out, void* dsdot_out,
+                void* ds_out_out) {
+  const rbd_model* m = w->model;
+  const bool solve = dvdot_out && m->nv > 0;
+  void* vd = vdot_out ? vdot_out : (solve ? w->d_tan_vd.p : nullptr);
+  int st;
+  if ((vd || sdot_out || solve) && (st = ctj_values<T>(w, B, o, q, v, s, tau, fext, sdot_out, vd))) return st;
+  if (!solve && !dsdot_out && !ds_out_out) return RBD_OK;
+  // M dv̇ = dτ − ∂ID(q, v, v̇)·(dq, dv, 0, d(total wrenches)): the pass at the TOTAL wrenches, the contact step adding the contact wrenches' tangents
+  TanArgs<T> A = tan_args<T>(w, B, o.layout, ntan, q, v, solve ? vd : nullptr, solve ? w->d_tw.p : nullptr);
+  A.dq = (const T*)dq; A.dv = (const T*)dv; A.dfext = solve ? (const T*)dfext : nullptr;
+  A.sign = T(-1);
+  if (solve) { A.out.a = (T*)w->d_tan_rhs.p; A.out.La = Layout{B, 1}; A.dadd = (const T*)dtau; }
+  TanContactArgs<T> C = ctj_args<T>(w, B, o.layout, ntan, s, ds);
+  C.dsdot.a = (T*)dsdot_out; C.dsdot.La = C.Lds;
+  C.dsout.a = (T*)ds_out_out; C.dsout.La = C.Lds;
+  C.forward_only = solve ? 0 : 1;
+  HIP_TRY(launch_tangent_contact_rnea<T>(w->tan, A, C, w->d_tan_scratch.p, w->tan_threads, w->stream));
+  if (solve) {
+    const ColOut<T> out = ColOut<T>::single((T*)dvdot_out, A.Ldv, m->nv);
+    HIP_TRY(launch_tangent_solve<T>(m->nv, B, 0, ntan, w->d_tan_L.p, Layout{B, 1}, w->d_tan_rhs.p, 0, out, w->d_tan_x.p, w->stream));
+  }
+  return RBD_OK;
+}
+
+// The columns of (q; v) in one pass (ColOut splits over two buffers), those of s in a second one with g0 = nq + nv; the right-hand sides of column g at g, so
+// that each block's solve writes its own Jacobian.  A block none of whose outputs is asked for is not launched; no wrench sweep and no solve without dvdot_*.
+template <typename T>
+int ctj_dyn_derivs(rbd_ws* w, int32_t B, const Opts& o, const void* q, const void* v, const void* s, const void* tau, const void* fext, void* vdot_out,
+                   void* sdot_out, void* dvdot_dq, void* dvdot_dv, void* dvdot_ds, void* dvdot_dtau, void* dsdot_dq, void* dsdot_dv, void* dsdot_ds) {
+  const rbd_model* m = w->model;
+  const int nq = m->nq, nv = m->nv, ns = 3 * m->ncp * m->nhs, layout = o.layout;
+  const bool mv = nv > 0;
+  const bool any_vd = mv && (dvdot_dq || dvdot_dv || dvdot_ds || dvdot_dtau);
+  void* vd = vdot_out ? vdot_out : (any_vd ? w->d_tan_vd.p : nullptr);
+  int st;
+  if ((vd || sdot_out || any_vd) && (st = ctj_values<T>(w, B, o, q, v, s, tau, fext, sdot_out, vd))) return st;
+  const Layout Li{B, 1};
+  auto jac = [&](int rows, int cols) { return layout_of(layout, (long)rows * cols, B); };
+  // one block of unit directions g0 … g1 − 1; out / dso: where the block's dv̇ and dṡ columns go
+  auto block = [&](int g0, int g1, bool solve, const ColOut<T>& out, const ColOut<T>& dso) -> int {
+    if (g1 <= g0) return RBD_OK;
+    TanArgs<T> A = tan_args<T>(w, B, layout, g1 - g0, q, v, solve ? vd : nullptr, solve ? w->d_tw.p : nullptr);
+    A.unit = 1; A.g0 = g0;
+    A.sign = T(-1);
+    if (solve) { A.out.a = (T*)w->d_tan_rhs.p; A.out.La = Li; }
+    TanContactArgs<T> C = ctj_args<T>(w, B, layout, g1 - g0, s, nullptr);
+    C.dsdot = dso;
+    C.forward_only = solve ? 0 : 1;
+    HIP_TRY(launch_tangent_contact_rnea<T>(w->tan, A, C, w->d_tan_scratch.p, w->tan_threads, w->stream));
+    if (solve) HIP_TRY(launch_tangent_solve<T>(nv, B, g0, g1 - g0, w->d_tan_L.p, Li, w->d_tan_rhs.p, 0, out, w->d_tan_x.p, w->stream));
+    return RBD_OK;
+  };
+  {
+    const bool wq = (mv && dvdot_dq) || dsdot_dq, wv = (mv && dvdot_dv) || dsdot_dv;
+    const ColOut<T> out{(T*)dvdot_dq, jac(nv, nq), (T*)dvdot_dv, jac(nv, nv), nq, nv};
+    const ColOut<T> dso{(T*)dsdot_dq, jac(ns, nq), (T*)dsdot_dv, jac(ns, nv), nq, ns};
+    if ((st = block(wq ? 0 : nq, wv ? nq + nv : nq, mv && (dvdot_dq || dvdot_dv), out, dso))) return st;
+  }
+  if ((mv && dvdot_ds) || dsdot_ds) {  // (columns < nq + nv do not occur in this block: the first buffer of its ColOuts is never asked for)
+    const ColOut<T> out{nullptr, Layout{0, 0}, (T*)dvdot_ds, jac(nv, ns), nq + nv, nv};
+    const ColOut<T> dso{nullptr, Layout{0, 0}, (T*)dsdot_ds, jac(ns, ns), nq + nv, ns};
+    if ((st = block(nq + nv, nq + nv + ns, mv && dvdot_ds, out, dso))) return st;
+  }
+  if (mv && dvdot_dtau) {  // ∂v̇/∂τ = M⁻¹ (the contact wrenches do not depend on τ): the solve against the identity
+    const ColOut<T> out = ColOut<T>::single((T*)dvdot_dtau, jac(nv, nv), nv);
+    HIP_TRY(launch_tangent_solve<T>(nv, B, 0, nv, w->d_tan_L.p, Li, nullptr, 1, out, w->d_tan_x.p, w->stream));
+  }
+  return RBD_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -954,6 +1065,68 @@ int rbd_dynamics_contact_vjp(rbd_ws_t* w, int32_t B, const void* q, const void* 
       if (fext_bar) HIP_TRY(hipMemsetAsync(fext_bar, 0, es * 6 * m->nb * B, w->stream));
     }
     return ct_adjoint<T>(w, B, o.layout, q, v, s, wbar, sdot_bar, s_out_bar, q_bar, v_bar, s_bar, vdot_bar ? 1 : 0);
+  });
+}
+
+// ---- forward mode through soft contact: rbd_contact_dynamics_jvp, rbd_dynamics_contact_jvp, rbd_dynamics_contact_derivatives ------------------------------------
+int rbd_contact_dynamics_jvp(rbd_ws_t* w, int32_t B, int32_t ntan, const void* q, const void* v, const void* s, const void* dq, const void* dv, const void* ds,
+                             void* dcw_out, void* dsdot_out, void* ds_out_out, const rbd_opts_t* opts) {
+  Opts o;
+  int st = contact_vjp_scope(w, B, opts, &o);
+  if (st != RBD_OK) return st;
+  if (ntan <= 0 || !q || !v || !s) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  if ((st = ctj_ensure(w, ntan))) return st;
+  Timed t(w);
+  w->last_kernel = "tangent_contact_rnea_kernel";
+  if (!dcw_out && !dsdot_out && !ds_out_out) return RBD_OK;
+  return by_dtype(w->dtype, [&](auto t) -> int {
+    using T = decltype(t);
+    // the tangent pass in its forward-only mode: no v̇, no wrenches, no wrench sweep
+    TanArgs<T> A = tan_args<T>(w, B, o.layout, ntan, q, v, nullptr, nullptr);
+    A.dq = (const T*)dq; A.dv = (const T*)dv;
+    TanContactArgs<T> C = ctj_args<T>(w, B, o.layout, ntan, s, ds);
+    C.dcw.a = (T*)dcw_out; C.dcw.La = A.Ldf;
+    C.dsdot.a = (T*)dsdot_out; C.dsdot.La = C.Lds;
+    C.dsout.a = (T*)ds_out_out; C.dsout.La = C.Lds;
+    C.forward_only = 1;
+    HIP_TRY(launch_tangent_contact_rnea<T>(w->tan, A, C, w->d_tan_scratch.p, w->tan_threads, w->stream));
+    return RBD_OK;
+  });
+}
+
+int rbd_dynamics_contact_jvp(rbd_ws_t* w, int32_t B, int32_t ntan, const void* q, const void* v, const void* s, const void* tau, const void* fext, const void* dq,
+                             const void* dv, const void* ds, const void* dtau, const void* dfext, void* vdot_out, void* sdot_out, void* dvdot_out,
+                             void* dsdot_out, void* ds_out_out, const rbd_opts_t* opts) {
+  Opts o;
+  int st = contact_vjp_scope(w, B, opts, &o);
+  if (st != RBD_OK) return st;
+  if (ntan <= 0 || !q || !v || !s) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  if ((st = ctj_ensure(w, ntan))) return st;
+  Timed t(w);
+  w->last_kernel = "contact_kernel + tangent_contact_rnea_kernel + tangent_solve_kernel";
+  return by_dtype(w->dtype, [&](auto t) {
+    return ctj_dyn_jvp<decltype(t)>(w, B, ntan, o, q, v, s, tau, fext, dq, dv, ds, dtau, dfext, vdot_out, sdot_out, dvdot_out, dsdot_out, ds_out_out);
+  });
+}
+
+int rbd_dynamics_contact_derivatives(rbd_ws_t* w, int32_t B, const void* q, const void* v, const void* s, const void* tau, const void* fext, void* vdot_out,
+                                     void* sdot_out, void* dvdot_dq, void* dvdot_dv, void* dvdot_ds, void* dvdot_dtau, void* dsdot_dq, void* dsdot_dv,
+                                     void* dsdot_ds, const rbd_opts_t* opts) {
+  Opts o;
+  int st = contact_vjp_scope(w, B, opts, &o);
+  if (st != RBD_OK) return st;
+  if (!q || !v || !s) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  if ((st = ctj_ensure(w, 1))) return st;
+  Timed t(w);
+  w->last_kernel = "contact_kernel + tangent_contact_rnea_kernel + tangent_solve_kernel";
+  return by_dtype(w->dtype, [&](auto t) {
+    return ctj_dyn_derivs<decltype(t)>(w, B, o, q, v, s, tau, fext, vdot_out, sdot_out, dvdot_dq, dvdot_dv, dvdot_ds, dvdot_dtau, dsdot_dq, dsdot_dv, dsdot_ds);
   });
 }
 

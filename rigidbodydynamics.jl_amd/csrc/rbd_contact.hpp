@@ -87,6 +87,127 @@ template <typename S> RBD_HD bool contact_pair_force(const S* pos, const S* vel,
   return true;
 }
 
+// One contact point against every half-space, from its body's kinematics: the contact step of forward mode (rbd_contact_dynamics_jvp, rbd_dynamics_contact_jvp:
+// S = Dual<T, N> between the two sweeps of the tangent RNEA pass, rbd_tangent.hpp) and, with S = T, contact_kernel's arithmetic for one point.
+//   K    the body's (R 9 row-major, p 3, twist 6 = (ω; v)) in the root frame, as tangent_rnea_state and the per-body kinematics export keep them
+//   c    the point's CP_STRIDE constants;  hs: the nh half-spaces, 6 values each
+//   xin(h, x)                    loads the pair's friction state (3 values of S: value and tangents) — wherever the caller keeps it
+//   xout(h, inside, xd, xo)      receives ẋ and the state after the reset (xo = x inside, 0 outside, tangents included) of the pair
+//   w    the point's wrench (pos × f; f) summed over the half-spaces, OVERWRITTEN (zero when every pair is outside)
+// Nothing here knows a buffer layout: the stage-wise passes of simulate can call it per stage state, and tests/test_contact_jvp_cpu.py builds it as plain C++.
+template <typename S, typename XIn, typename XOut>
+RBD_HD void contact_point_step(const S* K, const typename ScalarOf<S>::type* c, const typename ScalarOf<S>::type* hs, int nh, XIn xin, XOut xout, S* w) {
+  using T = typename ScalarOf<S>::type;
+  S loc[3], pos[3], vel[3], t3[3], fsum[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) { loc[j] = S(c[CP_LOC + j]); fsum[j] = S(T(0)); }
+  matvec3(K, loc, pos);  // point = body_to_root * location; velocity = ω × point + v (mechanism_algorithms.jl:697-699)
+#pragma unroll
+  for (int j = 0; j < 3; ++j) pos[j] += K[9 + j];
+  cross3(K + 12, pos, t3);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) vel[j] = t3[j] + K[15 + j];
+  for (int h = 0; h < nh; ++h) {
+    S x[3], f[3], xd[3], xo[3];
+    xin(h, x);
+    const bool inside = contact_pair_force<S>(pos, vel, x, c, hs + (long)h * 6, f, xd);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      xo[j] = inside ? x[j] : S(T(0));
+      fsum[j] += f[j];
+    }
+    xout(h, inside, xd, xo);
+  }
+  cross3(pos, fsum, w);  // Wrench(point, force) (:712), the sum over the half-spaces: pos × is linear in f
+#pragma unroll
+  for (int j = 0; j < 3; ++j) w[3 + j] = fsum[j];
+}
+
+// ---- forward mode: the contact variant of the tangent RNEA pass (rbd_tangent.hpp tangent_rnea_sweeps) -----------------------------------------------------------
+// What the variant needs beside TanArgs.  The friction state's tangents follow the rules of TanArgs' (direction e of a state at rows e·ns …, nullable = zero);
+// with A.unit the directions g ≥ gs0 are the unit vectors of s (gs0 = nq + nv: the third block of the columns of (q; v; s)).  The tangent outputs go by column
+// A.g0 + e like A.out (every buffer nullable): dcw rows of 6 nb (every body's, zero where no point sits), dsdot and dsout rows of ns.
+template <typename T> struct TanContactArgs {
+  ContactModel C;
+  const T *s, *ds;
+  Layout Ls, Lds;
+  int gs0;
+  ColOut<T> dcw, dsdot, dsout;
+  int forward_only;  // 1: return after the contact step (rbd_contact_dynamics_jvp: no wrench sweep for nothing)
+};
+
+// tangent_rnea_state with contact: after the forward sweep stored every body's Dual K, the thread walks the contact points in the order of the additional state,
+// calls contact_point_step<Dual<T, N>> on the point's body and SUBTRACTS THE TANGENT PART of the point's wrench from the body's TAN_W (the sign of fext there).
+// The value part is not touched: the caller hands the pass the TOTAL wrenches (fext + contact, contact_kernel's) as A.fext, the wrenches v̇ was solved at, so
+// the contact value is in TAN_W once already.  The wrench sweep and the right-hand sides then see d(total wrench) = dfext + d(contact wrench).
+template <typename T, int N>
+RBD_HD void tangent_contact_state(const BigModel& M, const TanArgs<T>& A, const TanContactArgs<T>& C, long st, int chunk, T* sc, long ld, long slot) {
+  using D = Dual<T, N>;
+  const int e0 = chunk * N;
+  const int np = C.C.np, nh = C.C.nh, ns = 3 * np * nh;
+  const T* cp = reinterpret_cast<const T*>(C.C.cp);
+  const T* hs = reinterpret_cast<const T*>(C.C.hs);
+  tangent_rnea_sweeps<T, N>(M, A, st, chunk, sc, ld, slot, [&](auto& get, auto& put) -> bool {
+    const bool want_cw = C.dcw.a || C.dcw.b;
+    if (want_cw)
+      for (int r = 0; r < 6 * M.nb; ++r)
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+          if (e0 + j < A.ntan)
+            if (T* o = C.dcw.at(A.g0 + e0 + j, r, st)) *o = T(0);
+    for (int ip = 0; ip < np; ++ip) {
+      const int body = C.C.cbody[ip];
+      D K[18], w[6];
+#pragma unroll
+      for (int k = 0; k < 18; ++k) K[k] = get(TAN_K + k, body);
+      contact_point_step<D>(
+          K, cp + (long)ip * CP_STRIDE, hs, nh,
+          [&](int h, D* x) {
+            const int so = (ip * nh + h) * 3;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+              x[k].v = C.s[(long)(so + k) * C.Ls.sk + layout_base(C.Ls, st)];
+#pragma unroll
+              for (int j = 0; j < N; ++j) {
+                const int e = e0 + j;
+                T d = T(0);
+                if (e < A.ntan) {
+                  if (A.unit) d = A.g0 + e == C.gs0 + so + k ? T(1) : T(0);
+                  else if (C.ds) d = C.ds[((long)e * ns + so + k) * C.Lds.sk + layout_base(C.Lds, st)];
+                }
+                x[k].d[j] = d;
+              }
+            }
+          },
+          [&](int h, bool, const D* xd, const D* xo) {
+            const int so = (ip * nh + h) * 3;
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+#pragma unroll
+              for (int j = 0; j < N; ++j) {
+                const int e = e0 + j;
+                if (e >= A.ntan) continue;
+                if (T* o = C.dsdot.at(A.g0 + e, so + k, st)) *o = xd[k].d[j];
+                if (T* o = C.dsout.at(A.g0 + e, so + k, st)) *o = xo[k].d[j];
+              }
+          },
+          w);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        D x = get(TAN_W + k, body);
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+          x.d[j] -= w[k].d[j];
+          if (want_cw && e0 + j < A.ntan)
+            if (T* o = C.dcw.at(A.g0 + e0 + j, 6 * body + k, st)) *o += w[k].d[j];
+        }
+        put(TAN_W + k, body, x);
+      }
+    }
+    return !C.forward_only;
+  });
+}
+
 // The pullback of one pair.  fb, tqb: the cotangent (τ̄q; f̄) of the body's wrench (pos × f; f) (each nullable: zero); xdb: that of ẋ; xob: that of the friction
 // state after the reset (each nullable).  pos_bar, vel_bar, x_bar (3 each) are OVERWRITTEN.  Returns whether the point is inside.
 template <typename T> RBD_HD bool contact_pair_adjoint(const T* pos, const T* vel, const T* x, const T* c, const T* H, const T* fb, const T* tqb, const T* xdb,

@@ -127,6 +127,9 @@ template <typename T> struct MkAdjArgs; template <typename T> struct PointArgs; 
 size_t tangent_scratch_elems_per_thread(const BigModel& M, int es);
 int tangent_chunk(int es);
 template <typename T> hipError_t launch_tangent_rnea(const BigModel& M, const TanArgs<T>& A, void* scratch, long max_threads, hipStream_t s);
+template <typename T> struct TanContactArgs;  // rbd_contact.hpp
+template <typename T>
+hipError_t launch_tangent_contact_rnea(const BigModel& M, const TanArgs<T>& A, const TanContactArgs<T>& C, void* scratch, long max_threads, hipStream_t s);
 template <typename T>
 hipError_t launch_tangent_solve(int nv, long B, int c0, int ncol, const void* L, Layout Ll, const void* rhs, int identity, const ColOut<T>& out, void* xmem, hipStream_t s);
 template <typename T> hipError_t launch_symmetrize(int nv, long B, void* M, Layout Lm, hipStream_t s);

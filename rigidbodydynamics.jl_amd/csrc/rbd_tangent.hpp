@@ -112,9 +112,11 @@ template <typename T> struct TanArgs {
 };
 
 // inverse_dynamics! with N tangents for state `st`, directions chunk·N … chunk·N + N − 1 of the call.  sc: scratch, element (field, component, body)
-// at ((field (N + 1) + component) nb + body) ld + slot
-template <typename T, int N>
-RBD_HD void tangent_rnea_state(const BigModel& M, const TanArgs<T>& A, long st, int chunk, T* sc, long ld, long slot) {
+// at ((field (N + 1) + component) nb + body) ld + slot.  `mid(get, put)` runs between the two sweeps, when every body's K and wrench (with their tangents) are
+// in the scratch: get(field, body) / put(field, body, x) are the scratch's accessors; it returns whether the wrench sweep runs.  The plain pass hands in a
+// functor that does nothing (tangent_rnea_state below); the contact variant forms the tangents of the contact wrenches there (tangent_contact_state).
+template <typename T, int N, typename Mid>
+RBD_HD void tangent_rnea_sweeps(const BigModel& M, const TanArgs<T>& A, long st, int chunk, T* sc, long ld, long slot, Mid mid) {
   using D = Dual<T, N>;
   auto at = [&](int f, int c, int i) -> T& { return sc[(((long)f * (N + 1) + c) * M.nb + i) * ld + slot]; };
   auto get = [&](int f, int i) {
@@ -182,6 +184,7 @@ RBD_HD void tangent_rnea_state(const BigModel& M, const TanArgs<T>& A, long st, 
       put(TAN_W + k, i, w[k] - fe);
     }
   }
+  if (!mid(get, put)) return;
   for (int i = M.nb - 1; i >= 0; --i) {  // joint_wrenches_and_torques!: τ = Sᵀ w, w added to the parent's
     const int jt = M.tbl[4 * i + 1], voff = M.tbl[4 * i + 3], p = M.tbl[4 * i];
     const T* rbt = rbase + (long)i * RB_STRIDE;
@@ -208,6 +211,14 @@ RBD_HD void tangent_rnea_state(const BigModel& M, const TanArgs<T>& A, long st, 
       for (int k = 0; k < 6; ++k) put(TAN_W + k, p, get(TAN_W + k, p) + w[k]);
     }
   }
+}
+
+struct TanNoMid {
+  template <typename G, typename P> RBD_HD bool operator()(G&, P&) const { return true; }
+};
+template <typename T, int N>
+RBD_HD void tangent_rnea_state(const BigModel& M, const TanArgs<T>& A, long st, int chunk, T* sc, long ld, long slot) {
+  tangent_rnea_sweeps<T, N>(M, A, st, chunk, sc, ld, slot, TanNoMid());
 }
 
 // x = M⁻¹ rhs for one right-hand side of one state against its Cholesky factor (lower triangle of L, column-major per state, layout Ll): the rhs of

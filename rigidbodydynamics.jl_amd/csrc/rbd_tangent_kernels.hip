@@ -1,6 +1,8 @@
 // rbd_tangent_kernels.hip — the kernels of the derivative entry points (rbd_inverse_dynamics_jvp, rbd_dynamics_jvp, rbd_inverse_dynamics_derivatives,
-// rbd_dynamics_derivatives, rbd_simulate_jvp, rbd_simulate_step_derivatives, rbd_inverse_dynamics_vjp, rbd_dynamics_vjp, rbd_simulate_vjp, rbd_point_kinematics_vjp): the tangent RNEA
-// (rbd_tangent.hpp) with one thread per (state, chunk of TAN_CHUNK directions), the multi-right-hand-side triangular solve of dynamics! tangents against the
+// rbd_dynamics_derivatives, rbd_simulate_jvp, rbd_simulate_step_derivatives, rbd_inverse_dynamics_vjp, rbd_dynamics_vjp, rbd_simulate_vjp, rbd_point_kinematics_vjp, rbd_contact_dynamics_jvp, rbd_dynamics_contact_jvp,
+// rbd_dynamics_contact_derivatives): the tangent RNEA
+// (rbd_tangent.hpp) with one thread per (state, chunk of TAN_CHUNK directions) and its variant with the soft-contact step between the sweeps (rbd_contact.hpp),
+// the multi-right-hand-side triangular solve of dynamics! tangents against the
 // Cholesky factor of M, the tangent of the integrator's stage map (rbd_tangent_mk.hpp) with one thread per (state, joint, chunk), the adjoint RNEA
 // (rbd_adjoint.hpp) with one thread per state, and the stage map's values and pullback (rbd_adjoint_mk.hpp) with one thread per (state, joint) of a
 // joint class.  Compiled with -ffinite-math-only -fno-signed-zeros (build.sh): the zero
@@ -10,6 +12,7 @@
 #include "rbd_tangent_mk.hpp"
 #include "rbd_adjoint_mk.hpp"
 #include "rbd_point.hpp"
+#include "rbd_contact.hpp"
 #include "rbd_internal.hpp"
 
 namespace rbd {
@@ -51,6 +54,27 @@ hipError_t launch_tangent_rnea(const BigModel& M, const TanArgs<T>& A, void* scr
   const long nchunks = (A.ntan + N - 1) / N;
   return launch_slabs(nchunks * A.B, max_threads, [&](long t0, long nt) {
     hipLaunchKernelGGL((tangent_rnea_kernel<T, N>), dim3((unsigned)((nt + 63) / 64)), dim3(64), 0, s, M, A, t0, nt, (T*)scratch);
+  });
+}
+
+// the contact variant (rbd_contact.hpp tangent_contact_state; rbd_contact_dynamics_jvp, rbd_dynamics_contact_jvp, rbd_dynamics_contact_derivatives): the same
+// threads, slabs and scratch; an instantiation of its own, so that tangent_rnea_kernel stays what it was
+template <typename T, int N>
+__global__ __launch_bounds__(64) void tangent_contact_rnea_kernel(BigModel M, TanArgs<T> A, TanContactArgs<T> C, long t0, long nt, T* __restrict__ scratch) {
+  const long slot = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= nt) return;
+  const long t = t0 + slot;  // (the thread of the CALL, not of the slab: its chunk picks the directions whose dsdot / ds_out / dcw rows it writes)
+  const int chunk = (int)(t / A.B);
+  const long st = t - (long)chunk * A.B;
+  tangent_contact_state<T, N>(M, A, C, st, chunk, scratch, nt, slot);
+}
+
+template <typename T>
+hipError_t launch_tangent_contact_rnea(const BigModel& M, const TanArgs<T>& A, const TanContactArgs<T>& C, void* scratch, long max_threads, hipStream_t s) {
+  constexpr int N = TanChunk<T>::N;
+  const long nchunks = (A.ntan + N - 1) / N;
+  return launch_slabs(nchunks * A.B, max_threads, [&](long t0, long nt) {
+    hipLaunchKernelGGL((tangent_contact_rnea_kernel<T, N>), dim3((unsigned)((nt + 63) / 64)), dim3(64), 0, s, M, A, C, t0, nt, (T*)scratch);
   });
 }
 
@@ -368,6 +392,7 @@ template <typename T> hipError_t launch_mk_stage_classes(MkAdjArgs<T> A, const i
 
 #define RBD_TAN_INST(T)                                                                                                                                    \
   template hipError_t launch_tangent_rnea<T>(const BigModel&, const TanArgs<T>&, void*, long, hipStream_t);                                              \
+  template hipError_t launch_tangent_contact_rnea<T>(const BigModel&, const TanArgs<T>&, const TanContactArgs<T>&, void*, long, hipStream_t);             \
   template hipError_t launch_tangent_solve<T>(int, long, int, int, const void*, Layout, const void*, int, const ColOut<T>&, void*, hipStream_t);          \
   template hipError_t launch_symmetrize<T>(int, long, void*, Layout, hipStream_t);                                                                   \
   template hipError_t launch_tangent_mk_stage<T>(const MkTanArgs<T>&, hipStream_t);                                                                     \

@@ -1229,3 +1229,108 @@ def simulate_contact_vjp_(q_bar: torch.Tensor, v_bar: torch.Tensor, s_bar: torch
                                               ctypes.byref(opts))
     _raise(st, "rbd_simulate_contact_vjp")
     return q_bar, v_bar, s_bar, tau_bar, fext_bar
+
+
+# ---- forward mode through soft contact (rbd_contact_dynamics_jvp, rbd_dynamics_contact_jvp, rbd_dynamics_contact_derivatives): what ForwardDiff computes
+# through `dynamics!` of a mechanism with contact points, on the branch each (point, half-space) pair takes.  Tangents as dynamics_jvp_ ((B, ntan·n), direction
+# d at columns d·n …); `s` (B, ns) is read, never reset; q, v, s default to the state's.
+
+def _contact_qvs(state: MechanismState, q, v, s):
+    f = state.flat
+    q = state.q if q is None else q
+    v = state.v if v is None else v
+    s = state.s if s is None else s
+    if q is None or v is None or s is None:
+        raise ValueError("q, v and s are required")
+    state._check(q, f.nq, "q")
+    state._check(v, f.nv, "v")
+    state._check(s, f.ns, "s")
+    return q, v, s
+
+
+def contact_dynamics_jvp_(state: MechanismState, ntan: int, dq: Optional[torch.Tensor] = None, dv: Optional[torch.Tensor] = None,
+                          ds: Optional[torch.Tensor] = None, dcw: Optional[torch.Tensor] = None, dsd: Optional[torch.Tensor] = None,
+                          ds_out: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None,
+                          s: Optional[torch.Tensor] = None):
+    """`contact_dynamics!` with `ntan` tangent directions per state: (dq, dv, ds) (each optional: a zero direction) -> the tangents of the contact wrenches
+    `dcw` (B, ntan·6·n_bodies), of ṡ `dsd` and of the friction state after the resets `ds_out` (B, ntan·ns), each optional, overwritten."""
+    f = state.flat
+    if int(ntan) <= 0:
+        raise ValueError("ntan must be positive")
+    q, v, s = _contact_qvs(state, q, v, s)
+    _check_tangent(state, dq, f.nq, ntan, "dq")
+    _check_tangent(state, dv, f.nv, ntan, "dv")
+    _check_tangent(state, ds, f.ns, ntan, "ds")
+    _check_tangent(state, dcw, 6 * f.n_bodies, ntan, "dcw")
+    _check_tangent(state, dsd, f.ns, ntan, "dsd")
+    _check_tangent(state, ds_out, f.ns, ntan, "ds_out")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_contact_dynamics_jvp(state.ws.handle, state.batch, int(ntan), _ptr(q), _ptr(v), _ptr(s), _ptr(dq), _ptr(dv), _ptr(ds), _ptr(dcw),
+                                              _ptr(dsd), _ptr(ds_out), ctypes.byref(opts))
+    _raise(st, "rbd_contact_dynamics_jvp")
+    return dcw, dsd, ds_out
+
+
+def dynamics_contact_jvp_(state: MechanismState, ntan: int, torques: Optional[torch.Tensor] = None, externalwrenches: Optional[torch.Tensor] = None,
+                          dq: Optional[torch.Tensor] = None, dv: Optional[torch.Tensor] = None, ds: Optional[torch.Tensor] = None,
+                          dtorques: Optional[torch.Tensor] = None, dexternalwrenches: Optional[torch.Tensor] = None, dvd: Optional[torch.Tensor] = None,
+                          dsd: Optional[torch.Tensor] = None, ds_out: Optional[torch.Tensor] = None, vdout: Optional[torch.Tensor] = None,
+                          sdout: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None,
+                          s: Optional[torch.Tensor] = None):
+    """`dynamics!` of a mechanism with contact points with `ntan` tangent directions per state, the ODE form (q, v, s, τ, f_ext) -> (v̇, ṡ, s after the
+    resets): the tangent inputs dq, dv, ds, dtorques, dexternalwrenches (each optional: a zero direction) -> `dvd` (B, ntan·nv), `dsd`, `ds_out` (B, ntan·ns),
+    each optional, overwritten, in one pass; `vdout` / `sdout` receive v̇ and ṡ themselves."""
+    f = state.flat
+    if int(ntan) <= 0:
+        raise ValueError("ntan must be positive")
+    q, v, s = _contact_qvs(state, q, v, s)
+    state._check(torques, f.nv, "torques")
+    state._check(externalwrenches, 6 * f.n_bodies, "externalwrenches")
+    _check_tangent(state, dq, f.nq, ntan, "dq")
+    _check_tangent(state, dv, f.nv, ntan, "dv")
+    _check_tangent(state, ds, f.ns, ntan, "ds")
+    _check_tangent(state, dtorques, f.nv, ntan, "dτ")
+    _check_tangent(state, dexternalwrenches, 6 * f.n_bodies, ntan, "dexternalwrenches")
+    _check_tangent(state, dvd, f.nv, ntan, "dv̇")
+    _check_tangent(state, dsd, f.ns, ntan, "dsd")
+    _check_tangent(state, ds_out, f.ns, ntan, "ds_out")
+    state._check(vdout, f.nv, "vdout")
+    state._check(sdout, f.ns, "sdout")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_dynamics_contact_jvp(state.ws.handle, state.batch, int(ntan), _ptr(q), _ptr(v), _ptr(s), _ptr(torques), _ptr(externalwrenches),
+                                              _ptr(dq), _ptr(dv), _ptr(ds), _ptr(dtorques), _ptr(dexternalwrenches), _ptr(vdout), _ptr(sdout), _ptr(dvd),
+                                              _ptr(dsd), _ptr(ds_out), ctypes.byref(opts))
+    _raise(st, "rbd_dynamics_contact_jvp")
+    return dvd, dsd, ds_out
+
+
+def dynamics_contact_derivatives_(state: MechanismState, torques: Optional[torch.Tensor] = None, externalwrenches: Optional[torch.Tensor] = None,
+                                  dvd_dq: Optional[torch.Tensor] = None, dvd_dv: Optional[torch.Tensor] = None, dvd_ds: Optional[torch.Tensor] = None,
+                                  dvd_dtau: Optional[torch.Tensor] = None, dsd_dq: Optional[torch.Tensor] = None, dsd_dv: Optional[torch.Tensor] = None,
+                                  dsd_ds: Optional[torch.Tensor] = None, vdout: Optional[torch.Tensor] = None, sdout: Optional[torch.Tensor] = None,
+                                  q: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None, s: Optional[torch.Tensor] = None):
+    """The Jacobians of `dynamics!` of a mechanism with contact points, the external wrenches held fixed, column-major per state (jacobian_view): dvd_dq
+    (B, nv·nq), dvd_dv (B, nv·nv), dvd_ds (B, nv·ns), dvd_dtau = M⁻¹ (B, nv·nv); dsd_dq (B, ns·nq), dsd_dv (B, ns·nv), dsd_ds (B, ns·ns) — every output
+    optional; `vdout` / `sdout` receive v̇ and ṡ."""
+    f = state.flat
+    q, v, s = _contact_qvs(state, q, v, s)
+    state._check(torques, f.nv, "torques")
+    state._check(externalwrenches, 6 * f.n_bodies, "externalwrenches")
+    state._check(dvd_dq, f.nv * f.nq, "dvd_dq")
+    state._check(dvd_dv, f.nv * f.nv, "dvd_dv")
+    state._check(dvd_ds, f.nv * f.ns, "dvd_ds")
+    state._check(dvd_dtau, f.nv * f.nv, "dvd_dtau")
+    state._check(dsd_dq, f.ns * f.nq, "dsd_dq")
+    state._check(dsd_dv, f.ns * f.nv, "dsd_dv")
+    state._check(dsd_ds, f.ns * f.ns, "dsd_ds")
+    state._check(vdout, f.nv, "vdout")
+    state._check(sdout, f.ns, "sdout")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_dynamics_contact_derivatives(state.ws.handle, state.batch, _ptr(q), _ptr(v), _ptr(s), _ptr(torques), _ptr(externalwrenches),
+                                                      _ptr(vdout), _ptr(sdout), _ptr(dvd_dq), _ptr(dvd_dv), _ptr(dvd_ds), _ptr(dvd_dtau), _ptr(dsd_dq),
+                                                      _ptr(dsd_dv), _ptr(dsd_ds), ctypes.byref(opts))
+    _raise(st, "rbd_dynamics_contact_derivatives")
+    return dvd_dq, dvd_dv, dvd_ds, dvd_dtau, dsd_dq, dsd_dv, dsd_ds
