@@ -574,6 +574,30 @@ int rbd_dynamics_contact_derivatives(rbd_ws_t* ws, int32_t B, const void* q, con
                                      void* dvdot_dq, void* dvdot_dv, void* dvdot_ds, void* dvdot_dtau,
                                      void* dsdot_dq, void* dsdot_dv, void* dsdot_ds, const rbd_opts_t* opts);
 
+/* Forward mode through simulate steps with soft contact (700 addition): rbd_simulate_jvp / rbd_simulate_step_derivatives with the friction state s beside
+ * (q, v), as in rbd_simulate_contact_vjp — the tangents of rbd_simulate_contact's steps and the step Jacobians A = ∂x⁺/∂x, B = ∂x⁺/∂τ with x = (q; v; s),
+ * what iLQR / DDP, multiple shooting and Gauss–Newton need of a mechanism with contact points.
+ *  - q, v, s: IN/OUT, advanced by nsteps steps on rbd_simulate_contact_vjp's value route (at every stage state the forward contact launch on a copy of the
+ *    stage's s, then CRBA + Cholesky at the total wrenches): rbd_simulate_contact's state to rounding, not bit for bit.
+ *  - dq (nq·ntan), dv (nv·ntan), ds (ns·ntan): IN/OUT, all required; dtau (nv·ntan), dfext (6·n_bodies·ntan): nullable, held over every stage of every
+ *    step.  Direction d of an n-coordinate tangent at rows d·n … d·n+n−1, as in every other JVP; raw coordinates q.
+ *  - The derivative is that of the branch each (point, half-space) pair takes AT EACH STAGE STATE, an outside pair contributing exact zeros; on a branch
+ *    boundary it is that of the branch taken.  The reset of an outside pair's friction state happens in the stage state only and reaches neither s⁺ nor ds⁺.
+ *    The integrator's small-angle branches are differentiated in the limit, as in rbd_simulate_jvp.
+ *  - Errors: no contact points or no environment: RBD_ERR_INVALID_ARGUMENT (use rbd_simulate_jvp); loop joints: RBD_ERR_HAS_LOOPS; RBD_MEM_HOST:
+ *    RBD_ERR_UNSUPPORTED; ntan <= 0, dt <= 0, nsteps < 0, or a NULL q, v, s, dq, dv or ds: RBD_ERR_INVALID_ARGUMENT; B beyond the workspace's batch:
+ *    RBD_ERR_DIMENSION_MISMATCH; B == 0 or nsteps == 0: a successful no-op.  fp32 and fp64, both layouts, trees of any size, every tree joint type.
+ *  - Allocation: the first call of a workspace, and one whose pass of directions is wider than any before; nothing else allocates or synchronises.  One pass
+ *    holds 2·nq + 6·nv + 4·ns tangent values per direction and state (for max_batch states), at most 2 GiB: more directions run as several passes, each
+ *    starting again from the caller's (q, v, s).
+ *  - rbd_workspace_last_kernel names tangent_contact_stage_kernel afterwards, among the others. */
+int rbd_simulate_contact_jvp(rbd_ws_t* ws, int32_t B, int32_t ntan, void* q, void* v, void* s, const void* tau, const void* fext, double dt,
+                             int32_t nsteps, void* dq, void* dv, void* ds, const void* dtau, const void* dfext, const rbd_opts_t* opts);
+/* One step: q, v, s advanced in place.  x = (q; v; s), nx = nq + nv + ns.  dx_dx: nx×nx, dx_dtau: nx×nv, column-major per state; column j is the JVP along
+ * the j-th unit vector (made on the device).  Both are nullable — a block none of whose outputs is asked for is not run —; fext is held fixed. */
+int rbd_simulate_contact_step_derivatives(rbd_ws_t* ws, int32_t B, void* q, void* v, void* s, const void* tau, const void* fext, double dt,
+                                          void* dx_dx, void* dx_dtau, const rbd_opts_t* opts);
+
 /* ---- diagnostics ------------------------------------------------------------ */
 const char* rbd_status_string(int status);
 const char* rbd_last_hip_error(void);   /* thread-local text of the last HIP failure     */
@@ -593,7 +617,8 @@ const char* rbd_workspace_last_kernel(const rbd_ws_t* ws);
  *      rbd_workspace_set_points, rbd_point_kinematics, rbd_point_kinematics_vjp (point kinematics);
  *      rbd_contact_dynamics_vjp, rbd_dynamics_contact_vjp (reverse mode through soft contact);
  *      rbd_simulate_contact_vjp (reverse mode through simulate steps with soft contact);
- *      rbd_contact_dynamics_jvp, rbd_dynamics_contact_jvp, rbd_dynamics_contact_derivatives (forward mode through soft contact). */
+ *      rbd_contact_dynamics_jvp, rbd_dynamics_contact_jvp, rbd_dynamics_contact_derivatives (forward mode through soft contact);
+ *      rbd_simulate_contact_jvp, rbd_simulate_contact_step_derivatives (forward mode through simulate steps with soft contact). */
 #define RBD_HIP_H_VERSION 700
 int rbd_version(void);
 /* Run-time specialisation.  The one-lane-per-state kernels (mass_matrix! and mass_matrix! + Cholesky at large batches) exist in a second form

@@ -31,7 +31,8 @@ using LinearAlgebra
 export BatchedMechanismState, BatchedDynamicsResult, DeviceMatrix, RbdComm, gather!, gatherv!, mass_matrix_solve_packed!, synchronize, librbd_hip, TorqueTable, PDControl,
     inverse_dynamics_jvp!, dynamics_jvp!, inverse_dynamics_derivatives!, dynamics_derivatives!, simulate_jvp!, simulate_step_derivatives!,
     inverse_dynamics_vjp!, dynamics_vjp!, simulate_vjp!, set_points!, point_kinematics!, point_jacobian!, point_velocity!, point_kinematics_vjp!,
-    contact_dynamics_vjp!, dynamics_contact_vjp!, simulate_contact_vjp!, contact_dynamics_jvp!, dynamics_contact_jvp!, dynamics_contact_derivatives!
+    contact_dynamics_vjp!, dynamics_contact_vjp!, simulate_contact_vjp!, contact_dynamics_jvp!, dynamics_contact_jvp!, dynamics_contact_derivatives!,
+    simulate_contact_jvp!, simulate_contact_step_derivatives!
 
 const librbd_hip = Ref("librbd_hip.so")   # set to <repo>/rigidbodydynamics.jl_amd/csrc/librbd_hip.so
 const libhip = Ref("libamdhip64.so")
@@ -920,6 +921,47 @@ function dynamics_contact_derivatives!(dv̇dq, dv̇dv, dv̇ds, dv̇dτ, dṡdq, 
         "rbd_dynamics_contact_derivatives")
     finish(state)
     dv̇dq, dv̇dv, dv̇ds, dv̇dτ, dṡdq, dṡdv, dṡds
+end
+
+"""`simulate_contact_jvp!(dq, dv, ds, state, ntan, Δt; nsteps = 1, torques, dτ, externalwrenches, dexternalwrenches)` — `nsteps` Munthe-Kaas RK4 steps of
+`simulate` of a mechanism with contact points with `ntan` directions per state carried along: `state`'s q, v and s, `dq` ((nq·ntan) × B), `dv` ((nv·ntan) × B)
+and `ds` ((ns·ntan) × B) advanced in place; `dτ` and the wrench directions held over every stage.  The derivative is that of the branch each (point,
+half-space) pair takes at each stage state (`rbd_simulate_contact_jvp`)."""
+function simulate_contact_jvp!(dq::Buffer{T}, dv::Buffer{T}, ds::Buffer{T}, state::BatchedMechanismState{T}, ntan::Integer, Δt::Real; nsteps::Integer = 1,
+        torques = nothing, dτ = nothing, externalwrenches = nothing, dexternalwrenches = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, ns, B = state.model.nq, state.model.nv, size(state.s, 1), batchsize(state)
+    ntan > 0 || throw(ArgumentError("ntan must be positive"))
+    Δt > 0 || throw(ArgumentError("Δt must be positive"))
+    nsteps >= 0 || throw(ArgumentError("nsteps must be non-negative"))
+    for (x, n) in ((dq, nq), (dv, nv), (ds, ns), (dτ, nv))
+        x === nothing || size(x) == (n * ntan, B) || throw(DimensionMismatch("tangent buffer has wrong size"))
+    end
+    check(ccall((:rbd_simulate_contact_jvp, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Cdouble, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, ntan, state.q, state.v, state.s, nullable(torques), nullable(densewrenches(state, externalwrenches)), Float64(Δt), Int32(nsteps), dq, dv,
+        ds, nullable(dτ), nullable(dexternalwrenches), opts(state)), "rbd_simulate_contact_jvp")
+    finish(state)
+    dq, dv, ds
+end
+
+"""`simulate_contact_step_derivatives!(∂x∂x, ∂x∂τ, state, Δt; torques, externalwrenches)` — one step of `simulate` of a mechanism with contact points (`state`'s
+q, v and s advanced in place) and its Jacobians with x = (q; v; s), nx = nq + nv + ns: (nx·nx) × B and (nx·nv) × B, column-major per state, either one
+`nothing`; the wrenches held fixed (`rbd_simulate_contact_step_derivatives`)."""
+function simulate_contact_step_derivatives!(dxdx, dxdτ, state::BatchedMechanismState{T}, Δt::Real; torques = nothing, externalwrenches = nothing) where {T}
+    checkmodcount(state)
+    nq, nv, ns, B = state.model.nq, state.model.nv, size(state.s, 1), batchsize(state)
+    nx = nq + nv + ns
+    Δt > 0 || throw(ArgumentError("Δt must be positive"))
+    for (x, n) in ((dxdx, nx * nx), (dxdτ, nx * nv))
+        x === nothing || size(x) == (n, B) || throw(DimensionMismatch("Jacobian buffer has wrong size"))
+    end
+    check(ccall((:rbd_simulate_contact_step_derivatives, librbd_hip[]), Cint,
+        (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Cdouble, Ptr{T}, Ptr{T}, Ref{RbdOpts}),
+        state.ws, B, state.q, state.v, state.s, nullable(torques), nullable(densewrenches(state, externalwrenches)), Float64(Δt), nullable(dxdx),
+        nullable(dxdτ), opts(state)), "rbd_simulate_contact_step_derivatives")
+    finish(state)
+    dxdx, dxdτ
 end
 
 # ---- multi-GPU: one process per GPU, the batch sharded by state, v̇ gathered over RCCL (SURVEY.md §8 e) ------------------------------

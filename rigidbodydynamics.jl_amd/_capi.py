@@ -32,6 +32,7 @@ SYMBOLS = (
     "rbd_contact_dynamics_vjp", "rbd_dynamics_contact_vjp",
     "rbd_simulate_contact_vjp",
     "rbd_contact_dynamics_jvp", "rbd_dynamics_contact_jvp", "rbd_dynamics_contact_derivatives",
+    "rbd_simulate_contact_jvp", "rbd_simulate_contact_step_derivatives",
 )
 
 
@@ -106,6 +107,8 @@ def lib():
         L.rbd_contact_dynamics_jvp.argtypes = [vp, i32, i32] + [vp] * 9 + [ctypes.POINTER(Opts)]
         L.rbd_dynamics_contact_jvp.argtypes = [vp, i32, i32] + [vp] * 15 + [ctypes.POINTER(Opts)]
         L.rbd_dynamics_contact_derivatives.argtypes = [vp, i32] + [vp] * 14 + [ctypes.POINTER(Opts)]
+        L.rbd_simulate_contact_jvp.argtypes = [vp, i32, i32] + [vp] * 5 + [ctypes.c_double, i32] + [vp] * 5 + [ctypes.POINTER(Opts)]
+        L.rbd_simulate_contact_step_derivatives.argtypes = [vp, i32] + [vp] * 5 + [ctypes.c_double, vp, vp, ctypes.POINTER(Opts)]
         L.rbd_model_chain_plan.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), i32]
         L.rbd_model_track_plan.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), i32, ctypes.POINTER(i32), i32, ctypes.POINTER(ctypes.c_double), i32]
         L.rbd_comm_unique_id.argtypes = [vp]

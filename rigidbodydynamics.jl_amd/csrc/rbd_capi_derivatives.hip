@@ -212,110 +212,6 @@ int tan_dyn_derivs(rbd_ws* w, int32_t B, int layout, const void* q, const void* 
   return RBD_OK;
 }
 
-// ---- derivatives of simulate steps (header 700 additions) -----------------------------------------------------------------------------------------------
-enum : long { SIM_TAN_CAP = 1L << 31 };  // bytes of the simulate tangent buffers at most: more directions run as several passes
-
-// tangents per (direction, state) of one pass: initial dq, dv, dτ; the stage state's dq, dv; the running sums' two; dv̇
-size_t sim_tan_per_dir(const rbd_model* m) { return 2 * (size_t)m->nq + 6 * (size_t)m->nv; }
-int sim_pass_width(rbd_ws* w, int ndir) {
-  const long per = (long)(esize(w) * sim_tan_per_dir(w->model) * (size_t)w->max_batch);
-  const int N = tangent_chunk((int)esize(w));
-  const long cap = std::max<long>(N, SIM_TAN_CAP / std::max<long>(1, per) / N * N);
-  return (int)std::min<long>(ndir, cap);
-}
-// the first call of a workspace allocates, and one whose pass is wider than any before; nothing else allocates
-int sim_ensure(rbd_ws* w, int width) {
-  const rbd_model* m = w->model;
-  const size_t es = esize(w), B = (size_t)w->max_batch;
-  int st;
-  if ((st = tan_ensure(w, width))) return st;
-  if ((st = ensure(w->d_sim_val, es * B * (4 * (size_t)m->nq + 6 * (size_t)m->nv)))) return st;
-  if (width > w->sim_tan_w) {
-    if ((st = ensure(w->d_sim_tan, es * B * sim_tan_per_dir(m) * (size_t)width))) return st;
-    w->sim_tan_w = width;
-  }
-  return RBD_OK;
-}
-
-// nsteps steps of the RK4 integrator with ndir directions carried along, in passes of at most sim_tan_w directions.  JVP (jac == false): the caller's
-// dq, dv (in/out), dτ, dfext, ndir directions in the call's layout.  Jacobians (jac): the columns g0 … g0 + ndir − 1 of [∂x⁺/∂x  ∂x⁺/∂τ], unit directions
-// made on the device, written to dxdx (columns < nx) and dxdtau.  Each stage: dynamics! at the stage state (CRBA + Cholesky, the factor in the workspace),
-// the tangent RNEA (sign −1, dadd = dτ), the solve for dv̇, the stage kernel.
-template <typename T>
-int sim_tan_run(rbd_ws* w, int32_t B, int layout, void* q, void* v, const void* tau, const void* fext, double dt, int nsteps, int ndir, bool jac, int g0,
-                void* dq, void* dv, const void* dtau, const void* dfext, void* dxdx, void* dxdtau) {
-  const rbd_model* m = w->model;
-  const int nq = m->nq, nv = m->nv, nx = nq + nv, W = w->sim_tan_w;
-  const long Bm = w->max_batch;
-  const size_t es = sizeof(T);
-  const Layout Lq = layout_of(layout, nq, B), Lv = layout_of(layout, nv, B), Li{B, 1};
-  const Layout Ldq = layout_of(layout, (long)nq * ndir, B), Ldv = layout_of(layout, (long)nv * ndir, B), Ldf = layout_of(layout, 6L * m->nb * ndir, B);
-  // values (the call's layout): q0, the two stage-state buffers, the saved initial state; v0, two stage states, the running sum, the saved state
-  T* val = (T*)w->d_sim_val.p;
-  T *q0 = val, *qa = q0 + nq * Bm, *qb = qa + nq * Bm, *qi = qb + nq * Bm, *v0 = qi + nq * Bm, *va = v0 + nv * Bm, *vb = va + nv * Bm;
-  T *accp = vb + nv * Bm, *accv = accp + nv * Bm, *vi = accv + nv * Bm;
-  // tangents of one pass, batch-innermost
-  T* tb = (T*)w->d_sim_tan.p;
-  const long tw = (long)W * Bm;
-  T *dq0 = tb, *dv0 = dq0 + nq * tw, *dd0 = dv0 + nv * tw, *dqs = dd0 + nv * tw, *dvs = dqs + nq * tw, *dap = dvs + nv * tw, *dav = dap + nv * tw,
-    *dvd = dav + nv * tw;
-  auto col = [&](T* p, int n) { return ColOut<T>::single(p, Li, n); };
-  auto user = [&](const void* p, Layout L, int n) { return ColOut<T>::single((T*)p, L, n); };
-  const int npass = (ndir + W - 1) / W;
-  if (npass > 1) {
-    HIP_TRY(hipMemcpyAsync(qi, q, es * nq * B, hipMemcpyDeviceToDevice, w->stream));
-    HIP_TRY(hipMemcpyAsync(vi, v, es * nv * B, hipMemcpyDeviceToDevice, w->stream));
-  }
-  for (int p = 0; p < npass; ++p) {
-    const int e0 = p * W, nw = std::min(W, ndir - e0);
-    if (p > 0) {  // every pass starts from the caller's state (each one writes the same state after the step)
-      HIP_TRY(hipMemcpyAsync(q, qi, es * nq * B, hipMemcpyDeviceToDevice, w->stream));
-      HIP_TRY(hipMemcpyAsync(v, vi, es * nv * B, hipMemcpyDeviceToDevice, w->stream));
-    }
-    HIP_TRY(launch_tangent_mk_load<T>(B, nw, nq, nv, jac ? g0 + e0 : e0, jac ? 1 : 0, user(dq, Ldq, nq), user(dv, Ldv, nv), user(dtau, Ldv, nv), col(dq0, nq),
-                                      col(dv0, nv), col(dd0, nv), w->stream));
-    for (int step = 0; step < nsteps; ++step) {
-      HIP_TRY(hipMemcpyAsync(q0, q, es * nq * B, hipMemcpyDeviceToDevice, w->stream));
-      HIP_TRY(hipMemcpyAsync(v0, v, es * nv * B, hipMemcpyDeviceToDevice, w->stream));
-      for (int stage = 0; stage < 4; ++stage) {
-        // the stage state: (q, v) at stage 0, then qa/va, qb/vb, qa/va; stage 3 writes the state after the step over (q, v)
-        T* qs = stage == 0 ? (T*)q : (stage == 2 ? qb : qa);
-        T* vs = stage == 0 ? (T*)v : (stage == 2 ? vb : va);
-        int st;
-        if ((st = tan_dynamics_value<T>(w, B, layout, qs, vs, tau, fext, w->d_tan_vd.p))) return st;
-        TanArgs<T> A = tan_args<T>(w, B, layout, nw, qs, vs, w->d_tan_vd.p, fext);
-        A.dq = stage == 0 ? dq0 : dqs; A.dv = stage == 0 ? dv0 : dvs; A.Ldq = Li; A.Ldv = Li;
-        A.dfext = (!jac && dfext) ? (const T*)dfext + (long)e0 * 6 * m->nb * Ldf.sk : nullptr; A.Ldf = Ldf;
-        A.out.a = (T*)w->d_tan_rhs.p; A.out.La = Li;
-        A.sign = T(-1); A.dadd = dd0;
-        HIP_TRY(launch_tangent_rnea<T>(w->tan, A, w->d_tan_scratch.p, w->tan_threads, w->stream));
-        HIP_TRY(launch_tangent_solve<T>(nv, B, 0, nw, w->d_tan_L.p, Li, w->d_tan_rhs.p, 0, col(dvd, nv), w->d_tan_x.p, w->stream));
-        MkTanArgs<T> S{};
-        S.B = B; S.ntan = nw; S.nb = w->tan.nb; S.stage = stage; S.dt = (T)dt; S.tbl = w->tan.tbl;
-        S.q0 = q0; S.v0 = v0; S.qs = qs; S.vs = vs; S.vd = (const T*)w->d_tan_vd.p; S.accp = accp; S.accv = accv;
-        S.qn = stage == 3 ? (T*)q : (stage == 1 ? qb : qa);
-        S.vn = stage == 3 ? (T*)v : (stage == 1 ? vb : va);
-        S.Lq = Lq; S.Lv = Lv;
-        S.dq0 = col(dq0, nq); S.dv0 = col(dv0, nv); S.dqs = stage == 0 ? S.dq0 : col(dqs, nq); S.dvs = stage == 0 ? S.dv0 : col(dvs, nv);
-        S.dvd = col(dvd, nv); S.daccp = col(dap, nv); S.daccv = col(dav, nv);
-        S.ocol = 0; S.ovrow = 0;
-        if (stage < 3) {
-          S.oq = col(dqs, nq); S.ov = col(dvs, nv);
-        } else if (step < nsteps - 1) {  // (the next step's base point, in place)
-          S.oq = S.dq0; S.ov = S.dv0;
-        } else if (jac) {
-          S.oq = S.ov = ColOut<T>{(T*)dxdx, layout_of(layout, (long)nx * nx, B), (T*)dxdtau, layout_of(layout, (long)nx * nv, B), nx, nx};
-          S.ocol = g0 + e0; S.ovrow = nq;
-        } else {
-          S.oq = user(dq, Ldq, nq); S.ov = user(dv, Ldv, nv); S.ocol = e0;
-        }
-        HIP_TRY(launch_tangent_mk_stage<T>(S, w->stream));
-      }
-    }
-  }
-  return RBD_OK;
-}
-
 // ---- reverse mode (header 700 additions): the adjoint RNEA, one thread per state -------------------------------------------------------------------------
 enum : long { ADJ_SCRATCH_CAP = TAN_SCRATCH_CAP };  // bytes of adjoint scratch at most: larger calls run in slabs of states
 
@@ -784,6 +680,159 @@ int ctj_dyn_derivs(rbd_ws* w, int32_t B, const Opts& o, const void* q, const voi
   }
   return RBD_OK;
 }
+
+// ---- derivatives of simulate steps (header 700 additions) -----------------------------------------------------------------------------------------------
+enum : long { SIM_TAN_CAP = 1L << 31 };  // bytes of the simulate tangent buffers at most: more directions run as several passes
+
+// values of the friction state per state (0 without contact points or environment: the entry points with contact in their name refuse such a mechanism)
+size_t sim_ns(const rbd_model* m) { return 3 * (size_t)m->ncp * (size_t)m->nhs; }
+// tangents per (direction, state) of one pass: initial dq, dv, dτ; the stage state's dq, dv; the running sums' two; dv̇; with contact the step's ds₀, the
+// stage state's ds, the running sum's tangent and dṡ
+size_t sim_tan_per_dir(const rbd_model* m) { return 2 * (size_t)m->nq + 6 * (size_t)m->nv + 4 * sim_ns(m); }
+// RBD_TUNE sim_tan_bytes=<n>: one pass's tangents in n bytes instead of the cap, at least one chunk of directions (tests reach the several-passes path at
+// small sizes)
+int sim_pass_width(rbd_ws* w, int ndir) {
+  const long per = (long)(esize(w) * sim_tan_per_dir(w->model) * (size_t)w->max_batch);
+  const int N = tangent_chunk((int)esize(w));
+  bool has;
+  const long knob = tune("sim_tan_bytes", 0, &has);
+  const long cap = std::max<long>(N, (has ? std::max(0L, knob) : (long)SIM_TAN_CAP) / std::max<long>(1, per) / N * N);
+  return (int)std::min<long>(ndir, cap);
+}
+// the first call of a workspace allocates, and one whose pass is wider than any before; nothing else allocates.  With contact: what rbd_simulate_contact_vjp's
+// value route does too (sct_ensure), and the saved initial s beside the saved (q, v)
+int sim_ensure(rbd_ws* w, int width, bool contact = false) {
+  const rbd_model* m = w->model;
+  const size_t es = esize(w), B = (size_t)w->max_batch;
+  int st;
+  if ((st = tan_ensure(w, width))) return st;
+  if (contact && (st = sct_ensure(w))) return st;
+  if ((st = ensure(w->d_sim_val, es * B * (4 * (size_t)m->nq + 6 * (size_t)m->nv + sim_ns(m))))) return st;
+  if (width > w->sim_tan_w) {
+    if ((st = ensure(w->d_sim_tan, es * B * sim_tan_per_dir(m) * (size_t)width))) return st;
+    w->sim_tan_w = width;
+  }
+  return RBD_OK;
+}
+
+// nsteps steps of the RK4 integrator with ndir directions carried along, in passes of at most sim_tan_w directions.  JVP (jac == false): the caller's
+// dq, dv (in/out), dτ, dfext, ndir directions in the call's layout.  Jacobians (jac): the columns g0 … g0 + ndir − 1 of [∂x⁺/∂x  ∂x⁺/∂τ], unit directions
+// made on the device, written to dxdx (columns < nx) and dxdtau.  Each stage: dynamics! at the stage state (CRBA + Cholesky, the factor in the workspace),
+// the tangent RNEA (sign −1, dadd = dτ), the solve for dv̇, the stage kernel.
+// With contact (C; rbd_simulate_contact_jvp, rbd_simulate_contact_step_derivatives): x = (q; v; s), the friction state s (in/out) and its tangents ds (the
+// JVP's, in/out) beside (q, v).  Each stage: the forward contact launch at the stage state (sct_contact: a copy of s₀ at stage 0, the total wrenches into
+// w->d_tw, ṡ into the workspace), dynamics! at those wrenches, tangent_contact_rnea_kernel in place of the plain pass (the pass's ds in, dṡ out), the solve,
+// the (q, v) stage kernel as it is, then tangent_contact_stage_kernel for s — values and tangents in one launch, where the value route has
+// contact_stage_value_kernel.  Three launches more per stage than without (the contact launch's two, the friction state's stage kernel).  NULL: no launch differs.
+struct SimTanContact { const Opts* o; void* s; void* ds; };
+template <typename T>
+int sim_tan_run(rbd_ws* w, int32_t B, int layout, void* q, void* v, const void* tau, const void* fext, double dt, int nsteps, int ndir, bool jac, int g0,
+                void* dq, void* dv, const void* dtau, const void* dfext, void* dxdx, void* dxdtau, const SimTanContact* C = nullptr) {
+  const rbd_model* m = w->model;
+  const int nq = m->nq, nv = m->nv, ns = C ? (int)sim_ns(m) : 0, nx = nq + nv + ns, W = w->sim_tan_w;
+  const long Bm = w->max_batch;
+  const size_t es = sizeof(T);
+  const Layout Lq = layout_of(layout, nq, B), Lv = layout_of(layout, nv, B), Ls = layout_of(layout, ns, B), Li{B, 1};
+  const Layout Ldq = layout_of(layout, (long)nq * ndir, B), Ldv = layout_of(layout, (long)nv * ndir, B), Ldf = layout_of(layout, 6L * m->nb * ndir, B);
+  const Layout Lds = layout_of(layout, (long)ns * ndir, B);
+  // values (the call's layout): q0, the two stage-state buffers, the saved initial state; v0, two stage states, the running sum, the saved state
+  T* val = (T*)w->d_sim_val.p;
+  T *q0 = val, *qa = q0 + nq * Bm, *qb = qa + nq * Bm, *qi = qb + nq * Bm, *v0 = qi + nq * Bm, *va = v0 + nv * Bm, *vb = va + nv * Bm;
+  T *accp = vb + nv * Bm, *accv = accp + nv * Bm, *vi = accv + nv * Bm, *si = vi + nv * Bm;
+  // tangents of one pass, batch-innermost
+  T* tb = (T*)w->d_sim_tan.p;
+  const long tw = (long)W * Bm;
+  T *dq0 = tb, *dv0 = dq0 + nq * tw, *dd0 = dv0 + nv * tw, *dqs = dd0 + nv * tw, *dvs = dqs + nq * tw, *dap = dvs + nv * tw, *dav = dap + nv * tw,
+    *dvd = dav + nv * tw;
+  T *ds0 = dvd + nv * tw, *dss = ds0 + ns * tw, *dsa = dss + ns * tw, *dsd = dsa + ns * tw;  // (with contact)
+  auto col = [&](T* p, int n) { return ColOut<T>::single(p, Li, n); };
+  auto user = [&](const void* p, Layout L, int n) { return ColOut<T>::single((T*)p, L, n); };
+  const int npass = (ndir + W - 1) / W;
+  if (npass > 1) {
+    HIP_TRY(hipMemcpyAsync(qi, q, es * nq * B, hipMemcpyDeviceToDevice, w->stream));
+    HIP_TRY(hipMemcpyAsync(vi, v, es * nv * B, hipMemcpyDeviceToDevice, w->stream));
+    if (C) HIP_TRY(hipMemcpyAsync(si, C->s, es * ns * B, hipMemcpyDeviceToDevice, w->stream));
+  }
+  for (int p = 0; p < npass; ++p) {
+    const int e0 = p * W, nw = std::min(W, ndir - e0);
+    if (p > 0) {  // every pass starts from the caller's state (each one writes the same state after the step)
+      HIP_TRY(hipMemcpyAsync(q, qi, es * nq * B, hipMemcpyDeviceToDevice, w->stream));
+      HIP_TRY(hipMemcpyAsync(v, vi, es * nv * B, hipMemcpyDeviceToDevice, w->stream));
+      if (C) HIP_TRY(hipMemcpyAsync(C->s, si, es * ns * B, hipMemcpyDeviceToDevice, w->stream));
+    }
+    // (the τ unit columns follow those of x: at nq + nv without contact, as before)
+    HIP_TRY(launch_tangent_mk_load<T>(B, nw, nq, nv, jac ? g0 + e0 : e0, jac ? 1 : 0, nx, user(dq, Ldq, nq), user(dv, Ldv, nv), user(dtau, Ldv, nv),
+                                      col(dq0, nq), col(dv0, nv), col(dd0, nv), w->stream));
+    if (C) HIP_TRY(launch_tangent_contact_load<T>(B, nw, ns, jac ? g0 + e0 : e0, jac ? 1 : 0, nq + nv, user(C->ds, Lds, ns), col(ds0, ns), w->stream));
+    for (int step = 0; step < nsteps; ++step) {
+      HIP_TRY(hipMemcpyAsync(q0, q, es * nq * B, hipMemcpyDeviceToDevice, w->stream));
+      HIP_TRY(hipMemcpyAsync(v0, v, es * nv * B, hipMemcpyDeviceToDevice, w->stream));
+      for (int stage = 0; stage < 4; ++stage) {
+        // the stage state: (q, v) at stage 0, then qa/va, qb/vb, qa/va; stage 3 writes the state after the step over (q, v)
+        T* qs = stage == 0 ? (T*)q : (stage == 2 ? qb : qa);
+        T* vs = stage == 0 ? (T*)v : (stage == 2 ? vb : va);
+        int st;
+        const SavContact sc{C ? C->o : nullptr, C ? C->s : nullptr, nullptr, nullptr};  // (sct_contact reads the options and the step's start)
+        if (C && (st = sct_contact<T>(w, B, sc, stage, qs, vs, fext))) return st;
+        const void* wr = C ? w->d_tw.p : fext;  // the wrenches dynamics! and the tangent pass see: with contact the total ones
+        if ((st = tan_dynamics_value<T>(w, B, layout, qs, vs, tau, wr, w->d_tan_vd.p))) return st;
+        TanArgs<T> A = tan_args<T>(w, B, layout, nw, qs, vs, w->d_tan_vd.p, wr);
+        A.dq = stage == 0 ? dq0 : dqs; A.dv = stage == 0 ? dv0 : dvs; A.Ldq = Li; A.Ldv = Li;
+        A.dfext = (!jac && dfext) ? (const T*)dfext + (long)e0 * 6 * m->nb * Ldf.sk : nullptr; A.Ldf = Ldf;
+        A.out.a = (T*)w->d_tan_rhs.p; A.out.La = Li;
+        A.sign = T(-1); A.dadd = dd0;
+        if (C) {
+          TanContactArgs<T> K = ctj_args<T>(w, B, layout, nw, sct_stage_state<T>(w, stage), stage == 0 ? ds0 : dss);
+          K.Lds = Li;
+          K.dsdot = col(dsd, ns);
+          HIP_TRY(launch_tangent_contact_rnea<T>(w->tan, A, K, w->d_tan_scratch.p, w->tan_threads, w->stream));
+        } else {
+          HIP_TRY(launch_tangent_rnea<T>(w->tan, A, w->d_tan_scratch.p, w->tan_threads, w->stream));
+        }
+        HIP_TRY(launch_tangent_solve<T>(nv, B, 0, nw, w->d_tan_L.p, Li, w->d_tan_rhs.p, 0, col(dvd, nv), w->d_tan_x.p, w->stream));
+        MkTanArgs<T> S{};
+        S.B = B; S.ntan = nw; S.nb = w->tan.nb; S.stage = stage; S.dt = (T)dt; S.tbl = w->tan.tbl;
+        S.q0 = q0; S.v0 = v0; S.qs = qs; S.vs = vs; S.vd = (const T*)w->d_tan_vd.p; S.accp = accp; S.accv = accv;
+        S.qn = stage == 3 ? (T*)q : (stage == 1 ? qb : qa);
+        S.vn = stage == 3 ? (T*)v : (stage == 1 ? vb : va);
+        S.Lq = Lq; S.Lv = Lv;
+        S.dq0 = col(dq0, nq); S.dv0 = col(dv0, nv); S.dqs = stage == 0 ? S.dq0 : col(dqs, nq); S.dvs = stage == 0 ? S.dv0 : col(dvs, nv);
+        S.dvd = col(dvd, nv); S.daccp = col(dap, nv); S.daccv = col(dav, nv);
+        S.ocol = 0; S.ovrow = 0;
+        if (stage < 3) {
+          S.oq = col(dqs, nq); S.ov = col(dvs, nv);
+        } else if (step < nsteps - 1) {  // (the next step's base point, in place)
+          S.oq = S.dq0; S.ov = S.dv0;
+        } else if (jac) {
+          S.oq = S.ov = ColOut<T>{(T*)dxdx, layout_of(layout, (long)nx * nx, B), (T*)dxdtau, layout_of(layout, (long)nx * nv, B), nx, nx};
+          S.ocol = g0 + e0; S.ovrow = nq;
+        } else {
+          S.oq = user(dq, Ldq, nq); S.ov = user(dv, Ldv, nv); S.ocol = e0;
+        }
+        HIP_TRY(launch_tangent_mk_stage<T>(S, w->stream));
+        if (!C) continue;
+        const SctBufs<T> b = sct_bufs<T>(w);
+        CtTanStageArgs<T> F{};
+        F.B = B; F.ntan = nw; F.ns = ns; F.stage = stage; F.dt = (T)dt;
+        F.s0 = (const T*)C->s; F.sd = b.sdot; F.acc = b.acc; F.sn = stage == 3 ? (T*)C->s : b.ss[stage];
+        F.Ls = Ls;
+        F.ds0 = col(ds0, ns); F.dsd = col(dsd, ns); F.dacc = col(dsa, ns);
+        F.ocol = S.ocol; F.orow = 0;
+        if (stage < 3) {
+          F.os = col(dss, ns);
+        } else if (step < nsteps - 1) {
+          F.os = F.ds0;
+        } else if (jac) {  // (rows nq + nv … of the columns the (q, v) stage kernel writes the rows above of)
+          F.os = S.oq; F.orow = nq + nv;
+        } else {
+          F.os = user(C->ds, Lds, ns);
+        }
+        HIP_TRY(launch_tangent_contact_stage<T>(F, w->stream));
+      }
+    }
+  }
+  return RBD_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1152,6 +1201,51 @@ int rbd_simulate_contact_vjp(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, 
                    "contact_stage_adjoint_kernel + point_adjoint_kernel";
   return by_dtype(w->dtype, [&](auto t) {
     return sav_run<decltype(t)>(w, B, o.layout, q, v, tau, fext, dt, nsteps, P, q_bar, v_bar, tau_bar, fext_bar, &o, s, s_bar);
+  });
+}
+
+// ---- forward mode through simulate steps with soft contact: rbd_simulate_contact_jvp, rbd_simulate_contact_step_derivatives -----------------------------------
+static const char* const kSimContactTanKernels =
+    "contact_kernel + tangent_contact_rnea_kernel + tangent_solve_kernel + tangent_mk_stage_kernel + tangent_contact_stage_kernel";
+
+int rbd_simulate_contact_jvp(rbd_ws_t* w, int32_t B, int32_t ntan, void* q, void* v, void* s, const void* tau, const void* fext, double dt, int32_t nsteps,
+                             void* dq, void* dv, void* ds, const void* dtau, const void* dfext, const rbd_opts_t* opts) {
+  Opts o;
+  int st = contact_vjp_scope(w, B, opts, &o);
+  if (st != RBD_OK) return st;
+  if (ntan <= 0 || !(dt > 0) || nsteps < 0 || !q || !v || !s || !dq || !dv || !ds) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0 || nsteps == 0) return RBD_OK;
+  if (w->model->nv == 0) return RBD_ERR_UNSUPPORTED;  // (as rbd_simulate_contact_vjp: contact points on a mechanism that cannot move)
+  HIP_TRY(hipSetDevice(w->device));
+  const int width = sim_pass_width(w, ntan);
+  if ((st = sim_ensure(w, width, true))) return st;
+  Timed t(w);
+  w->last_kernel = kSimContactTanKernels;
+  const SimTanContact C{&o, s, ds};
+  return by_dtype(w->dtype, [&](auto t) {
+    return sim_tan_run<decltype(t)>(w, B, o.layout, q, v, tau, fext, dt, nsteps, ntan, false, 0, dq, dv, dtau, dfext, nullptr, nullptr, &C);
+  });
+}
+
+int rbd_simulate_contact_step_derivatives(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, const void* tau, const void* fext, double dt, void* dx_dx,
+                                          void* dx_dtau, const rbd_opts_t* opts) {
+  Opts o;
+  int st = contact_vjp_scope(w, B, opts, &o);
+  if (st != RBD_OK) return st;
+  const rbd_model* m = w->model;
+  if (!(dt > 0) || !q || !v || !s) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0) return RBD_OK;
+  if (m->nv == 0) return RBD_ERR_UNSUPPORTED;
+  HIP_TRY(hipSetDevice(w->device));
+  // the columns asked for, as rbd_simulate_step_derivatives with nx = nq + nv + ns: those of ∂x⁺/∂x, then those of ∂x⁺/∂τ
+  const int nx = m->nq + m->nv + (int)sim_ns(m), g0 = dx_dx ? 0 : nx, g1 = dx_dtau ? nx + m->nv : nx, ncol = std::max(1, g1 - g0);
+  const int width = sim_pass_width(w, std::max(ncol, nx + m->nv));
+  if ((st = sim_ensure(w, width, true))) return st;
+  Timed t(w);
+  w->last_kernel = kSimContactTanKernels;
+  const SimTanContact C{&o, s, nullptr};
+  return by_dtype(w->dtype, [&](auto t) {
+    return sim_tan_run<decltype(t)>(w, B, o.layout, q, v, tau, fext, dt, 1, ncol, true, g0, nullptr, nullptr, nullptr, nullptr, dx_dx, dx_dtau, &C);
   });
 }
 

@@ -186,7 +186,8 @@ struct rbd_ws {
   // tan_ntan directions, and for more than 64 coordinates the solve's own vectors — allocated by the first derivative call and when ntan grows
   bool tan_ready = false; BigModel tan{}; DevBuf d_tan_tbl, d_tan_rb, d_tan_scratch; long tan_threads = 0; int tan_ntan = 0;
   DevBuf d_tan_M, d_tan_L, d_tan_c, d_tan_vd, d_tan_rhs, d_tan_x;
-  // the simulate derivatives (rbd_simulate_jvp, rbd_simulate_step_derivatives): the stage states' values, and the tangents of one pass of sim_tan_w directions
+  // the simulate derivatives (rbd_simulate_jvp, rbd_simulate_step_derivatives): the stage states' values, and the tangents of one pass of sim_tan_w directions;
+  // with contact (rbd_simulate_contact_jvp, rbd_simulate_contact_step_derivatives) the saved initial s and the friction state's four tangents as well
   DevBuf d_sim_val, d_sim_tan; int sim_tan_w = 0;
   // the reverse-mode entry points (rbd_inverse_dynamics_vjp, rbd_dynamics_vjp): the adjoint scratch (adj_states states per launch), the cotangent of v̇
   // staged batch-innermost, λ = M⁻¹ v̇̄ when the caller passes no τ̄, and for more than 64 coordinates the solve's own vector

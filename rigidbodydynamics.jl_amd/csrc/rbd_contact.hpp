@@ -315,4 +315,20 @@ template <typename T> RBD_HD void contact_stage_adjoint(int stage, T dt, T snb, 
   }
 }
 
+// one launch of tangent_contact_stage_kernel (rbd_tangent_kernels.hip; rbd_simulate_contact_jvp, rbd_simulate_contact_step_derivatives): contact_stage_value on
+// Dual<T, N>, the friction state's share of what MkTanArgs is for (q, v).  Values (the call's layout Ls; sn may be s0 itself at stage 3) are written by chunk 0;
+// tangents are ColOut views (direction e of the pass at column e, rows of the ns values of s), each thread reads and writes only its own.
+template <typename T> struct CtTanStageArgs {
+  long B;
+  int ntan, ns, stage;  // directions of the pass, values of s per state, stage 0..3
+  T dt;
+  const T *s0, *sd;  // the step's start, ṡ at the stage state just evaluated
+  T* acc;            // Σ dt b_j ṡ_j (read at stages 1-3, written at 0-2)
+  T* sn;             // the next stage state (stage 3: the state after the step)
+  Layout Ls;
+  ColOut<T> ds0, dsd, dacc;
+  ColOut<T> os;      // tangent of sn at rows orow + …, direction e at column ocol + e
+  int ocol, orow;
+};
+
 }  // namespace rbd

@@ -142,6 +142,10 @@ template <typename T>
 hipError_t launch_point_adjoint(const BigModel& M, const PointPlan& P, const AdjArgs<T>& A, const PointAdjArgs<T>& C, void* scratch, long max_states, hipStream_t s);
 template <typename T> hipError_t launch_mk_stage_classes(MkAdjArgs<T> A, const int32_t* jn, int nn, const int32_t* jw, int nw, int adjoint, hipStream_t s);
 template <typename T>
-hipError_t launch_tangent_mk_load(long B, int ncol, int nq, int nv, int col0, int unit, const ColOut<T>& sq, const ColOut<T>& sv, const ColOut<T>& sd,
-                                  const ColOut<T>& dq, const ColOut<T>& dv, const ColOut<T>& dd, hipStream_t s);
+hipError_t launch_tangent_mk_load(long B, int ncol, int nq, int nv, int col0, int unit, int tau0, const ColOut<T>& sq, const ColOut<T>& sv,
+                                  const ColOut<T>& sd, const ColOut<T>& dq, const ColOut<T>& dv, const ColOut<T>& dd, hipStream_t s);
+template <typename T> struct CtTanStageArgs;  // rbd_contact.hpp
+template <typename T> hipError_t launch_tangent_contact_stage(const CtTanStageArgs<T>& A, hipStream_t s);
+template <typename T>
+hipError_t launch_tangent_contact_load(long B, int ncol, int ns, int col0, int unit, int s0col, const ColOut<T>& src, const ColOut<T>& ds, hipStream_t s);
 }

@@ -1,9 +1,10 @@
 // rbd_tangent_kernels.hip — the kernels of the derivative entry points (rbd_inverse_dynamics_jvp, rbd_dynamics_jvp, rbd_inverse_dynamics_derivatives,
 // rbd_dynamics_derivatives, rbd_simulate_jvp, rbd_simulate_step_derivatives, rbd_inverse_dynamics_vjp, rbd_dynamics_vjp, rbd_simulate_vjp, rbd_point_kinematics_vjp, rbd_contact_dynamics_jvp, rbd_dynamics_contact_jvp,
-// rbd_dynamics_contact_derivatives): the tangent RNEA
+// rbd_dynamics_contact_derivatives, rbd_simulate_contact_jvp, rbd_simulate_contact_step_derivatives): the tangent RNEA
 // (rbd_tangent.hpp) with one thread per (state, chunk of TAN_CHUNK directions) and its variant with the soft-contact step between the sweeps (rbd_contact.hpp),
 // the multi-right-hand-side triangular solve of dynamics! tangents against the
-// Cholesky factor of M, the tangent of the integrator's stage map (rbd_tangent_mk.hpp) with one thread per (state, joint, chunk), the adjoint RNEA
+// Cholesky factor of M, the tangent of the integrator's stage map (rbd_tangent_mk.hpp) with one thread per (state, joint, chunk) and of the friction state's
+// (rbd_contact.hpp contact_stage_value) with one thread per (state, value of s, chunk), the adjoint RNEA
 // (rbd_adjoint.hpp) with one thread per state, and the stage map's values and pullback (rbd_adjoint_mk.hpp) with one thread per (state, joint) of a
 // joint class.  Compiled with -ffinite-math-only -fno-signed-zeros (build.sh): the zero
 // tangents of the mechanism's constants fold out of the products.
@@ -198,10 +199,11 @@ template <typename T> hipError_t launch_tangent_mk_stage(const MkTanArgs<T>& A, 
 }
 
 // the initial tangents of a pass of ncol directions (thread = direction · B + state): columns col0 … of the caller's (dq, dv, dτ) (nullable: zero), or
-// with `unit` the unit vectors of the step Jacobians' columns — column g is e_g of (q; v) for g < nq + nv, else e_{g − nq − nv} of τ
+// with `unit` the unit vectors of the step Jacobians' columns — column g is e_g of (q; v) for g < nq + nv, and e_{g − tau0} of τ for g ≥ tau0 (tau0 = nq + nv;
+// with the friction state's columns between, nq + nv + ns)
 template <typename T>
-__global__ __launch_bounds__(256) void tangent_mk_load_kernel(long B, int ncol, int nq, int nv, int col0, int unit, ColOut<T> sq, ColOut<T> sv, ColOut<T> sd,
-                                                              ColOut<T> dq, ColOut<T> dv, ColOut<T> dd) {
+__global__ __launch_bounds__(256) void tangent_mk_load_kernel(long B, int ncol, int nq, int nv, int col0, int unit, int tau0, ColOut<T> sq, ColOut<T> sv,
+                                                              ColOut<T> sd, ColOut<T> dq, ColOut<T> dv, ColOut<T> dd) {
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (long)ncol * B) return;
   const int e = (int)(t / B), g = col0 + e;
@@ -210,16 +212,79 @@ __global__ __launch_bounds__(256) void tangent_mk_load_kernel(long B, int ncol, 
   for (int r = 0; r < nq; ++r) *dq.at(e, r, st) = unit ? T(g == r ? 1 : 0) : src(sq, r);
   for (int r = 0; r < nv; ++r) {
     *dv.at(e, r, st) = unit ? T(g == nq + r ? 1 : 0) : src(sv, r);
-    *dd.at(e, r, st) = unit ? T(g == nq + nv + r ? 1 : 0) : src(sd, r);
+    *dd.at(e, r, st) = unit ? T(g == tau0 + r ? 1 : 0) : src(sd, r);
   }
 }
 
 template <typename T>
-hipError_t launch_tangent_mk_load(long B, int ncol, int nq, int nv, int col0, int unit, const ColOut<T>& sq, const ColOut<T>& sv, const ColOut<T>& sd,
-                                  const ColOut<T>& dq, const ColOut<T>& dv, const ColOut<T>& dd, hipStream_t s) {
+hipError_t launch_tangent_mk_load(long B, int ncol, int nq, int nv, int col0, int unit, int tau0, const ColOut<T>& sq, const ColOut<T>& sv,
+                                  const ColOut<T>& sd, const ColOut<T>& dq, const ColOut<T>& dv, const ColOut<T>& dd, hipStream_t s) {
   const long total = (long)ncol * B;
   if (total == 0) return hipSuccess;
-  hipLaunchKernelGGL(tangent_mk_load_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, B, ncol, nq, nv, col0, unit, sq, sv, sd, dq, dv, dd);
+  hipLaunchKernelGGL(tangent_mk_load_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, B, ncol, nq, nv, col0, unit, tau0, sq, sv, sd, dq, dv, dd);
+  return hipGetLastError();
+}
+
+// ---- simulate tangents with soft contact: the friction state through the tableau, one thread per (state, value of s, chunk of N directions), thread =
+// (chunk · ns + row) · B + state.  contact_stage_value on Dual<T, N> (rbd_contact.hpp): values and tangents of a stage in one launch (it stands where
+// contact_stage_value_kernel does on the value route).  Elementwise: every internal buffer is read and written contiguously over the state index.
+template <typename T, int N>
+__global__ __launch_bounds__(64) void tangent_contact_stage_kernel(CtTanStageArgs<T> A) {
+  using D = Dual<T, N>;
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long nchunks = (A.ntan + N - 1) / N;
+  if (t >= nchunks * A.ns * A.B) return;
+  const long st = t % A.B, r = t / A.B;
+  const int row = (int)(r % A.ns), chunk = (int)(r / A.ns);
+  const int e0 = chunk * N;
+  const long vo = (long)row * A.Ls.sk + layout_base(A.Ls, st);
+  auto load = [&](const T* val, const ColOut<T>& tan) {
+    D x(val ? val[vo] : T(0));
+#pragma unroll
+    for (int j = 0; j < N; ++j) x.d[j] = e0 + j < A.ntan ? *tan.at(e0 + j, row, st) : T(0);
+    return x;
+  };
+  // (the tableau is linear: no tangent depends on a value, so only chunk 0, which writes the values, reads them — the other chunks must not, at stage 3,
+  // where sn may be s0 itself; stage 0 reads neither the running sum's value nor its tangent)
+  const bool rv = chunk == 0;
+  const D s0 = load(rv ? A.s0 : nullptr, A.ds0), sd = load(rv ? A.sd : nullptr, A.dsd);
+  D acc = A.stage > 0 ? load(rv ? A.acc : nullptr, A.dacc) : D(T(0)), sn;
+  contact_stage_value<D>(A.stage, A.dt, s0, sd, acc, sn);
+  auto store = [&](T* val, const ColOut<T>& tan, int col0, int trow, const D& x) {
+    if (chunk == 0 && val) val[vo] = x.v;
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+      if (e0 + j < A.ntan)
+        if (T* o = tan.at(col0 + e0 + j, trow, st)) *o = x.d[j];
+  };
+  store(A.sn, A.os, A.ocol, A.orow + row, sn);
+  if (A.stage < 3) store(A.acc, A.dacc, 0, row, acc);
+}
+
+template <typename T> hipError_t launch_tangent_contact_stage(const CtTanStageArgs<T>& A, hipStream_t s) {
+  constexpr int N = TanChunk<T>::N;
+  const long total = (long)((A.ntan + N - 1) / N) * A.ns * A.B;
+  if (total == 0) return hipSuccess;
+  hipLaunchKernelGGL((tangent_contact_stage_kernel<T, N>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, A);
+  return hipGetLastError();
+}
+
+// the friction state's initial tangents of a pass of ncol directions (thread = direction · B + state), beside tangent_mk_load_kernel's (dq, dv, dτ): columns
+// col0 … of the caller's ds, or with `unit` the unit vectors — column g is e_{g − s0col} of s (s0col = nq + nv), zero for every other g
+template <typename T>
+__global__ __launch_bounds__(256) void tangent_contact_load_kernel(long B, int ncol, int ns, int col0, int unit, int s0col, ColOut<T> src, ColOut<T> ds) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)ncol * B) return;
+  const int e = (int)(t / B), g = col0 + e;
+  const long st = t % B;
+  for (int r = 0; r < ns; ++r) *ds.at(e, r, st) = unit ? T(g == s0col + r ? 1 : 0) : *src.at(g, r, st);
+}
+
+template <typename T>
+hipError_t launch_tangent_contact_load(long B, int ncol, int ns, int col0, int unit, int s0col, const ColOut<T>& src, const ColOut<T>& ds, hipStream_t s) {
+  const long total = (long)ncol * B;
+  if (total == 0) return hipSuccess;
+  hipLaunchKernelGGL(tangent_contact_load_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, B, ncol, ns, col0, unit, s0col, src, ds);
   return hipGetLastError();
 }
 
@@ -396,8 +461,10 @@ template <typename T> hipError_t launch_mk_stage_classes(MkAdjArgs<T> A, const i
   template hipError_t launch_tangent_solve<T>(int, long, int, int, const void*, Layout, const void*, int, const ColOut<T>&, void*, hipStream_t);          \
   template hipError_t launch_symmetrize<T>(int, long, void*, Layout, hipStream_t);                                                                   \
   template hipError_t launch_tangent_mk_stage<T>(const MkTanArgs<T>&, hipStream_t);                                                                     \
-  template hipError_t launch_tangent_mk_load<T>(long, int, int, int, int, int, const ColOut<T>&, const ColOut<T>&, const ColOut<T>&, const ColOut<T>&,   \
+  template hipError_t launch_tangent_mk_load<T>(long, int, int, int, int, int, int, const ColOut<T>&, const ColOut<T>&, const ColOut<T>&, const ColOut<T>&,   \
                                                 const ColOut<T>&, const ColOut<T>&, hipStream_t);                                                        \
+  template hipError_t launch_tangent_contact_stage<T>(const CtTanStageArgs<T>&, hipStream_t);                                                          \
+  template hipError_t launch_tangent_contact_load<T>(long, int, int, int, int, int, const ColOut<T>&, const ColOut<T>&, hipStream_t);                    \
   template hipError_t launch_adjoint_rnea<T>(const BigModel&, const AdjArgs<T>&, void*, long, hipStream_t);                                              \
   template hipError_t launch_point_adjoint<T>(const BigModel&, const PointPlan&, const AdjArgs<T>&, const PointAdjArgs<T>&, void*, long, hipStream_t);         \
   template hipError_t launch_stage_rows<T>(int, long, const void*, Layout, void*, hipStream_t);                                                        \

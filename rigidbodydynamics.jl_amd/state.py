@@ -1334,3 +1334,62 @@ def dynamics_contact_derivatives_(state: MechanismState, torques: Optional[torch
                                                       _ptr(dsd_dv), _ptr(dsd_ds), ctypes.byref(opts))
     _raise(st, "rbd_dynamics_contact_derivatives")
     return dvd_dq, dvd_dv, dvd_ds, dvd_dtau, dsd_dq, dsd_dv, dsd_ds
+
+
+# ---- forward mode through simulate steps with soft contact (rbd_simulate_contact_jvp, rbd_simulate_contact_step_derivatives): simulate_jvp_ /
+# simulate_step_derivatives_ with the friction state beside (q, v), x = (q; v; s); q, v, s (advanced in place) default to the state's.
+
+def simulate_contact_jvp_(dq: torch.Tensor, dv: torch.Tensor, ds: torch.Tensor, state: MechanismState, ntan: int, dt: float, nsteps: int = 1,
+                          torques: Optional[torch.Tensor] = None, dtorques: Optional[torch.Tensor] = None, externalwrenches: Optional[torch.Tensor] = None,
+                          dexternalwrenches: Optional[torch.Tensor] = None, q: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None,
+                          s: Optional[torch.Tensor] = None):
+    """`nsteps` steps of `simulate_` of a mechanism with contact points (constant `torques` and `externalwrenches`) with `ntan` tangent directions carried
+    along: q, v, s and the tangents `dq` (B, ntan·nq), `dv` (B, ntan·nv), `ds` (B, ntan·ns) are advanced in place.  `dtorques` / `dexternalwrenches` are held
+    over every stage of every step.  The derivative is that of the branch each (point, half-space) pair takes at each stage state."""
+    f = state.flat
+    if int(ntan) <= 0:
+        raise ValueError("ntan must be positive")
+    if not float(dt) > 0:
+        raise ValueError("dt must be positive")
+    if int(nsteps) < 0:
+        raise ValueError("nsteps must be non-negative")
+    if dq is None or dv is None or ds is None:
+        raise ValueError("dq, dv and ds are required (in / out)")
+    q, v, s = _contact_qvs(state, q, v, s)
+    _check_tangent(state, dq, f.nq, ntan, "dq")
+    _check_tangent(state, dv, f.nv, ntan, "dv")
+    _check_tangent(state, ds, f.ns, ntan, "ds")
+    state._check(torques, f.nv, "torques")
+    _check_tangent(state, dtorques, f.nv, ntan, "dτ")
+    state._check(externalwrenches, 6 * f.n_bodies, "externalwrenches")
+    _check_tangent(state, dexternalwrenches, 6 * f.n_bodies, ntan, "dexternalwrenches")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_simulate_contact_jvp(state.ws.handle, state.batch, int(ntan), _ptr(q), _ptr(v), _ptr(s), _ptr(torques), _ptr(externalwrenches),
+                                              ctypes.c_double(dt), int(nsteps), _ptr(dq), _ptr(dv), _ptr(ds), _ptr(dtorques), _ptr(dexternalwrenches),
+                                              ctypes.byref(opts))
+    _raise(st, "rbd_simulate_contact_jvp")
+    return dq, dv, ds
+
+
+def simulate_contact_step_derivatives_(state: MechanismState, dt: float, torques: Optional[torch.Tensor] = None, dx_dx: Optional[torch.Tensor] = None,
+                                       dx_dtau: Optional[torch.Tensor] = None, externalwrenches: Optional[torch.Tensor] = None,
+                                       q: Optional[torch.Tensor] = None, v: Optional[torch.Tensor] = None, s: Optional[torch.Tensor] = None):
+    """One step of `simulate_` of a mechanism with contact points (q, v, s advanced in place) and its Jacobians with x = (q; v; s), nx = nq + nv + ns:
+    dx_dx = ∂x⁺/∂x (B, nx·nx), dx_dtau = ∂x⁺/∂τ (B, nx·nv), column-major per state (jacobian_view(t, state, nx, cols)); both optional; the external
+    wrenches held fixed."""
+    f = state.flat
+    nx = f.nq + f.nv + f.ns
+    if not float(dt) > 0:
+        raise ValueError("dt must be positive")
+    q, v, s = _contact_qvs(state, q, v, s)
+    state._check(torques, f.nv, "torques")
+    state._check(dx_dx, nx * nx, "dx_dx")
+    state._check(dx_dtau, nx * f.nv, "dx_dtau")
+    state._check(externalwrenches, 6 * f.n_bodies, "externalwrenches")
+    state.ws.use_current_stream()
+    opts = state._opts()
+    st = _capi.lib().rbd_simulate_contact_step_derivatives(state.ws.handle, state.batch, _ptr(q), _ptr(v), _ptr(s), _ptr(torques), _ptr(externalwrenches),
+                                                           ctypes.c_double(dt), _ptr(dx_dx), _ptr(dx_dtau), ctypes.byref(opts))
+    _raise(st, "rbd_simulate_contact_step_derivatives")
+    return dx_dx, dx_dtau
