@@ -34,6 +34,22 @@
 #ifndef RBD_BANK_HANDOFF_LDS
 #define RBD_BANK_HANDOFF_LDS 0  // 1: every bottom-up hand-off through the exchange columns
 #endif
+// The program compiled per mechanism (RBD_BANK_FIXED_NL: level loops unrolled) has no loop-carried state, so what the looped kernels do to keep the register
+// allocator from copying it is not needed there.  Each part has its own switch (default: on in the compiled program, off in the looped kernels):
+#ifdef RBD_BANK_FIXED_NL
+#define RBD_BANK_UNROLLED 1
+#else
+#define RBD_BANK_UNROLLED 0
+#endif
+#ifndef RBD_BANK_COMMIT_INPLACE
+#define RBD_BANK_COMMIT_INPLACE RBD_BANK_UNROLLED  // 1: a level's new values are computed AND assigned under the exec mask of the lanes at that level (no massign)
+#endif
+#ifndef RBD_BANK_LEAN_INIT
+#define RBD_BANK_LEAN_INIT RBD_BANK_UNROLLED  // 1: no zero fill of values that are overwritten before anyone reads them, or that only the 6-dof lanes read
+#endif
+#ifndef RBD_BANK_ONE_BASE
+#define RBD_BANK_ONE_BASE RBD_BANK_UNROLLED  // 1: the 6-dof joint's q / v / tau / q̇ elements at one base address plus multiples of the stride
+#endif
 
 // Experiment (scripts/build_bank_variant.sh fixed -DRBD_BANK_FIXED_NL=11 -DRBD_BANK_FIXED_L0=5 "-DRBD_BANK_FIXED_NS=0,3,1,1,3,1,1,1,1,1,1"): the level structure of ONE
 // mechanism as compile-time constants and the level loops unrolled — what a per-mechanism compilation of this kernel (as rbd_jit.hip does for the large-batch
@@ -152,16 +168,41 @@ template <typename T> RBD_DEV void load_bank_body(const BankModel& M, int k, lon
   b.plane = b.parent >= 0 ? b.base + b.parent : b.lane;  // parent slot (of the parent's bank) in this state's lane group
 }
 
+// RBD_BANK_ONE_BASE: load_body_wrench / store_joint_v (rbd_lane.hpp) with the element's address formed once per lane and the elements at multiples of the
+// stride from it, under ONE exec mask each (the forms in rbd_lane.hpp multiply the 64-bit stride again for every element, each under a mask of its own)
+template <typename T> RBD_DEV void bank_load_wrench(const Body<T>& b, const T* __restrict__ f, Layout L, T* w) {
+  if (!RBD_BANK_ONE_BASE) { load_body_wrench(b, f, L, w); return; }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) w[k] = T(0);
+  if (f != nullptr && b.valid) {
+    const T* const fp = f + ((long)(6 * b.orig) * L.sk + b.state * L.sb);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) w[k] = fp[k * L.sk];
+  }
+}
+// (aba_bank_body's joints have 0, 1 or 6 velocities: see Scope above)
+template <typename T> RBD_DEV void bank_store_v(const Body<T>& b, T* __restrict__ out, Layout L, const T* x) {
+  if (!RBD_BANK_ONE_BASE) { store_joint_v(b, out, L, x); return; }
+  const int n = joint_nv(b.jtype);
+  if (b.valid && n >= 1) {
+    T* const op = out + ((long)b.voff * L.sk + b.state * L.sb);
+    op[0] = x[0];
+    if (n == 6) {
+#pragma unroll
+      for (int k = 1; k < 6; ++k) op[k * L.sk] = x[k];
+    }
+  }
+}
+
 // ---- forward kinematics -------------------------------------------------------------------------------------------------------
 // The sweep carries K = (R 9, p 3, Tw 6) per lane [+ vJ 6 in the generic form].  SIMPLE (revolute joints below level 0): ta = (axis, joint
 // velocity), the joint twist is S v with S = X (a; 0) = (R a; p x R a); S itself and the bias term are formed after the sweep, for every lane
 // at once (terms()).  The new values are computed by EVERY lane and committed in the lanes at level l (massign).
-template <typename T, bool SIMPLE>
-RBD_DEV void bank_fk_commit(bool mine, BankRegs<T>& c, const T* k18 /* the parent's R 9, p 3, Tw 6 */, const T* XR, const T* Xp, const T* tl) {
+// RBD_BANK_COMMIT_INPLACE (the unrolled program: nothing is loop-carried): computed and assigned by the lanes at level l alone, under their exec mask.
+template <typename T, bool SIMPLE> RBD_DEV void bank_fk_new(const T* k18 /* the parent's R 9, p 3, Tw 6 */, const T* XR, const T* Xp, const T* tl, T* n) {
   const T* pR = k18;
   const T* pp = k18 + 9;
   const T* pT = k18 + 12;
-  T n[24];
   matmul3(pR, XR, n);
   matvec3(pR, Xp, n + 9);
 #pragma unroll
@@ -172,12 +213,25 @@ RBD_DEV void bank_fk_commit(bool mine, BankRegs<T>& c, const T* k18 /* the paren
     cross3(n + 9, S, S + 3);
 #pragma unroll
     for (int k = 0; k < 6; ++k) n[12 + k] = pT[k] + S[k] * tl[3];
-    massign<T, 18>(mine, c.K, n);
   } else {
     xmotion(n, n + 9, tl, n + 18);
 #pragma unroll
     for (int k = 0; k < 6; ++k) n[12 + k] = pT[k] + n[18 + k];
-    massign<T, 24>(mine, c.K, n);
+  }
+}
+template <typename T, bool SIMPLE> RBD_DEV void bank_fk_commit(bool mine, BankRegs<T>& c, const T* k18, const T* XR, const T* Xp, const T* tl) {
+  constexpr int NK = SIMPLE ? 18 : 24;
+  T n[24];
+  if (RBD_BANK_COMMIT_INPLACE) {
+    if (mine) {
+      RBD_KEEP_BRANCH();
+      bank_fk_new<T, SIMPLE>(k18, XR, Xp, tl, n);
+#pragma unroll
+      for (int k = 0; k < NK; ++k) c.K[k] = n[k];
+    }
+  } else {
+    bank_fk_new<T, SIMPLE>(k18, XR, Xp, tl, n);
+    massign<T, NK>(mine, c.K, n);
   }
 }
 // level l inside a bank.  On most levels every body is the first child of its parent = the previous lane: (R, p, Tw) arrive by DPP.  On the
@@ -289,15 +343,30 @@ template <typename T, int MODE> RBD_DEV void bank_handoff(int l, int ns, const B
 }
 
 // v̇ = D^-1 (u - U'a'), a = a' + S v̇ with a' = a_parent + cb — computed by every lane, committed in the lanes of `mine`
-template <typename T> RBD_DEV void bank_joint_accel(bool mine, BankRegs<T>& r, const T* a_parent) {
-  T ap[6], n[6];
+// (RBD_BANK_COMMIT_INPLACE: computed and assigned by the lanes of `mine` alone)
+template <typename T> RBD_DEV T bank_joint_accel_new(const BankRegs<T>& r, const T* a_parent, T* n) {
+  T ap[6];
 #pragma unroll
   for (int k = 0; k < 6; ++k) ap[k] = a_parent[k] + r.cb[k];
   const T x = r.Dinv * (r.u - dot6(r.U, ap));
 #pragma unroll
   for (int k = 0; k < 6; ++k) n[k] = ap[k] + r.S[k] * x;
-  massign<T, 6>(mine, r.acc, n);
-  r.vd[0] = mine ? x : r.vd[0];
+  return x;
+}
+template <typename T> RBD_DEV void bank_joint_accel(bool mine, BankRegs<T>& r, const T* a_parent) {
+  T n[6];
+  if (RBD_BANK_COMMIT_INPLACE) {
+    if (mine) {
+      RBD_KEEP_BRANCH();
+      r.vd[0] = bank_joint_accel_new(r, a_parent, n);
+#pragma unroll
+      for (int k = 0; k < 6; ++k) r.acc[k] = n[k];
+    }
+  } else {
+    const T x = bank_joint_accel_new(r, a_parent, n);
+    massign<T, 6>(mine, r.acc, n);
+    r.vd[0] = mine ? x : r.vd[0];
+  }
 }
 // top-down acceleration step at level l inside a bank (same hop rules as bank_fk_step)
 template <typename T> RBD_DEV void bank_accel_step(const BankModel& M, int l, bool perm, BankRegs<T>& c, Pair2<T>* lds) {
@@ -356,10 +425,12 @@ RBD_DEV void aba_bank_body(const BankModel& M, long B, typename InPtr<T, !FUSED>
       qj[0] = qp[0];
       vj[0] = hv ? v[va] : T(0);
       c.tj[0] = ht ? tau[va] : T(0);
+      if (FUSED || !RBD_BANK_LEAN_INIT) {  // (elements 1.. are read by the 6-dof lanes alone — and by the integrator stage of the fused form)
 #pragma unroll
-      for (int k2 = 1; k2 < 7; ++k2) qj[k2] = T(0);
+        for (int k2 = 1; k2 < 7; ++k2) qj[k2] = T(0);
 #pragma unroll
-      for (int k2 = 1; k2 < 6; ++k2) { vj[k2] = T(0); c.tj[k2] = T(0); }
+        for (int k2 = 1; k2 < 6; ++k2) { vj[k2] = T(0); c.tj[k2] = T(0); }
+      }
       if (fl) {
         RBD_KEEP_BRANCH();
 #pragma unroll
@@ -367,10 +438,16 @@ RBD_DEV void aba_bank_body(const BankModel& M, long B, typename InPtr<T, !FUSED>
         if (hv) {
 #pragma unroll
           for (int k2 = 1; k2 < 6; ++k2) vj[k2] = v[va + k2 * Lv.sk];
+        } else if (!FUSED && RBD_BANK_LEAN_INIT) {
+#pragma unroll
+          for (int k2 = 1; k2 < 6; ++k2) vj[k2] = T(0);
         }
         if (ht) {
 #pragma unroll
           for (int k2 = 1; k2 < 6; ++k2) c.tj[k2] = tau[va + k2 * Lv.sk];
+        } else if (!FUSED && RBD_BANK_LEAN_INIT) {
+#pragma unroll
+          for (int k2 = 1; k2 < 6; ++k2) c.tj[k2] = T(0);
         }
       }
     } else {
@@ -404,8 +481,14 @@ RBD_DEV void aba_bank_body(const BankModel& M, long B, typename InPtr<T, !FUSED>
           o[2] = (z * vj[0] + w * vj[1] - x * vj[2]) * T(0.5);
           o[3] = (-y * vj[0] + x * vj[1] + w * vj[2]) * T(0.5);
           matvec3(Rj, vj + 3, o + 4);
+          if (RBD_BANK_ONE_BASE) {
+            T* const qd = qdot + ((long)c.b.qoff * Lq.sk + c.b.state * Lq.sb);
 #pragma unroll
-          for (int k = 0; k < 7; ++k) qdot[(long)(c.b.qoff + k) * Lq.sk + c.b.state * Lq.sb] = o[k];
+            for (int k = 0; k < 7; ++k) qd[k * Lq.sk] = o[k];
+          } else {
+#pragma unroll
+            for (int k = 0; k < 7; ++k) qdot[(long)(c.b.qoff + k) * Lq.sk + c.b.state * Lq.sb] = o[k];
+          }
         }
       } else if (qdot != nullptr && c.b.valid) {
         qdot[(long)c.b.qoff * Lq.sk + c.b.state * Lq.sb] = vj[0];
@@ -471,7 +554,7 @@ RBD_DEV void aba_bank_body(const BankModel& M, long B, typename InPtr<T, !FUSED>
     T Io[21], po[6];
     sym6_from_inertia(I, Io);
     momentum_cross(I, c.Tw(), po);
-    load_body_wrench(c.b, fext, Lf, fe);
+    bank_load_wrench(c.b, fext, Lf, fe);
     // (lanes without a body are never read by anyone: takers add only what their own children give, under their exec mask)
 #pragma unroll
     for (int i = 0; i < 21; ++i) c.IA[i] = accumulate ? c.IA[i] + Io[i] : Io[i];
@@ -563,8 +646,11 @@ RBD_BANK_UNROLL
   RBD_MARK(9);
 
   // ---- top-down: accelerations and v̇ ----
+  // (RBD_BANK_LEAN_INIT: every lane with a body commits its acc and the v̇ elements it stores at its own level; what the other lanes hold is moved but never used)
+  if (!RBD_BANK_LEAN_INIT) {
 #pragma unroll
-  for (int i = 0; i < 6; ++i) { r0.acc[i] = T(0); r0.vd[i] = T(0); }
+    for (int i = 0; i < 6; ++i) { r0.acc[i] = T(0); r0.vd[i] = T(0); }
+  }
   {
     const T a0[6] = {T(0), T(0), T(0), T(-M.gravity[0]), T(-M.gravity[1]), T(-M.gravity[2])};  // a_world = -gravity
     BankRegs<T>& c = r0;
@@ -581,16 +667,22 @@ RBD_BANK_UNROLL
       for (int i = 0; i < 6; ++i) d[i] = fa[i] - a0[i];
       lds_get<T, 12>(col, PK_KIN, k12);
       xmotion_inv(k12, k12 + 9, d, fv);
+      if (RBD_BANK_COMMIT_INPLACE) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) { c.acc[i] = fa[i]; c.vd[i] = fv[i]; }
+      }
     }
-    massign<T, 6>(fl0, c.acc, fa);
-    massign<T, 6>(fl0, c.vd, fv);
+    if (!RBD_BANK_COMMIT_INPLACE) {
+      massign<T, 6>(fl0, c.acc, fa);
+      massign<T, 6>(fl0, c.vd, fv);
+    }
     bank_joint_accel(c.b.level == 0 && !fl0, c, a0);
   }
 RBD_BANK_UNROLL
   for (int l = 1; l < RBD_BK_L0; ++l) bank_accel_step<T>(M, l, RBD_BK_PERM(l), r0, lds);
   RBD_MARK(10);
-  if (vdot) store_joint_v(r0.b, vdot, Lv, r0.vd);
-  if (FUSED) store_joint_v(r0.b, (T*)F.W.vd[F.stage], Lv, r0.vd);
+  if (vdot) bank_store_v(r0.b, vdot, Lv, r0.vd);
+  if (FUSED) bank_store_v(r0.b, (T*)F.W.vd[F.stage], Lv, r0.vd);
   {
     T f20[20];
     lds_get<T, 20>(col, PK_FWD, f20);
@@ -599,8 +691,7 @@ RBD_BANK_UNROLL
       r1.U[i] = f20[i];
       r1.S[i] = f20[8 + i];
       r1.cb[i] = f20[14 + i];
-      r1.acc[i] = T(0);
-      r1.vd[i] = T(0);
+      if (!RBD_BANK_LEAN_INIT) { r1.acc[i] = T(0); r1.vd[i] = T(0); }
     }
     r1.Dinv = f20[6];
     r1.u = f20[7];
@@ -616,8 +707,8 @@ RBD_BANK_UNROLL
 RBD_BANK_UNROLL
   for (int l = RBD_BK_L0 + 1; l < RBD_BK_NL; ++l) bank_accel_step<T>(M, l, RBD_BK_PERM(l), r1, lds);
   RBD_MARK(11);
-  if (vdot) store_joint_v(r1.b, vdot, Lv, r1.vd);
-  if (FUSED) store_joint_v(r1.b, (T*)F.W.vd[F.stage], Lv, r1.vd);
+  if (vdot) bank_store_v(r1.b, vdot, Lv, r1.vd);
+  if (FUSED) bank_store_v(r1.b, (T*)F.W.vd[F.stage], Lv, r1.vd);
 }
 #ifndef RBD_BANK_FIXED_NL
 template <typename T, bool FUSED, bool SIMPLE>
@@ -651,13 +742,13 @@ template <typename T> struct RneaRegs {
 // kinematics step with spatial accelerations (spatial_accelerations! :387-417): a_b = a_p + (-T_b) x T_p + X a_joint — computed by every lane
 // from the parent's values k24, committed in the lanes of `mine`
 // SIMPLE: tl = (axis, joint velocity, joint acceleration): joint twist and acceleration are S v, S v̇ with S = (R a; p x R a)
-template <typename T, bool SIMPLE>
-RBD_DEV void rnea_fk_commit(bool mine, RneaRegs<T>& c, const T* k24, const T* XR, const T* Xp, const T* tl, const T* al) {
+// (RBD_BANK_COMMIT_INPLACE: computed and assigned by the lanes of `mine` alone, as in bank_fk_commit)
+template <typename T, bool SIMPLE> RBD_DEV void rnea_fk_new(const T* k24, const T* XR, const T* Xp, const T* tl, const T* al, T* n) {
   const T* pR = k24;
   const T* pp = k24 + 9;
   const T* pT = k24 + 12;
   const T* pa = k24 + 18;
-  T n[24], vJ[6], nT[6], cr[6], aj[6];
+  T vJ[6], nT[6], cr[6], aj[6];
   matmul3(pR, XR, n);
   matvec3(pR, Xp, n + 9);
 #pragma unroll
@@ -677,7 +768,21 @@ RBD_DEV void rnea_fk_commit(bool mine, RneaRegs<T>& c, const T* k24, const T* XR
   se3_comm(nT, pT, cr);
 #pragma unroll
   for (int k = 0; k < 6; ++k) n[18 + k] = pa[k] + cr[k] + aj[k];
-  massign<T, 24>(mine, c.K, n);
+}
+template <typename T, bool SIMPLE>
+RBD_DEV void rnea_fk_commit(bool mine, RneaRegs<T>& c, const T* k24, const T* XR, const T* Xp, const T* tl, const T* al) {
+  T n[24];
+  if (RBD_BANK_COMMIT_INPLACE) {
+    if (mine) {
+      RBD_KEEP_BRANCH();
+      rnea_fk_new<T, SIMPLE>(k24, XR, Xp, tl, al, n);
+#pragma unroll
+      for (int k = 0; k < 24; ++k) c.K[k] = n[k];
+    }
+  } else {
+    rnea_fk_new<T, SIMPLE>(k24, XR, Xp, tl, al, n);
+    massign<T, 24>(mine, c.K, n);
+  }
 }
 template <typename T, bool SIMPLE>
 RBD_DEV void rnea_fk_step(const BankModel& M, int l, bool perm, RneaRegs<T>& c, Pair2<T>* lds, const T* XR, const T* Xp, const T* tl, const T* al) {
@@ -746,10 +851,12 @@ RBD_DEV void rnea_bank_body(const BankModel& M, long B, int ncol, const T* __res
       qj[0] = qp[0];
       vj[0] = hv ? v[va] : T(0);
       aj[0] = ha ? vdot[va] : T(0);
+      if (!RBD_BANK_LEAN_INIT) {  // (elements 1.. are read by the 6-dof lanes alone)
 #pragma unroll
-      for (int k2 = 1; k2 < 7; ++k2) qj[k2] = T(0);
+        for (int k2 = 1; k2 < 7; ++k2) qj[k2] = T(0);
 #pragma unroll
-      for (int k2 = 1; k2 < 6; ++k2) { vj[k2] = T(0); aj[k2] = T(0); }
+        for (int k2 = 1; k2 < 6; ++k2) { vj[k2] = T(0); aj[k2] = T(0); }
+      }
       if (fl) {
         RBD_KEEP_BRANCH();
 #pragma unroll
@@ -757,10 +864,16 @@ RBD_DEV void rnea_bank_body(const BankModel& M, long B, int ncol, const T* __res
         if (hv) {
 #pragma unroll
           for (int k2 = 1; k2 < 6; ++k2) vj[k2] = v[va + k2 * Lv.sk];
+        } else if (RBD_BANK_LEAN_INIT) {
+#pragma unroll
+          for (int k2 = 1; k2 < 6; ++k2) vj[k2] = T(0);
         }
         if (ha) {
 #pragma unroll
           for (int k2 = 1; k2 < 6; ++k2) aj[k2] = vdot[va + k2 * Lv.sk];
+        } else if (RBD_BANK_LEAN_INIT) {
+#pragma unroll
+          for (int k2 = 1; k2 < 6; ++k2) aj[k2] = T(0);
         }
       }
     } else {
@@ -793,8 +906,14 @@ RBD_DEV void rnea_bank_body(const BankModel& M, long B, int ncol, const T* __res
           o[2] = (z * vj[0] + w * vj[1] - x * vj[2]) * T(0.5);
           o[3] = (-y * vj[0] + x * vj[1] + w * vj[2]) * T(0.5);
           matvec3(Rj, vj + 3, o + 4);
+          if (RBD_BANK_ONE_BASE) {
+            T* const qd = qdot + ((long)c.b.qoff * Lq.sk + c.b.state * Lq.sb);
 #pragma unroll
-          for (int k = 0; k < 7; ++k) qdot[(long)(c.b.qoff + k) * Lq.sk + c.b.state * Lq.sb] = o[k];
+            for (int k = 0; k < 7; ++k) qd[k * Lq.sk] = o[k];
+          } else {
+#pragma unroll
+            for (int k = 0; k < 7; ++k) qdot[(long)(c.b.qoff + k) * Lq.sk + c.b.state * Lq.sb] = o[k];
+          }
         }
       } else if (qdot != nullptr && c.b.valid) {
         qdot[(long)c.b.qoff * Lq.sk + c.b.state * Lq.sb] = vj[0];
@@ -834,7 +953,7 @@ RBD_DEV void rnea_bank_body(const BankModel& M, long B, int ncol, const T* __res
     inertia_to_root(Jb, mc, c.rb[RB_M], c.R(), c.p(), I);
     mul_inertia(I, c.acc(), Ia);
     momentum_cross(I, c.Tw(), x);
-    load_body_wrench(c.b, fext, Lf, fe);
+    bank_load_wrench(c.b, fext, Lf, fe);
 #pragma unroll
     for (int k = 0; k < 6; ++k) c.w[k] = Ia[k] + x[k] - fe[k];
     if (acc_out != nullptr && c.b.valid) store6(acc_out, 6L * c.b.orig, Lf, c.b.state, c.acc(), out_vec);
