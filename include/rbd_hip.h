@@ -234,9 +234,10 @@ int rbd_sync(rbd_ws_t* ws);
  * fext[6*n_bodies×B] external wrench on each moving body in the ROOT frame,
  * (torque; force) (NULL => none, like NullDict); outputs vdot[nv×B],
  * qdot[nq×B] (nullable), lambda[nc×B] (nullable).                              */
-/* Mechanisms WITH contact points and an environment: rbd_dynamics / rbd_simulate / rbd_mk_stage return RBD_ERR_UNSUPPORTED — the reference's
+/* Mechanisms WITH contact points and an environment: rbd_dynamics / rbd_simulate / rbd_simulate_controlled return RBD_ERR_UNSUPPORTED — the reference's
  * dynamics! always adds the contact wrenches (src/mechanism_algorithms.jl:849-856), which needs the additional state: use
- * rbd_dynamics_contact / rbd_simulate_contact. */
+ * rbd_dynamics_contact / rbd_simulate_contact / rbd_simulate_contact_controlled.  rbd_mk_stage takes them: its stage covers (q, v) only, and a caller with a
+ * host-side controller carries the additional state through the same tableau beside it (rbd_dynamics_contact at every stage state). */
 int rbd_dynamics(rbd_ws_t* ws, int32_t B, const void* q, const void* v, const void* tau,
                  const void* fext, void* vdot, void* qdot, void* lambda, const rbd_opts_t* opts);
 
@@ -320,7 +321,7 @@ int rbd_mk_stage(rbd_ws_t* ws, int32_t B, int32_t stage, double dt, void* q, voi
  *   RBD_CONTROL_PD       : τ_i = tau_i − kp_i (q_i − q_des_i) − kd_i v_i on every Revolute / Prismatic joint, evaluated on the STAGE state inside
  *                          the dynamics launch (other joint types: τ = tau).  kp, kd: [nv] gains, q_des: nq × B (NULL = 0), all DEVICE arrays of
  *                          the workspace's scalar type.
- * Device memory only (opts->memory = RBD_MEM_DEVICE); tree mechanisms without contact points. */
+ * Device memory only (opts->memory = RBD_MEM_DEVICE); tree mechanisms without contact points (with them: rbd_simulate_contact_controlled). */
 enum { RBD_CONTROL_CONSTANT = 0, RBD_CONTROL_TABLE = 1, RBD_CONTROL_PD = 2 };
 typedef struct rbd_control {
   int32_t kind;       /* RBD_CONTROL_*                                   */
@@ -348,6 +349,21 @@ int rbd_dynamics_contact(rbd_ws_t* ws, int32_t B, const void* q, const void* v, 
                          void* sdot, void* contactwrenches, void* totalwrenches, const rbd_opts_t* opts);
 int rbd_simulate_contact(rbd_ws_t* ws, int32_t B, void* q, void* v, void* s, const void* tau, const void* fext, double dt, int32_t nsteps,
                          const rbd_opts_t* opts);
+
+/* rbd_simulate_contact_controlled (700 addition): `simulate(state, T, control!)` of a mechanism with contact points — rbd_simulate_contact's step (Munthe-Kaas
+ * RK4, the friction state s through the same tableau and reset by contact_dynamics! at each stage state) with rbd_simulate_controlled's device-side controllers:
+ *   RBD_CONTROL_CONSTANT : τ = tau (NULL = 0) — rbd_simulate_contact's result to rounding.
+ *   RBD_CONTROL_TABLE    : entry 4·step + stage (per_stage = 1) or entry `step` (per_stage = 0), nv × B each in the layout of opts.
+ *   RBD_CONTROL_PD       : τ_i = tau_i − kp_i (q_i − q_des_i) − kd_i v_i on Revolute / Prismatic joints, on the stage state; τ = tau on every other joint's
+ *                          coordinates (q_des NULL = 0, tau NULL = 0).
+ * The controller sees the stage state that contact_dynamics! and dynamics! of that stage see.  Per stage: the integrator's stage launch, contact_head_kernel (the
+ * per-body kinematics of the stage state and the PD law), contact_sim_kernel (s through the tableau, the contact model, the total wrenches), forward dynamics.
+ * fp32 and fp64, both layouts, device pointers only (RBD_MEM_HOST: RBD_ERR_UNSUPPORTED); trees of at most 64 bodies; loop joints: RBD_ERR_UNSUPPORTED; no contact
+ * points or no environment: RBD_ERR_INVALID_ARGUMENT (use rbd_simulate_controlled).  NULL control, q, v or s, dt <= 0, nsteps < 0, TABLE without tau, PD without
+ * kp or kd, kind out of range: RBD_ERR_INVALID_ARGUMENT.  B == 0 or nsteps == 0: nothing is touched.  Only the first call of a workspace (or a larger B)
+ * allocates; no call synchronises.  No derivative entry point covers it. */
+int rbd_simulate_contact_controlled(rbd_ws_t* ws, int32_t B, void* q, void* v, void* s, const rbd_control_t* control, const void* fext, double dt,
+                                    int32_t nsteps, const rbd_opts_t* opts);
 
 /* ---- kinematics by-products of the same forward-kinematics pass (every output nullable; opts->memory as for rbd_dynamics) ---------------
  * momentum_matrix: 6×nv column-major per state, root frame, (angular; linear) — momentum_matrix!(out, state)
@@ -618,7 +634,8 @@ const char* rbd_workspace_last_kernel(const rbd_ws_t* ws);
  *      rbd_contact_dynamics_vjp, rbd_dynamics_contact_vjp (reverse mode through soft contact);
  *      rbd_simulate_contact_vjp (reverse mode through simulate steps with soft contact);
  *      rbd_contact_dynamics_jvp, rbd_dynamics_contact_jvp, rbd_dynamics_contact_derivatives (forward mode through soft contact);
- *      rbd_simulate_contact_jvp, rbd_simulate_contact_step_derivatives (forward mode through simulate steps with soft contact). */
+ *      rbd_simulate_contact_jvp, rbd_simulate_contact_step_derivatives (forward mode through simulate steps with soft contact);
+ *      rbd_simulate_contact_controlled (simulate with soft contact under a device-side controller); rbd_mk_stage takes mechanisms with contact points. */
 #define RBD_HIP_H_VERSION 700
 int rbd_version(void);
 /* Run-time specialisation.  The one-lane-per-state kernels (mass_matrix! and mass_matrix! + Cholesky at large batches) exist in a second form

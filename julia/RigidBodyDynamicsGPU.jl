@@ -689,7 +689,8 @@ end
 """`simulate(state0, final_time, control; Δt)` with a controller that runs on the device (no host round trip per Runge-Kutta stage — the
 reference calls `control!(τ, t, state)` before every stage's `dynamics!`, src/simulate.jl:42-48):
 `TorqueTable(τ, per_stage)` — τ :: (nv·B) × entries, entry 4·step + stage (the stage times) or entry `step` (zero-order hold);
-`PDControl(kp, kd, q_des, τff)` — τ = τff − kp (q − q_des) − kd v on Revolute / Prismatic joints, on the stage state (kp, kd :: nv × 1)."""
+`PDControl(kp, kd, q_des, τff)` — τ = τff − kp (q − q_des) − kd v on Revolute / Prismatic joints, on the stage state (kp, kd :: nv × 1).
+A mechanism with contact points takes both (`rbd_simulate_contact_controlled`): `state.s` is integrated beside (q, v) and reset at every stage state."""
 struct TorqueTable{T}; torques::DeviceMatrix{T}; per_stage::Bool; end
 struct PDControl{T}; kp::DeviceMatrix{T}; kd::DeviceMatrix{T}; q_des::Union{Nothing, DeviceMatrix{T}}; torques::Union{Nothing, DeviceMatrix{T}}; end
 function simulate(state::BatchedMechanismState{T}, final_time, control::Union{TorqueTable{T}, PDControl{T}}; Δt = 1e-4, externalwrenches = nothing) where {T}
@@ -711,8 +712,14 @@ function simulate(state::BatchedMechanismState{T}, final_time, control::Union{To
     vp(x) = x === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(pointer(x))
     ctl = control isa TorqueTable ? RbdControl(1, control.per_stage ? 1 : 0, vp(control.torques), C_NULL, C_NULL, C_NULL) :
                                     RbdControl(2, 0, vp(control.torques), vp(control.q_des), vp(control.kp), vp(control.kd))
-    check(ccall((:rbd_simulate_controlled, librbd_hip[]), Cint, (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ref{RbdControl}, Ptr{T}, Cdouble, Int32, Ref{RbdOpts}),
-        state.ws, B, state.q, state.v, ctl, nullable(wext), Float64(Δt), nsteps, opts(state)), "rbd_simulate_controlled")
+    if size(state.s, 1) > 0     # contact points: the controller on the stage state contact_dynamics! and dynamics! see, s integrated beside (q, v)
+        check(ccall((:rbd_simulate_contact_controlled, librbd_hip[]), Cint,
+            (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ptr{T}, Ref{RbdControl}, Ptr{T}, Cdouble, Int32, Ref{RbdOpts}),
+            state.ws, B, state.q, state.v, state.s, ctl, nullable(wext), Float64(Δt), nsteps, opts(state)), "rbd_simulate_contact_controlled")
+    else
+        check(ccall((:rbd_simulate_controlled, librbd_hip[]), Cint, (Ptr{Cvoid}, Int32, Ptr{T}, Ptr{T}, Ref{RbdControl}, Ptr{T}, Cdouble, Int32, Ref{RbdOpts}),
+            state.ws, B, state.q, state.v, ctl, nullable(wext), Float64(Δt), nsteps, opts(state)), "rbd_simulate_controlled")
+    end
     finish(state)
     range(zero(T), step = T(Δt), length = nsteps + 1), nothing, nothing
 end

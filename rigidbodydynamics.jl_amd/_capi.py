@@ -33,6 +33,7 @@ SYMBOLS = (
     "rbd_simulate_contact_vjp",
     "rbd_contact_dynamics_jvp", "rbd_dynamics_contact_jvp", "rbd_dynamics_contact_derivatives",
     "rbd_simulate_contact_jvp", "rbd_simulate_contact_step_derivatives",
+    "rbd_simulate_contact_controlled",
 )
 
 
@@ -133,6 +134,7 @@ def lib():
         L.rbd_contact_dynamics.argtypes = [vp, i32, vp, vp, vp, vp, vp, ctypes.POINTER(Opts)]
         L.rbd_dynamics_contact.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(Opts)]
         L.rbd_simulate_contact.argtypes = [vp, i32, vp, vp, vp, vp, vp, ctypes.c_double, i32, ctypes.POINTER(Opts)]
+        L.rbd_simulate_contact_controlled.argtypes = [vp, i32, vp, vp, vp, ctypes.POINTER(Control), vp, ctypes.c_double, i32, ctypes.POINTER(Opts)]
         L.rbd_workspace_enable_timing.argtypes = [vp, i32]
         L.rbd_jit_precompile.argtypes = [vp, i32, ctypes.c_char_p, ctypes.c_int64]
         L.rbd_jit_source.argtypes = [vp, i32, i32, ctypes.c_char_p, ctypes.c_int64]

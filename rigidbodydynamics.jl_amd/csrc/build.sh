@@ -11,7 +11,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I../../include -I. -ffp-contr
 pids=()
 # the headers the run-time compiled kernels include, as string literals for hiprtc (rbd_jit.hip)
 python3 ../../scripts/embed_jit_headers.py
-TUS="rbd_kernels rbd_bank_kernels rbd_big_kernels rbd_walk_kernels rbd_state_kernels rbd_contact_kernels rbd_tangent_kernels rbd_point_kernels rbd_capi rbd_capi_derivatives rbd_comm rbd_jit"
+TUS="rbd_kernels rbd_bank_kernels rbd_big_kernels rbd_walk_kernels rbd_state_kernels rbd_contact_kernels rbd_contact_sim_kernels rbd_tangent_kernels rbd_point_kernels rbd_capi rbd_capi_derivatives rbd_comm rbd_jit"
 for tu in $TUS; do
   # the tangent kernels: the zero tangents of the mechanism's constants fold out of the products (rbd_tangent.hpp)
   TUFLAGS=""; [ $tu = rbd_tangent_kernels ] && TUFLAGS="-ffinite-math-only -fno-signed-zeros -Wno-pass-failed"

@@ -1964,7 +1964,8 @@ int rbd_mk_stage(rbd_ws_t* w, int32_t B, int32_t stage, double dt, void* q, void
   int st = begin_call(w, B, opts, kAnySize, &o);
   if (st != RBD_OK) return st;
   if (!q || !v || stage < 0 || stage > 4 || (stage > 0 && !vdot_prev) || o.memory != RBD_MEM_DEVICE) return RBD_ERR_INVALID_ARGUMENT;
-  if (w->model->ncp > 0 && w->model->nhs > 0) return RBD_ERR_UNSUPPORTED;  // the additional contact state is not part of this stage form
+  // (a mechanism with contact points: the stage covers (q, v) only — the caller takes the additional state s through the same tableau beside it and evaluates
+  //  rbd_dynamics_contact at the stage state, as the host-controller loop of `simulate` does)
   if (B == 0) return RBD_OK;
   HIP_TRY(hipSetDevice(w->device));
   if ((st = mk_ensure(w, B))) return st;
@@ -2229,6 +2230,58 @@ int rbd_simulate_contact(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, cons
       }
     }
   }
+  return RBD_OK;
+}
+
+// rbd_simulate_contact's step with simulate_core's controllers, on a stage of its own (rbd_contact_sim_kernels.hip): launch_mk_stage leaves the stage state
+// in (q, v); contact_head_kernel exports its per-body kinematics and evaluates the PD law on it; contact_sim_kernel takes s through the tableau to the same
+// stage state, evaluates the contact model there and writes ṡ, the reset s and the total wrenches; run_dynamics (whatever route it picks) solves v̇ at the
+// stage's τ — so the controller, contact_dynamics! and dynamics! of a stage all see one state.  The closing stage is launch_mk_stage(4) + contact_sim_kernel(4).
+int rbd_simulate_contact_controlled(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, const rbd_control_t* control, const void* fext, double dt,
+                                    int32_t nsteps, const rbd_opts_t* opts) {
+  Opts o;
+  int st = begin_call(w, B, opts, kUpTo64Bodies, &o);  // (its stage launches are the lane-per-body kernels')
+  if (st != RBD_OK) return st;
+  if ((st = contact_scope(w, o))) return st;  // (no contact points: rbd_simulate_controlled)
+  if (!control || !q || !v || !s || nsteps < 0 || !(dt > 0)) return RBD_ERR_INVALID_ARGUMENT;
+  const rbd_control_t& ctl = *control;
+  if (ctl.kind < RBD_CONTROL_CONSTANT || ctl.kind > RBD_CONTROL_PD) return RBD_ERR_INVALID_ARGUMENT;
+  if (ctl.kind == RBD_CONTROL_TABLE && !ctl.tau) return RBD_ERR_INVALID_ARGUMENT;
+  if (ctl.kind == RBD_CONTROL_PD && (!ctl.kp || !ctl.kd)) return RBD_ERR_INVALID_ARGUMENT;
+  if (B == 0 || nsteps == 0) return RBD_OK;
+  HIP_TRY(hipSetDevice(w->device));
+  const rbd_model* m = w->model;
+  const size_t es = esize(w);
+  const size_t ns = (size_t)3 * m->ncp * m->nhs * B, entry = es * (size_t)m->nv * B;
+  const bool pd = ctl.kind == RBD_CONTROL_PD;
+  if ((st = mk_ensure(w, B)) || (st = ensure(w->d_tw, es * (size_t)6 * m->nb * B)) || (st = ensure(w->d_s0, es * ns)) || (st = ensure(w->d_sacc, es * ns)) ||
+      (st = ensure(w->d_sdot, es * ns)) || (st = ensure(w->d_body, es * (size_t)m->nb * 24 * B)) || (pd && (st = ensure(w->d_tauwork, entry))))
+    return st;
+  const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B), Lf = layout_of(o.layout, 6L * m->nb, B),
+               Ls = layout_of(o.layout, 3L * m->ncp * m->nhs, B);
+  // the torques of (step, stage): constant, an entry of the table, or the buffer contact_head_kernel fills from the feed-forward
+  auto tau_at = [&](int step, int stage) -> const void* {
+    if (pd) return w->d_tauwork.p;
+    if (ctl.kind != RBD_CONTROL_TABLE) return ctl.tau;
+    return (const char*)ctl.tau + entry * (size_t)(ctl.per_stage ? 4 * step + stage : step);
+  };
+  for (int step = 0; step < nsteps; ++step) {
+    for (int stage = 0; stage <= 4; ++stage) {
+      if ((st = by_dtype(w->dtype, [&](auto t) -> int {
+             using T = decltype(t);
+             HIP_TRY(launch_mk_stage<T>(w->dm, B, stage, dt, q, v, w->d_vdwork.p, w->mk, Lq, Lv, w->stream));
+             if (stage < 4)
+               HIP_TRY(launch_contact_head<T>(w->dm, B, q, v, pd ? ctl.tau : nullptr, ctl.q_des, ctl.kp, ctl.kd, pd ? w->d_tauwork.p : nullptr, w->d_body.p, Lq, Lv,
+                                              w->stream));
+             HIP_TRY(launch_contact_sim<T>(w->ctm, B, stage, dt, w->d_body.p, s, w->d_sdot.p, w->d_s0.p, w->d_sacc.p, fext, w->d_tw.p, Ls, Lf, w->stream));
+             return RBD_OK;
+           })))
+        return st;
+      if (stage < 4 && (st = run_dynamics(w, B, o, q, v, tau_at(step, stage), w->d_tw.p, w->d_vdwork.p, nullptr, nullptr))) return st;
+    }
+  }
+  w->last_kernel_text = std::string("contact_head_kernel + contact_sim_kernel + ") + w->last_kernel;  // (run_dynamics named its route)
+  w->last_kernel = w->last_kernel_text.c_str();
   return RBD_OK;
 }
 

@@ -180,6 +180,7 @@ struct rbd_ws {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool ev_pending = false;
   const char* last_kernel = "";  // dominant kernel of the last rbd_dynamics / rbd_simulate / rbd_mass_matrix_solve call
+  std::string last_kernel_text;  // where an entry point composes the name (rbd_simulate_contact_controlled: its stage kernels + run_dynamics' route): last_kernel points into it
   int last_aba = ABA_OTHER;  // what the last run_aba launched (AbaProgram): simulate_core routes by it
   // the derivative entry points (rbd_capi_derivatives.hip; kernels: rbd_tangent_kernels.hip): the tree in the reference's order for every mechanism (BigModel
   // tables), the tangent scratch (tan_threads (state, chunk) threads per launch) and the dynamics! buffers — M, its factor, c, v̇, tangent right-hand sides for

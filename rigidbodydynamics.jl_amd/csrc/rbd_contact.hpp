@@ -87,6 +87,60 @@ template <typename S> RBD_HD bool contact_pair_force(const S* pos, const S* vel,
   return true;
 }
 
+// The forward path's pair, statement for statement what contact_kernel has always computed (contact_pair_force above is the same model with the slip scale and
+// the wrench formed in the order the derivative passes want): shared by contact_kernel and contact_sim_kernel (rbd_contact_sim_kernels.hip).  pt, vel: the
+// contact point in the root frame; x: the pair's friction state; c, H as above.  Returns whether the point is inside; xd = ẋ (3) is always written (zero
+// outside, where the caller resets x), and the pair's wrench (pt × f; f) is ADDED to w (6) when inside.
+template <typename T> RBD_HD bool contact_pair_wrench(const T* pt, const T* vel, const T* x, const T* c, const T* H, T* xd, T* w) {
+  const T* n = H + 3;
+  const T sep = (pt[0] - H[0]) * n[0] + (pt[1] - H[1]) * n[1] + (pt[2] - H[2]) * n[2];  // separation (contact.jl:224)
+  if (!(sep <= T(0))) {  // not point_inside (:225): reset! the state, zero! the derivative (mechanism_algorithms.jl:714-715)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) xd[j] = T(0);
+    return false;
+  }
+  // contact_dynamics! (contact.jl:79-93)
+  const T z = -sep;
+  const T zd = -(vel[0] * n[0] + vel[1] * n[1] + vel[2] * n[2]);
+  const T zn = ct_pow(z, c[CP_HCN]);
+  T fn = c[CP_HCL] * zn * zd + c[CP_HCK] * zn;  // HuntCrossley normal_force (:115-118)
+  fn = fn > T(0) ? fn : T(0);
+  T vt[3], fs[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) vt[j] = vel[j] + zd * n[j];
+  // friction_force (:150-169): stick force −k x − b v, clipped to the friction cone
+#pragma unroll
+  for (int j = 0; j < 3; ++j) fs[j] = -c[CP_K] * x[j] - c[CP_B] * vt[j];
+  const T n2 = fs[0] * fs[0] + fs[1] * fs[1] + fs[2] * fs[2], m2 = (c[CP_MU] * fn) * (c[CP_MU] * fn);
+  if (n2 > m2) {
+    const T sc = ct_sqrt(m2 / n2);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) fs[j] *= sc;
+  }
+  // dynamics! of the friction state (:171-178): ẋ = (−k x − f_tangential) / b
+#pragma unroll
+  for (int j = 0; j < 3; ++j) xd[j] = (-c[CP_K] * x[j] - fs[j]) / c[CP_B];
+  T f[3], tq[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) f[j] = fn * n[j] + fs[j];
+  cross3(pt, f, tq);  // Wrench(point, force) (:712)
+#pragma unroll
+  for (int j = 0; j < 3; ++j) { w[j] += tq[j]; w[3 + j] += f[j]; }
+  return true;
+}
+
+// The point of contact_kernel's walk: point = body_to_root * location; velocity = point_velocity(twist, point) = ω × point + v (mechanism_algorithms.jl:697-699),
+// from the body's exported kinematics k (R 9, p 3, twist 6) and the point's constants c.
+template <typename T> RBD_HD void contact_point_in_root(const T* k, const T* c, T* pt, T* vel) {
+  T t3[3];
+  matvec3(k, c + CP_LOC, pt);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) pt[j] += k[9 + j];
+  cross3(k + 12, pt, t3);
+#pragma unroll
+  for (int j = 0; j < 3; ++j) vel[j] = t3[j] + k[15 + j];
+}
+
 // One contact point against every half-space, from its body's kinematics: the contact step of forward mode (rbd_contact_dynamics_jvp, rbd_dynamics_contact_jvp:
 // S = Dual<T, N> between the two sweeps of the tangent RNEA pass, rbd_tangent.hpp) and, with S = T, contact_kernel's arithmetic for one point.
 //   K    the body's (R 9 row-major, p 3, twist 6 = (ω; v)) in the root frame, as tangent_rnea_state and the per-body kinematics export keep them

@@ -19,10 +19,6 @@
 
 namespace rbd {
 
-template <typename T> RBD_DEV T pow_t(T x, T n);
-template <> RBD_DEV double pow_t<double>(double x, double n) { return pow(x, n); }
-template <> RBD_DEV float pow_t<float>(float x, float n) { return powf(x, n); }
-
 template <typename T>
 __global__ __launch_bounds__(256) void contact_kernel(ContactModel M, long B, const T* __restrict__ body, T* __restrict__ s, T* __restrict__ sdot,
                                                      const T* __restrict__ fext, T* __restrict__ cw, T* __restrict__ tw, Layout Ls, Layout Lf) {
@@ -44,53 +40,18 @@ __global__ __launch_bounds__(256) void contact_kernel(ContactModel M, long B, co
     const T* c = cp + (long)ip * CP_STRIDE;
     T w[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
     // point = body_to_root * location; velocity = point_velocity(twist, point) = ω × point + v   (:697-699)
-    T pt[3], vel[3], t3[3];
-    matvec3(k, c + CP_LOC, pt);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) pt[j] += k[9 + j];
-    cross3(k + 12, pt, t3);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) vel[j] = t3[j] + k[15 + j];
+    T pt[3], vel[3];
+    contact_point_in_root(k, c, pt, vel);
     for (int h = 0; h < M.nh; ++h) {
-      const T* H = hs + (long)h * 6;
       const long so = (long)(ip * M.nh + h) * 3;
-      const T* n = H + 3;
-      const T sep = (pt[0] - H[0]) * n[0] + (pt[1] - H[1]) * n[1] + (pt[2] - H[2]) * n[2];  // separation (contact.jl:224)
-      if (sep <= T(0)) {  // point_inside (:225)
-        // contact_dynamics! (contact.jl:79-93)
-        const T z = -sep;
-        const T zd = -(vel[0] * n[0] + vel[1] * n[1] + vel[2] * n[2]);
-        const T zn = pow_t(z, c[CP_HCN]);
-        T fn = c[CP_HCL] * zn * zd + c[CP_HCK] * zn;  // HuntCrossley normal_force (:115-118)
-        fn = fn > T(0) ? fn : T(0);
-        T vt[3], x[3], fs[3];
+      T x[3], xd[3];
 #pragma unroll
-        for (int j = 0; j < 3; ++j) { vt[j] = vel[j] + zd * n[j]; x[j] = sx[(so + j) * Ls.sk]; }
-        // friction_force (:150-169): stick force −k x − b v, clipped to the friction cone
+      for (int j = 0; j < 3; ++j) x[j] = sx[(so + j) * Ls.sk];
+      const bool inside = contact_pair_wrench<T>(pt, vel, x, c, hs + (long)h * 6, xd, w);  // the pair model (rbd_contact.hpp)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) fs[j] = -c[CP_K] * x[j] - c[CP_B] * vt[j];
-        const T n2 = fs[0] * fs[0] + fs[1] * fs[1] + fs[2] * fs[2], m2 = (c[CP_MU] * fn) * (c[CP_MU] * fn);
-        if (n2 > m2) {
-          const T sc = SqrtT<T>::f(m2 / n2);
-#pragma unroll
-          for (int j = 0; j < 3; ++j) fs[j] *= sc;
-        }
-        if (sd) {  // dynamics! of the friction state (:171-178): ẋ = (−k x − f_tangential) / b
-#pragma unroll
-          for (int j = 0; j < 3; ++j) sd[(so + j) * Ls.sk] = (-c[CP_K] * x[j] - fs[j]) / c[CP_B];
-        }
-        T f[3], tq[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) f[j] = fn * n[j] + fs[j];
-        cross3(pt, f, tq);  // Wrench(point, force) (:712)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) { w[j] += tq[j]; w[3 + j] += f[j]; }
-      } else {  // reset! the state, zero! the derivative (:714-715)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          sx[(so + j) * Ls.sk] = T(0);
-          if (sd) sd[(so + j) * Ls.sk] = T(0);
-        }
+      for (int j = 0; j < 3; ++j) {
+        if (!inside) sx[(so + j) * Ls.sk] = T(0);  // reset! the state (:714-715); ẋ is zero there
+        if (sd) sd[(so + j) * Ls.sk] = xd[j];
       }
     }
 #pragma unroll

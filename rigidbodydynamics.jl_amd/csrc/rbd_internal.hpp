@@ -80,6 +80,15 @@ template <typename T> hipError_t launch_contact_stage_value(long n, int stage, d
 template <typename T>
 hipError_t launch_contact_stage_adjoint(const ContactModel& M, long B, int stage, double dt, const void* body, const void* s, const void* wbar, void* fbar, void* sbar,
                                         void* s0b, void* accb, void* pbar, void* vbar, Layout Ls, Layout Lf, Layout L3, hipStream_t st);
+// rbd_contact_sim_kernels.hip: the stage of rbd_simulate_contact_controlled.  launch_contact_head: the per-body kinematics [state][body][24] of the stage state
+// (R, p, twist; slots 18 … 23 not written) and, with tau_out != nullptr, the PD law's τ (tau_ff, qdes nullable: zero).  launch_contact_sim: s through the
+// tableau (stage 0 … 4, contact_stage_kernel's buffers) and, at stages 0 … 3, contact_kernel's model on it: ṡ, the reset s and tw = fext + contact wrenches.
+template <typename T>
+hipError_t launch_contact_head(const DevModel& M, long B, const void* q, const void* v, const void* tau_ff, const void* qdes, const void* kp, const void* kd,
+                               void* tau_out, void* body_out, Layout Lq, Layout Lv, hipStream_t st);
+template <typename T>
+hipError_t launch_contact_sim(const ContactModel& M, long B, int stage, double dt, const void* body, void* s, void* sdot, void* s0, void* acc, const void* fext,
+                              void* tw, Layout Ls, Layout Lf, hipStream_t st);
 // rbd_walk_kernels.hip: one wavefront per track, one lane per state
 template <typename T>
 hipError_t launch_aba_walk(const WalkModel& M, int flt, int gen, int pair, long B, size_t lds_bytes, const void* q, const void* v, const void* tau, const void* fext,

@@ -797,7 +797,8 @@ RK4_C = (0.0, 0.5, 0.5, 1.0)  # c = row sums of the runge_kutta_4 tableau (src/o
 class TorqueTable:
     """Device-side open-loop controller for `simulate_`: `torques[k]` is the (B, nv) torque of entry k — entry 4·step + stage with
     `per_stage=True` (the stage times t, t + h/2, t + h/2, t + h at which the reference calls control!(τ, t, state), src/simulate.jl:42-48), entry
-    `step` otherwise (zero-order hold).  No host round trip per stage (`rbd_simulate_controlled`, RBD_CONTROL_TABLE)."""
+    `step` otherwise (zero-order hold).  No host round trip per stage (`rbd_simulate_controlled`, with contact points `rbd_simulate_contact_controlled`:
+    RBD_CONTROL_TABLE)."""
 
     def __init__(self, torques: torch.Tensor, per_stage: bool = True):
         self.torques, self.per_stage = torques, bool(per_stage)
@@ -805,10 +806,35 @@ class TorqueTable:
 
 class PDControl:
     """Device-side PD controller for `simulate_`: τ_i = torques_i − kp_i (q_i − q_des_i) − kd_i v_i on every Revolute / Prismatic joint, evaluated on the
-    stage state inside the dynamics launch (`rbd_simulate_controlled`, RBD_CONTROL_PD).  kp, kd: (nv,) tensors; q_des: (B, nq) or None (zero)."""
+    stage state on the device (`rbd_simulate_controlled`, with contact points `rbd_simulate_contact_controlled`: RBD_CONTROL_PD).  kp, kd: (nv,) tensors;
+    q_des: (B, nq) or None (zero)."""
 
     def __init__(self, kp: torch.Tensor, kd: torch.Tensor, q_des: Optional[torch.Tensor] = None, torques: Optional[torch.Tensor] = None):
         self.kp, self.kd, self.q_des, self.torques = kp, kd, q_des, torques
+
+
+def _control_descriptor(state: MechanismState, control_, nsteps: int):
+    """The rbd_control_t of a TorqueTable / PDControl for `nsteps` steps, and the tensors it points into (kept alive by the caller across the call)."""
+    f = state.flat
+    ctl = _capi.Control()
+    if isinstance(control_, TorqueTable):
+        per = 4 if control_.per_stage else 1
+        tt = control_.torques
+        if tt.dtype != state.dtype or not tt.is_cuda or not tt.is_contiguous() or tt.dim() != 3 or tt.shape[0] < per * nsteps:
+            raise DimensionMismatch(f"TorqueTable needs a contiguous device tensor of at least {per * nsteps} entries of the batch's (B, nv) shape")
+        state._check(tt[0], f.nv, "torque table entry")
+        ctl.kind, ctl.per_stage, ctl.tau = _capi.CONTROL_TABLE, int(control_.per_stage), tt.data_ptr()
+        return ctl, (tt,)
+    kp = control_.kp.to(device=state.device, dtype=state.dtype).contiguous()
+    kd = control_.kd.to(device=state.device, dtype=state.dtype).contiguous()
+    if tuple(kp.shape) != (f.nv,) or tuple(kd.shape) != (f.nv,):
+        raise DimensionMismatch(f"PDControl gains must be ({f.nv},)")
+    state._check(control_.q_des, f.nq, "q_des")
+    state._check(control_.torques, f.nv, "torques")
+    ctl.kind, ctl.kp, ctl.kd = _capi.CONTROL_PD, kp.data_ptr(), kd.data_ptr()
+    ctl.q_des = control_.q_des.data_ptr() if control_.q_des is not None else None
+    ctl.tau = control_.torques.data_ptr() if control_.torques is not None else None
+    return ctl, (kp, kd)
 
 
 def simulate_(state: MechanismState, final_time: float, control_=None, dt: float = 1e-4, torques: Optional[torch.Tensor] = None,
@@ -820,7 +846,10 @@ def simulate_(state: MechanismState, final_time: float, control_=None, dt: float
       the GPU without returning to the host (`rbd_simulate`).
     * `control_(torques, t, state)`: called before each stage's `dynamics!` exactly like the reference's closure
       (src/simulate.jl:42-48); it must fill the (B, nv) `torques` tensor in place.
-    Returns `ts` (and the lists `qs`, `vs` of per-step snapshots when `store`), with the reference's loop `while t < final_time`."""
+    * a `TorqueTable` / `PDControl`: the controller runs on the device (`rbd_simulate_controlled`; with contact points
+      `rbd_simulate_contact_controlled`), no host round trip per stage.
+    A mechanism with contact points carries `state.s` beside (q, v) under every one of these.
+    Returns `ts` (and the lists `qs`, `vs` — with contact points `ss` too — of per-step snapshots when `store`), with the reference's loop `while t < final_time`."""
     f = state.flat
     state._check(torques, f.nv, "torques")
     state._check(externalwrenches, 6 * f.n_bodies, "externalwrenches")
@@ -834,41 +863,48 @@ def simulate_(state: MechanismState, final_time: float, control_=None, dt: float
         t += dt
         ts.append(t)
         nsteps += 1
+    device_ctl = isinstance(control_, (TorqueTable, PDControl))
+    if device_ctl:
+        if torques is not None:
+            raise ValueError("pass the torques through the controller object")
+        ctl, keep = _control_descriptor(state, control_, nsteps)
+        if store:
+            raise NotImplementedError("store=True with a device-side controller: call simulate_ once per step")
     if getattr(f, "ns", 0) > 0:  # soft contact: the additional state is integrated beside (q, v)
-        if control_ is not None:
-            raise NotImplementedError("control callbacks with contact points: use dynamics_ per stage")
+        if device_ctl:  # the controller on the device, on the stage state contact_dynamics! and dynamics! see (rbd_simulate_contact_controlled)
+            _raise(L.rbd_simulate_contact_controlled(state.ws.handle, state.batch, _ptr(state.q), _ptr(state.v), _ptr(state.s), ctypes.byref(ctl),
+                                                     _ptr(externalwrenches), ctypes.c_double(dt), nsteps, ctypes.byref(opts)), "rbd_simulate_contact_controlled")
+            del keep
+            return np.array(ts)
         ss = [state.s.clone()] if store else None
+        if control_ is not None:
+            # control_(torques, t, state) on the host before every stage's dynamics!: rbd_mk_stage for (q, v), the same tableau for s here (what
+            # contact_stage_kernel does: s0 is the step's start before any reset, the reset of rbd_dynamics_contact acts on the stage state only)
+            tau = torch.zeros_like(state.v) if torques is None else torques
+            vd, sd = torch.zeros_like(state.v), torch.zeros_like(state.s)
+            for k in range(nsteps):
+                for stage in range(5):
+                    _raise(L.rbd_mk_stage(state.ws.handle, state.batch, stage, ctypes.c_double(dt), _ptr(state.q), _ptr(state.v),
+                                          _ptr(vd if stage > 0 else None), ctypes.byref(opts)), "rbd_mk_stage")
+                    if stage == 0:
+                        s0, acc = state.s.clone(), torch.zeros_like(state.s)
+                    else:
+                        acc = acc + (1 / 6 if stage in (1, 4) else 1 / 3) * sd
+                        state.s.copy_(s0 + dt * acc if stage == 4 else s0 + (1.0 if stage == 3 else 0.5) * dt * sd)
+                    if stage < 4:
+                        control_(tau, ts[k] + RK4_C[stage] * dt, state)
+                        _raise(L.rbd_dynamics_contact(state.ws.handle, state.batch, _ptr(state.q), _ptr(state.v), _ptr(state.s), _ptr(tau), _ptr(externalwrenches),
+                                                      _ptr(vd), None, _ptr(sd), None, None, ctypes.byref(opts)), "rbd_dynamics_contact")
+                if store:
+                    qs.append(state.q.clone()); vs.append(state.v.clone()); ss.append(state.s.clone())
+            return (np.array(ts), qs, vs, ss) if store else np.array(ts)
         for _ in range(nsteps if store else 1):
             _raise(L.rbd_simulate_contact(state.ws.handle, state.batch, _ptr(state.q), _ptr(state.v), _ptr(state.s), _ptr(torques), _ptr(externalwrenches),
                                           ctypes.c_double(dt), 1 if store else nsteps, ctypes.byref(opts)), "rbd_simulate_contact")
             if store:
                 qs.append(state.q.clone()); vs.append(state.v.clone()); ss.append(state.s.clone())
         return (np.array(ts), qs, vs, ss) if store else np.array(ts)
-    if isinstance(control_, (TorqueTable, PDControl)):
-        if torques is not None:
-            raise ValueError("pass the torques through the controller object")
-        ctl = _capi.Control()
-        if isinstance(control_, TorqueTable):
-            per = 4 if control_.per_stage else 1
-            tt = control_.torques
-            if tt.dtype != state.dtype or not tt.is_cuda or not tt.is_contiguous() or tt.dim() != 3 or tt.shape[0] < per * nsteps:
-                raise DimensionMismatch(f"TorqueTable needs a contiguous device tensor of at least {per * nsteps} entries of the batch's (B, nv) shape")
-            state._check(tt[0], f.nv, "torque table entry")
-            ctl.kind, ctl.per_stage, ctl.tau = _capi.CONTROL_TABLE, int(control_.per_stage), tt.data_ptr()
-            keep = (tt,)
-        else:
-            kp = control_.kp.to(device=state.device, dtype=state.dtype).contiguous()
-            kd = control_.kd.to(device=state.device, dtype=state.dtype).contiguous()
-            if tuple(kp.shape) != (f.nv,) or tuple(kd.shape) != (f.nv,):
-                raise DimensionMismatch(f"PDControl gains must be ({f.nv},)")
-            state._check(control_.q_des, f.nq, "q_des")
-            state._check(control_.torques, f.nv, "torques")
-            ctl.kind, ctl.kp, ctl.kd = _capi.CONTROL_PD, kp.data_ptr(), kd.data_ptr()
-            ctl.q_des = control_.q_des.data_ptr() if control_.q_des is not None else None
-            ctl.tau = control_.torques.data_ptr() if control_.torques is not None else None
-            keep = (kp, kd)
-        if store:
-            raise NotImplementedError("store=True with a device-side controller: call simulate_ once per step")
+    if device_ctl:
         _raise(L.rbd_simulate_controlled(state.ws.handle, state.batch, _ptr(state.q), _ptr(state.v), ctypes.byref(ctl), _ptr(externalwrenches),
                                          ctypes.c_double(dt), nsteps, ctypes.byref(opts)), "rbd_simulate_controlled")
         del keep
