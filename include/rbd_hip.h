@@ -342,7 +342,11 @@ int rbd_simulate_controlled(rbd_ws_t* ws, int32_t B, void* q, void* v, const rbd
  * rbd_dynamics_contact: dynamics!(result, state, τ, wext) of a mechanism with contact points (:845-864): contact_dynamics!, then
  *   totalwrenches = wext + contactwrenches (:851-856), then forward dynamics with those.  totalwrenches nullable.
  * rbd_simulate_contact: simulate (src/simulate.jl:36-55) with the additional state integrated beside (q, v) by the same Runge–Kutta
- *   tableau (src/ode_integrators.jl:233-299).  Tree mechanisms.                                                                */
+ *   tableau (src/ode_integrators.jl:233-299).  Tree mechanisms.  It is rbd_simulate_contact_controlled with RBD_CONTROL_CONSTANT (below): one
+ *   stage driver, the same scope and status codes, and rbd_workspace_last_kernel answers "contact_head_kernel + contact_sim_kernel + <the
+ *   forward-dynamics route>" afterwards.  (Until the two were folded it ran a stage of its own — a kernel for s, a whole RNEA launch for the
+ *   per-body kinematics, contact_kernel: fp64 results are those of that stage bit for bit on the recorded cases, fp32 results to rounding.)
+ * rbd_contact_dynamics and rbd_dynamics_contact take their per-body kinematics from the same contact_head_kernel (trees of at most 64 bodies). */
 int rbd_model_contact_dims(const rbd_model_t* model, int32_t* n_contact_points, int32_t* n_halfspaces, int32_t* n_additional_states);
 int rbd_contact_dynamics(rbd_ws_t* ws, int32_t B, const void* q, const void* v, void* s, void* contactwrenches, void* sdot, const rbd_opts_t* opts);
 int rbd_dynamics_contact(rbd_ws_t* ws, int32_t B, const void* q, const void* v, void* s, const void* tau, const void* fext, void* vdot, void* qdot,
@@ -350,9 +354,9 @@ int rbd_dynamics_contact(rbd_ws_t* ws, int32_t B, const void* q, const void* v, 
 int rbd_simulate_contact(rbd_ws_t* ws, int32_t B, void* q, void* v, void* s, const void* tau, const void* fext, double dt, int32_t nsteps,
                          const rbd_opts_t* opts);
 
-/* rbd_simulate_contact_controlled (700 addition): `simulate(state, T, control!)` of a mechanism with contact points — rbd_simulate_contact's step (Munthe-Kaas
- * RK4, the friction state s through the same tableau and reset by contact_dynamics! at each stage state) with rbd_simulate_controlled's device-side controllers:
- *   RBD_CONTROL_CONSTANT : τ = tau (NULL = 0) — rbd_simulate_contact's result to rounding.
+/* rbd_simulate_contact_controlled (700 addition): `simulate(state, T, control!)` of a mechanism with contact points — the Munthe-Kaas RK4 step, the friction
+ * state s through the same tableau and reset by contact_dynamics! at each stage state, with rbd_simulate_controlled's device-side controllers:
+ *   RBD_CONTROL_CONSTANT : τ = tau (NULL = 0) — this is rbd_simulate_contact, bit for bit.
  *   RBD_CONTROL_TABLE    : entry 4·step + stage (per_stage = 1) or entry `step` (per_stage = 0), nv × B each in the layout of opts.
  *   RBD_CONTROL_PD       : τ_i = tau_i − kp_i (q_i − q_des_i) − kd_i v_i on Revolute / Prismatic joints, on the stage state; τ = tau on every other joint's
  *                          coordinates (q_des NULL = 0, tau NULL = 0).

@@ -1975,6 +1975,25 @@ int rbd_mk_stage(rbd_ws_t* w, int32_t B, int32_t stage, double dt, void* q, void
   return RBD_OK;
 }
 
+// A controller descriptor's fields, as every simulate entry point checks them (after its own scope checks)
+static int control_check(const rbd_control_t& ctl) {
+  if (ctl.kind == RBD_CONTROL_TABLE && !ctl.tau) return RBD_ERR_INVALID_ARGUMENT;
+  if (ctl.kind == RBD_CONTROL_PD && (!ctl.kp || !ctl.kd)) return RBD_ERR_INVALID_ARGUMENT;
+  if (ctl.kind < RBD_CONTROL_CONSTANT || ctl.kind > RBD_CONTROL_PD) return RBD_ERR_INVALID_ARGUMENT;
+  return RBD_OK;
+}
+// the torques of (step, stage): an entry of the table (`entry` bytes each) from `base` on, or `base` itself — the constant τ, the PD feed-forward, or the
+// buffer a kernel fills with the PD law's τ of the stage
+struct ControlTau {
+  const rbd_control_t& ctl;
+  const void* base;
+  size_t entry;
+  const void* at(int step, int stage) const {
+    if (ctl.kind != RBD_CONTROL_TABLE) return base;
+    return (const char*)base + entry * (size_t)(ctl.per_stage ? 4 * step + stage : step);
+  }
+};
+
 // simulate with a controller descriptor (rbd_simulate: constant τ)
 static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_control_t& ctl, const void* fext, double dt, int32_t nsteps, const rbd_opts_t* opts) {
   Opts o;
@@ -1983,9 +2002,7 @@ static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_con
   if (!q || !v || nsteps < 0 || !(dt > 0)) return RBD_ERR_INVALID_ARGUMENT;
   if (w->model->ncp > 0 && w->model->nhs > 0) return RBD_ERR_UNSUPPORTED;  // contact points: rbd_simulate_contact (carries the additional state)
   if (ctl.kind != RBD_CONTROL_CONSTANT && (o.memory != RBD_MEM_DEVICE || w->model->nloops > 0)) return RBD_ERR_UNSUPPORTED;
-  if (ctl.kind == RBD_CONTROL_TABLE && !ctl.tau) return RBD_ERR_INVALID_ARGUMENT;
-  if (ctl.kind == RBD_CONTROL_PD && (!ctl.kp || !ctl.kd)) return RBD_ERR_INVALID_ARGUMENT;
-  if (ctl.kind < RBD_CONTROL_CONSTANT || ctl.kind > RBD_CONTROL_PD) return RBD_ERR_INVALID_ARGUMENT;
+  if ((st = control_check(ctl))) return st;
   if (B == 0 || nsteps == 0) return RBD_OK;
   HIP_TRY(hipSetDevice(w->device));
   const rbd_model* m = w->model;
@@ -2001,10 +2018,7 @@ static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_con
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B);
   // the torques of (step, stage): constant / PD feed-forward, or an entry of the table
   const size_t entry = es * (size_t)m->nv * B;
-  auto tau_at = [&](int step, int stage) -> const void* {
-    if (ctl.kind != RBD_CONTROL_TABLE) return dtau;
-    return (const char*)dtau + entry * (size_t)(ctl.per_stage ? 4 * step + stage : step);
-  };
+  const ControlTau tau{ctl, dtau, entry};
   const bool pd = ctl.kind == RBD_CONTROL_PD;
   // large batches: the walk kernel (one wavefront per track, §3.4 of DESIGN.md) with the stage bookkeeping in its own launches beats the
   // lane-per-body kernels with the stage fused in (fp64 Atlas, 65 536 states: 4 x 147 us + 5 stage launches vs 4 x 290 us)
@@ -2043,7 +2057,7 @@ static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_con
     for (int step = 0; step < nsteps; ++step) {
       MkStage F{4, pd ? 1 : 0, dt, w->mk.q0, w->mk.v0, w->mk.phid[0], w->mk.vd[0], dq, dv, ctl.kp, ctl.kd, ctl.q_des, 0};
       F.tau_stride = per_stage ? (int64_t)m->nv * B : 0;
-      st = run_aba(w, B, RBD_ALGO_ABA_WALK, dq, dv, tau_at(step, 0), df, nullptr, nullptr, Lq, Lv, Lf, nullptr, nullptr, &F);
+      st = run_aba(w, B, RBD_ALGO_ABA_WALK, dq, dv, tau.at(step, 0), df, nullptr, nullptr, Lq, Lv, Lf, nullptr, nullptr, &F);
       if (st == RBD_ERR_UNSUPPORTED && step == 0) { ok = false; break; }
       if (st) return st;
     }
@@ -2055,7 +2069,7 @@ static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_con
   for (int step = 0; try_spec_sim && step < nsteps; ++step) {
     for (int stage = 0; stage < 4; ++stage) {
       const MkStage F{stage, pd ? 1 : 0, dt, w->mk.q0, w->mk.v0, w->mk.phid[0], w->mk.vd[0], dq, dv, ctl.kp, ctl.kd, ctl.q_des};
-      st = run_aba(w, B, sim_algo, dq, dv, tau_at(step, stage), df, nullptr, nullptr, Lq, Lv, Lf, nullptr, nullptr, &F);
+      st = run_aba(w, B, sim_algo, dq, dv, tau.at(step, stage), df, nullptr, nullptr, Lq, Lv, Lf, nullptr, nullptr, &F);
       if (st == RBD_ERR_UNSUPPORTED && step == 0 && stage == 0) break;
       if (st) return st;
       if (!spec_sim) {
@@ -2082,7 +2096,7 @@ static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_con
       MkFuse F{};
       F.stage = stage; F.close_prev = (stage == 0 && step > 0) ? 1 : 0; F.dt = dt; F.W = w->mk; F.q_state = dq; F.v_state = dv;
       if (pd) { F.pd_kp = ctl.kp; F.pd_kd = ctl.kd; F.pd_qdes = ctl.q_des; }
-      if ((st = run_aba(w, B, RBD_ALGO_ABA, dq, dv, tau_at(step, stage), df, nullptr, nullptr, Lq, Lv, Lf, nullptr, &F))) return st;
+      if ((st = run_aba(w, B, RBD_ALGO_ABA, dq, dv, tau.at(step, stage), df, nullptr, nullptr, Lq, Lv, Lf, nullptr, &F))) return st;
     }
     if (step == nsteps - 1) HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_mk_stage<decltype(t)>(w->dm, B, 4, dt, dq, dv, nullptr, w->mk, Lq, Lv, w->stream); }));
   }
@@ -2092,7 +2106,7 @@ static int simulate_core(rbd_ws_t* w, int32_t B, void* q, void* v, const rbd_con
     for (int stage = 0; stage < 4; ++stage) {
       const int close_prev = (stage == 0 && step > 0) ? 1 : 0;
       HIP_TRY(stage_launch(w, B, stage, dt, dq, dv, w->d_vdwork.p, Lq, Lv, close_prev));
-      const void* ts = tau_at(step, stage);
+      const void* ts = tau.at(step, stage);
       if (pd) {  // the PD law on the stage state the launch above left in (q, v): one element-wise launch, no host round trip
         HIP_TRY(by_dtype(w->dtype, [&](auto t) {
           using T = decltype(t);
@@ -2129,21 +2143,22 @@ int rbd_model_contact_dims(const rbd_model_t* m, int32_t* n_contact_points, int3
   return RBD_OK;
 }
 
-// the per-body kinematics [state][body][24] of (q, v) into w->d_body (the RNEA launch exports them; its bias torques go to the workspace)
+// the per-body kinematics [state][body][24] of (q, v) into w->d_body: R, p, twist in slots 0 … 17, all the contact kernels read (contact_head_kernel, the export
+// of the simulate stage, without its PD law; trees of more than 64 bodies: out of the any-size RNEA's scratch, its bias torques go to the workspace)
 int run_contact_kinematics(rbd_ws* w, int32_t B, const Opts& o, const void* dq, const void* dv) {
   const rbd_model* m = w->model;
   const size_t es = esize(w);
   int st;
-  if ((st = ensure(w->d_body, es * (size_t)m->nb * 24 * B)) || (st = ensure(w->d_c, es * (size_t)m->nv * B))) return st;
+  if ((st = ensure(w->d_body, es * (size_t)m->nb * 24 * B))) return st;
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B), Lf = layout_of(o.layout, 6L * m->nb, B);
-  if (m->big && (st = big_scratch(w, B))) return st;
+  if (m->big && ((st = big_scratch(w, B)) || (st = ensure(w->d_c, es * (size_t)m->nv * B)))) return st;
   return by_dtype(w->dtype, [&](auto t) -> int {
     using T = decltype(t);
-    if (m->big) {  // more than 64 bodies: the per-body kinematics from the any-size kernels
+    if (m->big) {
       HIP_TRY(launch_big_rnea<T>(w->big, B, dq, dv, nullptr, nullptr, w->d_c.p, nullptr, w->d_big_scratch.p, nullptr, nullptr, Lq, Lv, Lf, w->stream));
       HIP_TRY(launch_big_export_body<T>(w->big, B, w->d_big_scratch.p, w->d_body.p, w->stream));
     } else {
-      HIP_TRY(launch_rnea<T>(w->dm, B, dq, dv, nullptr, nullptr, w->d_c.p, nullptr, w->d_body.p, Lq, Lv, Lf, w->stream));
+      HIP_TRY(launch_contact_head<T>(w->dm, B, dq, dv, nullptr, nullptr, nullptr, nullptr, nullptr, w->d_body.p, Lq, Lv, w->stream));
     }
     return RBD_OK;
   });
@@ -2198,56 +2213,20 @@ int rbd_dynamics_contact(rbd_ws_t* w, int32_t B, const void* q, const void* v, v
   return run_dynamics(w, B, o, q, v, tau, dtw, vdot, qdot, nullptr);
 }
 
-int rbd_simulate_contact(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, const void* tau, const void* fext, double dt, int32_t nsteps,
-                         const rbd_opts_t* opts) {
-  Opts o;
-  int st = begin_call(w, B, opts, kUpTo64Bodies, &o);  // (its stage launches are the lane-per-body mk_stage kernel's)
-  if (st != RBD_OK) return st;
-  if ((st = contact_scope(w, o))) return st;
-  if (!q || !v || !s || nsteps < 0 || !(dt > 0)) return RBD_ERR_INVALID_ARGUMENT;
-  if (B == 0 || nsteps == 0) return RBD_OK;
-  HIP_TRY(hipSetDevice(w->device));
-  const rbd_model* m = w->model;
-  const size_t es = esize(w);
-  const long ns = 3L * m->ncp * m->nhs * B;
-  if ((st = mk_ensure(w, B)) || (st = ensure(w->d_tw, es * (size_t)6 * m->nb * B)) || (st = ensure(w->d_s0, es * (size_t)ns)) ||
-      (st = ensure(w->d_sacc, es * (size_t)ns)) || (st = ensure(w->d_sdot, es * (size_t)ns)))
-    return st;
-  const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B);
-  for (int step = 0; step < nsteps; ++step) {
-    // MuntheKaasIntegrator.step (src/ode_integrators.jl:233-299): (q, v) through mk_stage_kernel, s beside them with the same tableau
-    for (int stage = 0; stage <= 4; ++stage) {
-      if ((st = by_dtype(w->dtype, [&](auto t) -> int {
-             using T = decltype(t);
-             HIP_TRY(launch_mk_stage<T>(w->dm, B, stage, dt, q, v, w->d_vdwork.p, w->mk, Lq, Lv, w->stream));
-             HIP_TRY(launch_contact_stage<T>(ns, stage, dt, s, w->d_sdot.p, w->d_s0.p, w->d_sacc.p, w->stream));
-             return RBD_OK;
-           })))
-        return st;
-      if (stage < 4) {
-        if ((st = run_contact(w, B, o, q, v, s, w->d_sdot.p, fext, nullptr, w->d_tw.p))) return st;
-        if ((st = run_dynamics(w, B, o, q, v, tau, w->d_tw.p, w->d_vdwork.p, nullptr, nullptr))) return st;
-      }
-    }
-  }
-  return RBD_OK;
-}
-
-// rbd_simulate_contact's step with simulate_core's controllers, on a stage of its own (rbd_contact_sim_kernels.hip): launch_mk_stage leaves the stage state
-// in (q, v); contact_head_kernel exports its per-body kinematics and evaluates the PD law on it; contact_sim_kernel takes s through the tableau to the same
-// stage state, evaluates the contact model there and writes ṡ, the reset s and the total wrenches; run_dynamics (whatever route it picks) solves v̇ at the
-// stage's τ — so the controller, contact_dynamics! and dynamics! of a stage all see one state.  The closing stage is launch_mk_stage(4) + contact_sim_kernel(4).
-int rbd_simulate_contact_controlled(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, const rbd_control_t* control, const void* fext, double dt,
-                                    int32_t nsteps, const rbd_opts_t* opts) {
+// `simulate` of a mechanism with contact points under simulate_core's controllers (rbd_simulate_contact: constant τ), on a stage of its own
+// (rbd_contact_sim_kernels.hip): launch_mk_stage leaves the stage state in (q, v) (MuntheKaasIntegrator.step, src/ode_integrators.jl:233-299);
+// contact_head_kernel exports its per-body kinematics and evaluates the PD law on it; contact_sim_kernel takes s through the tableau to the same stage state,
+// evaluates the contact model there and writes ṡ, the reset s and the total wrenches; run_dynamics (whatever route it picks) solves v̇ at the stage's τ — so the
+// controller, contact_dynamics! and dynamics! of a stage all see one state.  The closing stage is launch_mk_stage(4) + contact_sim_kernel(4).
+static int simulate_contact_core(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, const rbd_control_t* control, const void* fext, double dt, int32_t nsteps,
+                                 const rbd_opts_t* opts) {
   Opts o;
   int st = begin_call(w, B, opts, kUpTo64Bodies, &o);  // (its stage launches are the lane-per-body kernels')
   if (st != RBD_OK) return st;
-  if ((st = contact_scope(w, o))) return st;  // (no contact points: rbd_simulate_controlled)
-  if (!control || !q || !v || !s || nsteps < 0 || !(dt > 0)) return RBD_ERR_INVALID_ARGUMENT;
+  if ((st = contact_scope(w, o))) return st;  // (no contact points: rbd_simulate, rbd_simulate_controlled)
+  if (!control || !q || !v || !s || nsteps < 0 || !(dt > 0)) return RBD_ERR_INVALID_ARGUMENT;  // (a NULL descriptor here, not in the wrapper: the scope answers first)
   const rbd_control_t& ctl = *control;
-  if (ctl.kind < RBD_CONTROL_CONSTANT || ctl.kind > RBD_CONTROL_PD) return RBD_ERR_INVALID_ARGUMENT;
-  if (ctl.kind == RBD_CONTROL_TABLE && !ctl.tau) return RBD_ERR_INVALID_ARGUMENT;
-  if (ctl.kind == RBD_CONTROL_PD && (!ctl.kp || !ctl.kd)) return RBD_ERR_INVALID_ARGUMENT;
+  if ((st = control_check(ctl))) return st;
   if (B == 0 || nsteps == 0) return RBD_OK;
   HIP_TRY(hipSetDevice(w->device));
   const rbd_model* m = w->model;
@@ -2260,11 +2239,7 @@ int rbd_simulate_contact_controlled(rbd_ws_t* w, int32_t B, void* q, void* v, vo
   const Layout Lq = layout_of(o.layout, m->nq, B), Lv = layout_of(o.layout, m->nv, B), Lf = layout_of(o.layout, 6L * m->nb, B),
                Ls = layout_of(o.layout, 3L * m->ncp * m->nhs, B);
   // the torques of (step, stage): constant, an entry of the table, or the buffer contact_head_kernel fills from the feed-forward
-  auto tau_at = [&](int step, int stage) -> const void* {
-    if (pd) return w->d_tauwork.p;
-    if (ctl.kind != RBD_CONTROL_TABLE) return ctl.tau;
-    return (const char*)ctl.tau + entry * (size_t)(ctl.per_stage ? 4 * step + stage : step);
-  };
+  const ControlTau tau{ctl, pd ? w->d_tauwork.p : ctl.tau, entry};
   for (int step = 0; step < nsteps; ++step) {
     for (int stage = 0; stage <= 4; ++stage) {
       if ((st = by_dtype(w->dtype, [&](auto t) -> int {
@@ -2277,12 +2252,23 @@ int rbd_simulate_contact_controlled(rbd_ws_t* w, int32_t B, void* q, void* v, vo
              return RBD_OK;
            })))
         return st;
-      if (stage < 4 && (st = run_dynamics(w, B, o, q, v, tau_at(step, stage), w->d_tw.p, w->d_vdwork.p, nullptr, nullptr))) return st;
+      if (stage < 4 && (st = run_dynamics(w, B, o, q, v, tau.at(step, stage), w->d_tw.p, w->d_vdwork.p, nullptr, nullptr))) return st;
     }
   }
   w->last_kernel_text = std::string("contact_head_kernel + contact_sim_kernel + ") + w->last_kernel;  // (run_dynamics named its route)
   w->last_kernel = w->last_kernel_text.c_str();
   return RBD_OK;
+}
+int rbd_simulate_contact(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, const void* tau, const void* fext, double dt, int32_t nsteps,
+                         const rbd_opts_t* opts) {
+  rbd_control_t ctl{};
+  ctl.kind = RBD_CONTROL_CONSTANT;
+  ctl.tau = tau;
+  return simulate_contact_core(w, B, q, v, s, &ctl, fext, dt, nsteps, opts);
+}
+int rbd_simulate_contact_controlled(rbd_ws_t* w, int32_t B, void* q, void* v, void* s, const rbd_control_t* control, const void* fext, double dt,
+                                    int32_t nsteps, const rbd_opts_t* opts) {
+  return simulate_contact_core(w, B, q, v, s, control, fext, dt, nsteps, opts);
 }
 
 int rbd_cholesky_solve(rbd_ws_t* w, int32_t B, const void* M, const void* rhs, void* x, void* L_out, const rbd_opts_t* opts) {

@@ -335,7 +335,7 @@ template <typename T> RBD_HD bool contact_pair_adjoint(const T* pos, const T* ve
 }
 
 // ---- the friction state through the Runge–Kutta tableau (rbd_simulate_contact_vjp) ---------------------------------------------------------------------------
-// contact_stage_kernel's map (runge_kutta_4, ode_integrators.jl:48-55) in its value form, stage k = 0 … 3 like mk_stage_value_joint: from the step's start s0
+// contact_sim_kernel's map of s (runge_kutta_4, ode_integrators.jl:48-55) in its value form, stage k = 0 … 3 like mk_stage_value_joint: from the step's start s0
 // and ṡ_k at stage state k, the next stage state s_{k+1} = s0 + dt a_k ṡ_k and the running sum acc = Σ_{j ≤ k} dt b_j ṡ_j (stages 0-2; acc is not read at stage
 // 0), or at stage 3 the state after the step s⁺ = s0 + acc + dt b_3 ṡ_3.  The stage states stay apart from s0: the reset of an outside pair's state happens in
 // the stage state only.  Templated on the scalar: tests/test_simulate_contact_vjp_cpu.py takes J·d from the Dual<double, 1> instantiation.

@@ -1,9 +1,11 @@
 // rbd_contact_kernels.hip — soft contact on the device: contact_dynamics! (src/mechanism_algorithms.jl:680-723) with the reference's
 // default models (src/contact.jl: HuntCrossleyModel :98-119, ViscoelasticCoulombModel :122-178, HalfSpace3D :202-228), and the
-// Runge–Kutta bookkeeping of the additional state for `simulate` (src/ode_integrators.jl:233-299).
+// Runge–Kutta bookkeeping of the additional state for the derivatives of `simulate` (src/ode_integrators.jl:233-299; `simulate`
+// itself: rbd_contact_sim_kernels.hip).
 //
-// contact_kernel: one thread per state.  Body transforms and twists come from the per-body kinematics rnea_kernel exports
-// ([state][body][24]: R, p, twist, acceleration); the thread walks the contact points in the order of the additional state, tests each
+// contact_kernel: one thread per state.  Body transforms and twists come from the exported per-body kinematics ([state][body][24]:
+// R, p, twist in slots 0 … 17 — contact_head_kernel's export, or the any-size kernels' on trees of more than 64 bodies); the thread
+// walks the contact points in the order of the additional state, tests each
 // against every half-space and adds its wrench to its body's; it writes contactwrenches and totalwrenches = wext + contactwrenches
 // (mechanism_algorithms.jl:851-856) for EVERY body, so the forward-dynamics launch that follows reads one wrench buffer.
 // No contact configuration is on a BASELINE hot path: clarity over speed here.
@@ -79,13 +81,8 @@ __global__ __launch_bounds__(256) void contact_adjoint_kernel(ContactModel M, lo
     const int body_i = M.cbody[ip];
     const T* k = body + (b * M.nb + body_i) * 24;
     const T* c = cp + (long)ip * CP_STRIDE;
-    T pt[3], vel[3], t3[3], wb[6], pb[3] = {T(0), T(0), T(0)}, vb[3] = {T(0), T(0), T(0)};
-    matvec3(k, c + CP_LOC, pt);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) pt[j] += k[9 + j];
-    cross3(k + 12, pt, t3);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) vel[j] = t3[j] + k[15 + j];
+    T pt[3], vel[3], wb[6], pb[3] = {T(0), T(0), T(0)}, vb[3] = {T(0), T(0), T(0)};
+    contact_point_in_root(k, c, pt, vel);
 #pragma unroll
     for (int j = 0; j < 6; ++j) wb[j] = wbar ? wbar[(long)(6 * body_i + j) * Lf.sk + bf] : T(0);
     for (int h = 0; h < M.nh; ++h) {
@@ -115,24 +112,8 @@ __global__ __launch_bounds__(256) void contact_adjoint_kernel(ContactModel M, lo
   }
 }
 
-// the additional state through a Runge–Kutta step, stage by stage like mk_stage_kernel does (q, v):
-//   stage 0: s0 = s;  stage k = 1..3: acc += b_k ṡ_k, s = s0 + a_{k+1,k} dt ṡ_k;  stage 4: s = s0 + dt (acc + b_4 ṡ_4)
-// with the runge_kutta_4 tableau (ode_integrators.jl:48-55): a = 1/2, 1/2, 1; b = 1/6, 1/3, 1/3, 1/6.
-template <typename T>
-__global__ __launch_bounds__(256) void contact_stage_kernel(long n, int stage, T dt, T* __restrict__ s, const T* __restrict__ sdot, T* __restrict__ s0,
-                                                           T* __restrict__ acc) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  if (stage == 0) { s0[i] = s[i]; acc[i] = T(0); return; }
-  const T bk = (stage == 1 || stage == 4) ? T(1) / T(6) : T(1) / T(3);
-  const T a = acc[i] + bk * sdot[i];
-  if (stage == 4) { s[i] = s0[i] + dt * a; return; }
-  acc[i] = a;
-  s[i] = s0[i] + (stage == 3 ? T(1) : T(0.5)) * dt * sdot[i];
-}
-
-// The value form of contact_stage_kernel for rbd_simulate_contact_vjp (rbd_contact.hpp contact_stage_value), elementwise over the ns·B values like
-// value_mk_stage_kernel over the joints: stage 0 … 3, the stage states and the sum in buffers of their own (sn may be s0 itself at stage 3).
+// The additional state through a Runge–Kutta step in value form for rbd_simulate_contact_vjp (rbd_contact.hpp contact_stage_value), elementwise over the ns·B
+// values like value_mk_stage_kernel over the joints: stage 0 … 3, the stage states and the sum in buffers of their own (sn may be s0 itself at stage 3).
 template <typename T>
 __global__ __launch_bounds__(256) void contact_stage_value_kernel(long n, int stage, T dt, const T* s0, const T* __restrict__ sdot, T* __restrict__ acc, T* sn) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -171,13 +152,8 @@ __global__ __launch_bounds__(256) void contact_stage_adjoint_kernel(ContactModel
     const int body_i = M.cbody[ip];
     const T* k = body + (b * M.nb + body_i) * 24;
     const T* c = cp + (long)ip * CP_STRIDE;
-    T pt[3], vel[3], t3[3], wb[6], pb[3] = {T(0), T(0), T(0)}, vb[3] = {T(0), T(0), T(0)};
-    matvec3(k, c + CP_LOC, pt);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) pt[j] += k[9 + j];
-    cross3(k + 12, pt, t3);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) vel[j] = t3[j] + k[15 + j];
+    T pt[3], vel[3], wb[6], pb[3] = {T(0), T(0), T(0)}, vb[3] = {T(0), T(0), T(0)};
+    contact_point_in_root(k, c, pt, vel);
 #pragma unroll
     for (int j = 0; j < 6; ++j) wb[j] = wbar[(long)(6 * body_i + j) * Lf.sk + bf];
     for (int h = 0; h < M.nh; ++h) {
@@ -224,11 +200,6 @@ hipError_t launch_contact_adjoint(const ContactModel& M, long B, const void* bod
   return hipGetLastError();
 }
 template <typename T>
-hipError_t launch_contact_stage(long n, int stage, double dt, void* s, const void* sdot, void* s0, void* acc, hipStream_t st) {
-  contact_stage_kernel<T><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, stage, (T)dt, (T*)s, (const T*)sdot, (T*)s0, (T*)acc);
-  return hipGetLastError();
-}
-template <typename T>
 hipError_t launch_contact_stage_value(long n, int stage, double dt, const void* s0, const void* sdot, void* acc, void* sn, hipStream_t st) {
   contact_stage_value_kernel<T><<<(unsigned)((n + 255) / 256), 256, 0, st>>>(n, stage, (T)dt, (const T*)s0, (const T*)sdot, (T*)acc, (T*)sn);
   return hipGetLastError();
@@ -246,8 +217,6 @@ template hipError_t launch_contact_adjoint<double>(const ContactModel&, long, co
                                                   Layout, Layout, hipStream_t);
 template hipError_t launch_contact_adjoint<float>(const ContactModel&, long, const void*, const void*, const void*, const void*, const void*, void*, void*, void*, Layout,
                                                  Layout, Layout, hipStream_t);
-template hipError_t launch_contact_stage<double>(long, int, double, void*, const void*, void*, void*, hipStream_t);
-template hipError_t launch_contact_stage<float>(long, int, double, void*, const void*, void*, void*, hipStream_t);
 template hipError_t launch_contact_stage_value<double>(long, int, double, const void*, const void*, void*, void*, hipStream_t);
 template hipError_t launch_contact_stage_value<float>(long, int, double, const void*, const void*, void*, void*, hipStream_t);
 template hipError_t launch_contact_stage_adjoint<double>(const ContactModel&, long, int, double, const void*, const void*, const void*, void*, void*, void*, void*, void*,

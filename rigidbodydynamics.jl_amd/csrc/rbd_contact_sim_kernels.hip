@@ -1,16 +1,20 @@
-// rbd_contact_sim_kernels.hip — the stage of rbd_simulate_contact_controlled: `simulate(state, T, control!)` of a mechanism with contact points
-// (src/simulate.jl:36-55 — control! runs before every stage's dynamics!, which begins with contact_dynamics!, src/mechanism_algorithms.jl:845-864).
+// rbd_contact_sim_kernels.hip — the per-body kinematics every contact route of a tree of at most 64 bodies reads, and the stage of `simulate` with contact
+// points (rbd_simulate_contact, rbd_simulate_contact_controlled: src/simulate.jl:36-55 — control! runs before every stage's dynamics!, which begins with
+// contact_dynamics!, src/mechanism_algorithms.jl:845-864).
 //
 // Between launch_mk_stage, which leaves the stage state in (q, v), and the forward-dynamics launch the stage needs three things: the controller's τ on the stage
 // state, the per-body kinematics the contact model reads, and the friction state s taken through the Runge–Kutta tableau, evaluated and reset.  Two kernels:
 //
 // contact_head_kernel: one lane per (state, body) like rnea_kernel — the top-down kinematics sweep only (transforms to root and twists), exported as
-//   [state][body][24] (R, p, twist; slots 18 … 23, rnea_kernel's accelerations, are not written: contact_kernel and contact_sim_kernel read 0 … 17), and, for
-//   RBD_CONTROL_PD, pd_control_lane's law on the lane's joint into the τ buffer of the stage.  No accelerations, no Newton–Euler wrench, no bottom-up sweep, no
-//   bias torque: it stands for pd_control_kernel plus the whole of rnea_kernel.
-// contact_sim_kernel: one thread per state like contact_kernel — contact_stage_kernel's tableau for s folded into contact_kernel's walk over the (point,
-//   half-space) pairs: each pair's three values of s are advanced from (s0, acc, the previous stage's ṡ), the pair model (rbd_contact.hpp contact_pair_wrench:
-//   contact_kernel's) is evaluated on them, ṡ and the reset s are written and the wrench is added into totalwrenches = fext + contact.  Stage 4 only closes s.
+//   [state][body][24] (R, p, twist; slots 18 … 23, where rnea_kernel's export has accelerations, are not written: contact_kernel, contact_sim_kernel and the
+//   adjoint contact kernels read 0 … 17), and, for RBD_CONTROL_PD, pd_control_lane's law on the lane's joint into the τ buffer of the stage.  No accelerations,
+//   no Newton–Euler wrench, no bottom-up sweep, no bias torque.  Besides the simulate stage it serves run_contact_kinematics (rbd_capi.hip) with
+//   tau_out = nullptr: rbd_contact_dynamics, rbd_dynamics_contact and the forward contact launches of the contact derivative drivers.
+// contact_sim_kernel: one thread per state like contact_kernel — the tableau for s folded into contact_kernel's walk over the (point, half-space) pairs:
+//   each pair's three values of s are advanced from (s0, acc, the previous stage's ṡ), the pair model (rbd_contact.hpp contact_pair_wrench: contact_kernel's)
+//   is evaluated on them, ṡ and the reset s are written and the wrench is added into totalwrenches = fext + contact.  Stage 4 only closes s.
+//   The tableau (runge_kutta_4, src/ode_integrators.jl:48-55: a = 1/2, 1/2, 1; b = 1/6, 1/3, 1/3, 1/6), stage by stage like mk_stage_kernel does (q, v):
+//     stage 0: s0 = s, acc = 0;  stage k = 1 … 3: acc += b_k ṡ_k, s = s0 + a_{k+1,k} dt ṡ_k;  stage 4: s = s0 + dt (acc + b_4 ṡ_4).
 #include "rbd_device.hpp"
 #include "rbd_internal.hpp"
 #include "rbd_lane.hpp"
@@ -48,15 +52,15 @@ __global__ __launch_bounds__(256) void contact_head_kernel(DevModel M, long B, c
   }
 }
 
-// stage 0 … 3: s0, acc, sdot as contact_stage_kernel keeps them (the call's layout Ls, like s); `sdot` holds the previous stage's ṡ on entry and this stage's on
+// stage 0 … 3: s0, acc, sdot in the call's layout Ls, like s; `sdot` holds the previous stage's ṡ on entry and this stage's on
 // return.  stage 4: s = s0 + dt (acc + b_4 ṡ_4), one thread per VALUE of s; nothing else is touched (body, fext, tw are not read).
 template <typename T>
 __global__ __launch_bounds__(256) void contact_sim_kernel(ContactModel M, long B, int stage, T dt, const T* __restrict__ body, T* __restrict__ s,
                                                          T* __restrict__ sdot, T* __restrict__ s0, T* __restrict__ acc, const T* __restrict__ fext,
                                                          T* __restrict__ tw, Layout Ls, Layout Lf) {
   const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const T bk = (stage == 1 || stage == 4) ? T(1) / T(6) : T(1) / T(3);  // contact_stage_kernel's weights: b of the stage whose ṡ comes in
-  if (stage == 4) {  // uniform.  Element-wise over the ns·B values like contact_stage_kernel (the launcher sizes the grid for it): the four buffers share a layout
+  const T bk = (stage == 1 || stage == 4) ? T(1) / T(6) : T(1) / T(3);  // b of the stage whose ṡ comes in
+  if (stage == 4) {  // uniform.  Element-wise over the ns·B values (the launcher sizes the grid for it): the four buffers share a layout
     if (b >= 3L * M.np * M.nh * B) return;
     const T a = acc[b] + bk * sdot[b];
     s[b] = s0[b] + dt * a;

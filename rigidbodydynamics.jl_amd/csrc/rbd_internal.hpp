@@ -75,14 +75,14 @@ hipError_t launch_contact(const ContactModel& M, long B, const void* body, void*
 template <typename T>
 hipError_t launch_contact_adjoint(const ContactModel& M, long B, const void* body, const void* s, const void* wbar, const void* sdbar, const void* sobar, void* sbar,
                                   void* pbar, void* vbar, Layout Ls, Layout Lf, Layout L3, hipStream_t st);
-template <typename T> hipError_t launch_contact_stage(long n, int stage, double dt, void* s, const void* sdot, void* s0, void* acc, hipStream_t st);
 template <typename T> hipError_t launch_contact_stage_value(long n, int stage, double dt, const void* s0, const void* sdot, void* acc, void* sn, hipStream_t st);
 template <typename T>
 hipError_t launch_contact_stage_adjoint(const ContactModel& M, long B, int stage, double dt, const void* body, const void* s, const void* wbar, void* fbar, void* sbar,
                                         void* s0b, void* accb, void* pbar, void* vbar, Layout Ls, Layout Lf, Layout L3, hipStream_t st);
-// rbd_contact_sim_kernels.hip: the stage of rbd_simulate_contact_controlled.  launch_contact_head: the per-body kinematics [state][body][24] of the stage state
-// (R, p, twist; slots 18 … 23 not written) and, with tau_out != nullptr, the PD law's τ (tau_ff, qdes nullable: zero).  launch_contact_sim: s through the
-// tableau (stage 0 … 4, contact_stage_kernel's buffers) and, at stages 0 … 3, contact_kernel's model on it: ṡ, the reset s and tw = fext + contact wrenches.
+// rbd_contact_sim_kernels.hip.  launch_contact_head: the per-body kinematics [state][body][24] of (q, v) every contact route reads (R, p, twist; slots 18 … 23
+// not written) and, with tau_out != nullptr, the PD law's τ (tau_ff, qdes nullable: zero).  launch_contact_sim, the stage of rbd_simulate_contact[_controlled]:
+// s through the tableau (stage 0 … 4; s0, acc, sdot in the call's layout) and, at stages 0 … 3, contact_kernel's model on it: ṡ, the reset s and
+// tw = fext + contact wrenches.
 template <typename T>
 hipError_t launch_contact_head(const DevModel& M, long B, const void* q, const void* v, const void* tau_ff, const void* qdes, const void* kp, const void* kd,
                                void* tau_out, void* body_out, Layout Lq, Layout Lv, hipStream_t st);

@@ -857,83 +857,67 @@ def simulate_(state: MechanismState, final_time: float, control_=None, dt: float
     opts = state._opts(_capi.ALGO_ABA, _set_stabilization_gains(state, stabilization_gains))
     L = _capi.lib()
     ts, t = [0.0], 0.0
-    qs, vs = ([state.q.clone()], [state.v.clone()]) if store else (None, None)
     nsteps = 0
     while t < final_time:  # ode_integrators.jl:311-314
         t += dt
         ts.append(t)
         nsteps += 1
+    contact = getattr(f, "ns", 0) > 0  # soft contact: the additional state s is integrated beside (q, v)
     device_ctl = isinstance(control_, (TorqueTable, PDControl))
     if device_ctl:
         if torques is not None:
             raise ValueError("pass the torques through the controller object")
-        ctl, keep = _control_descriptor(state, control_, nsteps)
+        ctl, keep = _control_descriptor(state, control_, nsteps)  # (keep: the tensors the descriptor points into, alive until this function returns)
         if store:
             raise NotImplementedError("store=True with a device-side controller: call simulate_ once per step")
-    if getattr(f, "ns", 0) > 0:  # soft contact: the additional state is integrated beside (q, v)
-        if device_ctl:  # the controller on the device, on the stage state contact_dynamics! and dynamics! see (rbd_simulate_contact_controlled)
-            _raise(L.rbd_simulate_contact_controlled(state.ws.handle, state.batch, _ptr(state.q), _ptr(state.v), _ptr(state.s), ctypes.byref(ctl),
-                                                     _ptr(externalwrenches), ctypes.c_double(dt), nsteps, ctypes.byref(opts)), "rbd_simulate_contact_controlled")
-            del keep
-            return np.array(ts)
-        ss = [state.s.clone()] if store else None
-        if control_ is not None:
-            # control_(torques, t, state) on the host before every stage's dynamics!: rbd_mk_stage for (q, v), the same tableau for s here (what
-            # contact_stage_kernel does: s0 is the step's start before any reset, the reset of rbd_dynamics_contact acts on the stage state only)
-            tau = torch.zeros_like(state.v) if torques is None else torques
-            vd, sd = torch.zeros_like(state.v), torch.zeros_like(state.s)
-            for k in range(nsteps):
-                for stage in range(5):
-                    _raise(L.rbd_mk_stage(state.ws.handle, state.batch, stage, ctypes.c_double(dt), _ptr(state.q), _ptr(state.v),
-                                          _ptr(vd if stage > 0 else None), ctypes.byref(opts)), "rbd_mk_stage")
-                    if stage == 0:
-                        s0, acc = state.s.clone(), torch.zeros_like(state.s)
-                    else:
-                        acc = acc + (1 / 6 if stage in (1, 4) else 1 / 3) * sd
-                        state.s.copy_(s0 + dt * acc if stage == 4 else s0 + (1.0 if stage == 3 else 0.5) * dt * sd)
-                    if stage < 4:
-                        control_(tau, ts[k] + RK4_C[stage] * dt, state)
-                        _raise(L.rbd_dynamics_contact(state.ws.handle, state.batch, _ptr(state.q), _ptr(state.v), _ptr(state.s), _ptr(tau), _ptr(externalwrenches),
-                                                      _ptr(vd), None, _ptr(sd), None, None, ctypes.byref(opts)), "rbd_dynamics_contact")
-                if store:
-                    qs.append(state.q.clone()); vs.append(state.v.clone()); ss.append(state.s.clone())
-            return (np.array(ts), qs, vs, ss) if store else np.array(ts)
-        for _ in range(nsteps if store else 1):
-            _raise(L.rbd_simulate_contact(state.ws.handle, state.batch, _ptr(state.q), _ptr(state.v), _ptr(state.s), _ptr(torques), _ptr(externalwrenches),
-                                          ctypes.c_double(dt), 1 if store else nsteps, ctypes.byref(opts)), "rbd_simulate_contact")
-            if store:
-                qs.append(state.q.clone()); vs.append(state.v.clone()); ss.append(state.s.clone())
-        return (np.array(ts), qs, vs, ss) if store else np.array(ts)
-    if device_ctl:
-        _raise(L.rbd_simulate_controlled(state.ws.handle, state.batch, _ptr(state.q), _ptr(state.v), ctypes.byref(ctl), _ptr(externalwrenches),
-                                         ctypes.c_double(dt), nsteps, ctypes.byref(opts)), "rbd_simulate_controlled")
-        del keep
-    elif control_ is None and not store:
-        _raise(L.rbd_simulate(state.ws.handle, state.batch, _ptr(state.q), _ptr(state.v), _ptr(torques), _ptr(externalwrenches),
-                              ctypes.c_double(dt), nsteps, ctypes.byref(opts)), "rbd_simulate")
-    elif control_ is None:
-        for _ in range(nsteps):
-            _raise(L.rbd_simulate(state.ws.handle, state.batch, _ptr(state.q), _ptr(state.v), _ptr(torques), _ptr(externalwrenches),
-                                  ctypes.c_double(dt), 1, ctypes.byref(opts)), "rbd_simulate")
-            qs.append(state.q.clone())
-            vs.append(state.v.clone())
+    snaps = [[x.clone()] for x in ((state.q, state.v, state.s) if contact else (state.q, state.v))] if store else None  # qs, vs(, ss)
+
+    def snapshot():
+        for xs, x in zip(snaps, (state.q, state.v, state.s)):
+            xs.append(x.clone())
+
+    def advance(n):
+        """n steps on the device: rbd_simulate[_contact][_controlled] — with contact points s rides beside (q, v); a device-side controller goes in as its
+        descriptor where the constant torques go otherwise"""
+        name = "rbd_simulate" + ("_contact" if contact else "") + ("_controlled" if device_ctl else "")
+        x = (_ptr(state.q), _ptr(state.v)) + ((_ptr(state.s),) if contact else ())
+        _raise(getattr(L, name)(state.ws.handle, state.batch, *x, ctypes.byref(ctl) if device_ctl else _ptr(torques), _ptr(externalwrenches), ctypes.c_double(dt),
+                                n, ctypes.byref(opts)), name)
+
+    if device_ctl or control_ is None:
+        if store:
+            for _ in range(nsteps):
+                advance(1)
+                snapshot()
+        else:
+            advance(nsteps)
     else:
+        # control_(torques, t, state) on the host before every stage's dynamics!: rbd_mk_stage for (q, v) and, with contact points, the same tableau for s here
+        # (what contact_sim_kernel does: s0 is the step's start before any reset, the reset of rbd_dynamics_contact acts on the stage state only)
         tau = torch.zeros_like(state.v) if torques is None else torques
-        vd = torch.zeros_like(state.v)
-        lam = torch.zeros((state.batch, max(f.nc, 1)), dtype=state.dtype, device=state.device)
+        vd, sd = torch.zeros_like(state.v), torch.zeros_like(state.s)
+        lam = torch.zeros((state.batch, f.nc), dtype=state.dtype, device=state.device) if f.nc else None
         for k in range(nsteps):
             for stage in range(5):
                 _raise(L.rbd_mk_stage(state.ws.handle, state.batch, stage, ctypes.c_double(dt), _ptr(state.q), _ptr(state.v),
                                       _ptr(vd if stage > 0 else None), ctypes.byref(opts)), "rbd_mk_stage")
-                if stage < 4:
-                    control_(tau, ts[k] + RK4_C[stage] * dt, state)
+                if contact and stage == 0:
+                    s0, acc = state.s.clone(), torch.zeros_like(state.s)
+                elif contact:
+                    acc = acc + (1 / 6 if stage in (1, 4) else 1 / 3) * sd
+                    state.s.copy_(s0 + dt * acc if stage == 4 else s0 + (1.0 if stage == 3 else 0.5) * dt * sd)
+                if stage == 4:
+                    break
+                control_(tau, ts[k] + RK4_C[stage] * dt, state)
+                if contact:
+                    _raise(L.rbd_dynamics_contact(state.ws.handle, state.batch, _ptr(state.q), _ptr(state.v), _ptr(state.s), _ptr(tau), _ptr(externalwrenches),
+                                                  _ptr(vd), None, _ptr(sd), None, None, ctypes.byref(opts)), "rbd_dynamics_contact")
+                else:
                     _raise(L.rbd_dynamics(state.ws.handle, state.batch, _ptr(state.q), _ptr(state.v), _ptr(tau), _ptr(externalwrenches),
-                                          _ptr(vd), None, _ptr(lam if f.nc else None), ctypes.byref(opts)), "rbd_dynamics")
+                                          _ptr(vd), None, _ptr(lam), ctypes.byref(opts)), "rbd_dynamics")
             if store:
-                qs.append(state.q.clone())
-                vs.append(state.v.clone())
-    ts = np.array(ts)
-    return (ts, qs, vs) if store else ts
+                snapshot()
+    return (np.array(ts), *snaps) if store else np.array(ts)
 
 
 def dynamics_ode_(xd: torch.Tensor, result: DynamicsResult, state: MechanismState, x: torch.Tensor, torques: Optional[torch.Tensor] = None,

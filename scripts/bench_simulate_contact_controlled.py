@@ -1,8 +1,10 @@
 """Times `simulate` with soft contact under a device-side controller on Atlas with a floating base, four contact points per foot and one floor (the set-up of
-scripts/bench_contact_vjp.py), per step of a `--steps`-step call, four ways in one run:
+scripts/bench_contact_vjp.py), per step of a `--steps`-step call, four ways in one run — and (e) one rbd_dynamics_contact call on the same inputs, per call:
   (a) rbd_simulate_contact_controlled with RBD_CONTROL_CONSTANT: the stage of contact_head_kernel + contact_sim_kernel;
   (b) the same with RBD_CONTROL_PD (feed-forward, q_des, small gains on every 1-dof joint);
-  (c) rbd_simulate_contact on the same inputs: the stage of contact_stage_kernel + rnea_kernel + contact_kernel — the yardstick, (a) computes the same thing;
+  (c) rbd_simulate_contact on the same inputs: the constant kind of (a) behind its own entry point, so the same stage — it ran a stage of its own
+      (a kernel for s + rnea_kernel + contact_kernel) until the two were folded; the leg stays as the measurement of rbd_simulate_contact against a library
+      built from an earlier commit (RBD_LIB);
   (d) rbd_simulate of the mechanism without contact points: what contact costs on top.
 Every call starts from the same state (copied in before the call, inside the timed region of all four).  HIP events around `--iters` calls after `--warmup`;
 the four are timed in turn, `--repeats` rounds, and the median with the lowest and highest round is recorded: a difference inside that spread is not one.
@@ -80,7 +82,14 @@ def case(bare, dtype, B, steps, iters, warmup, repeats):
         start(2)
         C.check(L.rbd_simulate(sb.ws.handle, B, p(work[0]), p(work[1]), p(tau), p(fext), ctypes.c_double(DT), steps, ctypes.byref(ob)), "rbd_simulate")
 
-    legs = dict(a=controlled(const), b=controlled(pd), c=contact, d=bare_sim)
+    vd, sd = torch.empty_like(v), torch.empty_like(s)
+
+    def dynamics_contact():
+        start(3)
+        C.check(L.rbd_dynamics_contact(sc.ws.handle, B, p(work[0]), p(work[1]), p(work[2]), p(tau), p(fext), p(vd), None, p(sd), None, None, ctypes.byref(oc)),
+                "rbd_dynamics_contact")
+
+    legs = dict(a=controlled(const), b=controlled(pd), c=contact, d=bare_sim, e=dynamics_contact)
     state_of = lambda: [x.clone() for x in work]
     legs["a"](); a_out, a_kernel = state_of(), rbd.last_kernel(sc)
     legs["b"](); b_kernel = rbd.last_kernel(sc)
@@ -90,13 +99,13 @@ def case(bare, dtype, B, steps, iters, warmup, repeats):
     ms = {k: [] for k in legs}
     for r in range(repeats):
         for k in legs:
-            ms[k].append(timed(legs[k], iters, warmup if r == 0 else 1) / steps)
+            ms[k].append(timed(legs[k], iters, warmup if r == 0 else 1) / (1 if k == "e" else steps))
     fig = lambda k: dict(median=round(statistics.median(ms[k]), 4), low=round(min(ms[k]), 4), high=round(max(ms[k]), 4))
-    names = dict(a="a_controlled_constant", b="b_controlled_pd", c="c_simulate_contact", d="d_simulate_bare")
+    names = dict(a="a_controlled_constant", b="b_controlled_pd", c="c_simulate_contact", d="d_simulate_bare", e="e_dynamics_contact")
     out = dict(metric="simulate_contact_controlled", mechanism="atlas_floating", contact_points=P, halfspaces=1, dtype=str(dtype).replace("torch.", ""), B=B, nq=nq,
                nv=nv, ns=ns, steps=steps, dt=DT, iters=iters, repeats=repeats)
     for k in legs:
-        out[names[k] + "_ms_per_step"] = fig(k)
+        out[names[k] + ("_ms_per_call" if k == "e" else "_ms_per_step")] = fig(k)
     med = lambda k: statistics.median(ms[k])
     out.update(a_kernel=a_kernel, b_kernel=b_kernel, c_kernel=c_kernel, d_kernel=d_kernel, a_over_c=round(med("a") / med("c"), 3), b_over_c=round(med("b") / med("c"), 3),
                a_minus_d_ms_per_step=round(med("a") - med("d"), 4), a_vs_c_max_rel_diff=agree, device=torch.cuda.get_device_name(0))

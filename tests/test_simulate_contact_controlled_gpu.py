@@ -1,8 +1,11 @@
 """rbd_simulate_contact_controlled on the GPU: `simulate(state, T, control!)` of a mechanism with contact points under the device-side controllers, against
 the numpy step with a controller (tests/simulate_contact_controlled_ref.py: oracle/simulate_np.py's step around oracle.dynamics_contact), against
-rbd_simulate_contact (the CONSTANT kind), and the Python callback path of simulate_.  The conditions the parity tests assume of their inputs (branch margins,
+rbd_simulate_contact (the CONSTANT kind: one code path since the fold of DESIGN.md §3.14) and what rbd_simulate_contact / rbd_dynamics_contact computed before
+that fold (tests/golden/vectors/simulate_contact_parent.npz, recorded by tests/golden/make_simulate_contact_parent.py), and the Python callback path of
+simulate_.  The conditions the parity tests assume of their inputs (branch margins,
 pairs in and out of contact, branch changes) are asserted on the CPU, on the same inputs: test_simulate_contact_controlled_cpu.py."""
 import ctypes
+import hashlib
 import os
 
 import numpy as np
@@ -90,6 +93,8 @@ def simulate_contact(rbd, w, dtype=torch.float64, fext=True, layout="aos"):
     stt = rbd._capi.lib().rbd_simulate_contact(st.ws.handle, w["B"], ptr(q), ptr(v), ptr(s), ptr(tau), ptr(fe), ctypes.c_double(DT), w["nsteps"],
                                               ctypes.byref(st._opts()))
     assert stt == 0 and rbd.sync(st) == 0
+    k = rbd.last_kernel(st)
+    assert "contact_head_kernel" in k and "contact_sim_kernel" in k, k
     return host(q, layout), host(v, layout), host(s, layout)
 
 
@@ -107,6 +112,26 @@ def close(got, want, tol, what):
 
 
 @pytest.fixture(scope="module")
+def parent():
+    """What the commit before the fold computed on the walker's inputs, every `every`-th state (tests/golden/make_simulate_contact_parent.py)."""
+    return dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vectors", "simulate_contact_parent.npz")))
+
+
+def recorded(parent, w, name, keys="qvs"):
+    """The recorded arrays `name`_{keys} as fp64 — after the assertion that they were recorded on the inputs of `w`: a SHA-256 over the bytes of q, v, s, tau, fext."""
+    h = hashlib.sha256()
+    for k in ("q", "v", "s", "tau", "fext"):
+        h.update(np.ascontiguousarray(w[k], dtype=np.float64).tobytes())
+    assert h.hexdigest() == str(parent["input_hash"]), "walker_case no longer builds the inputs simulate_contact_parent.npz was recorded on"
+    return tuple(parent["%s_%s" % (name, k)].astype(np.float64) for k in keys)
+
+
+def thin(parent, got):
+    """the recorded states of full-batch results"""
+    return tuple(g[::int(parent["every"])] for g in got)
+
+
+@pytest.fixture(scope="module")
 def walker(rbd, oracle):
     """The walker, B = 130, 3 steps: the inputs and, per controller case, the reference's final state (computed once on first use, shared, left unchanged)."""
     w = ref.walker_case(rbd)
@@ -114,7 +139,8 @@ def walker(rbd, oracle):
 
     def reference(case):
         if case not in cache:
-            cache[case] = ref.rollout(oracle, w["flat"], w["q"], w["v"], w["s"], ref.walker_control(w, case), w["fext"], w["nsteps"])[:3]
+            ctl = ref.constant_control(w["tau"]) if case == "constant" else ref.walker_control(w, case)
+            cache[case] = ref.rollout(oracle, w["flat"], w["q"], w["v"], w["s"], ctl, w["fext"], w["nsteps"])[:3]
         return cache[case]
     return dict(w, reference=reference)
 
@@ -136,30 +162,65 @@ def test_atlas_with_pd_on_every_joint(rbd, oracle, models):
 
 
 @pytest.mark.parametrize("layout", ["aos", "soa"])
-def test_constant_kind_is_simulate_contact(rbd, walker, layout):
-    """CONSTANT against rbd_simulate_contact on the same inputs: fp64 within 1e-12·(1 + max), fp32 within 16·2⁻²³·(1 + max) (the head kernel's sweep orders
-    the same arithmetic differently from rnea_kernel's)."""
-    close(run_case(rbd, walker, "constant", layout), simulate_contact(rbd, walker, layout=layout), 1e-12, f"constant f64 {layout}")
-    close(run_case(rbd, walker, "constant", layout, torch.float32), simulate_contact(rbd, walker, torch.float32, layout=layout), 16 * 2.0 ** -23,
-          f"constant f32 {layout}")
+def test_constant_kind_is_simulate_contact(rbd, oracle, walker, parent, layout):
+    """CONSTANT and rbd_simulate_contact are one code path: equal bit for bit in fp64 and fp32 (the wrapper's forwarding of tau and fext).  Both against what
+    rbd_simulate_contact computed before the fold, on its stage of contact_stage_kernel + rnea_kernel + contact_kernel (recorded, AOS, every second state): fp64
+    within 1e-12·(1 + max), fp32 within 16·2⁻²³·(1 + max) (the head kernel's sweep orders the same arithmetic differently from rnea_kernel's).  And fp64 within
+    1e-10·(1 + max) of the numpy step with the constant controller, the reference of the four controller cases."""
+    for dtype, name, tol in ((torch.float64, "f64", 1e-12), (torch.float32, "f32", 16 * 2.0 ** -23)):
+        got = run_case(rbd, walker, "constant", layout, dtype)
+        plain = simulate_contact(rbd, walker, dtype, layout=layout)
+        for k, g, r in zip("qvs", got, plain):
+            assert np.array_equal(g, r), (name, k)
+        want = recorded(parent, walker, "sim_" + name)
+        if name == "f64":
+            print("constant f64 %s bit-identical to the recording: %s" % (layout, all(np.array_equal(g, r) for g, r in zip(thin(parent, got), want))))
+        close(thin(parent, got), want, tol, f"constant {name} {layout} vs recording")
+        close(thin(parent, plain), want, tol, f"simulate_contact {name} {layout} vs recording")
+        if name == "f64":
+            close(got, walker["reference"]("constant"), 1e-10, f"constant f64 {layout} vs numpy")
 
 
-def test_fp32_with_pd(rbd, oracle, walker):
-    """fp32, PD with feed-forward and q_des (no external wrenches: simulate_np.simulate_contact takes none), error against the fp64 numpy step.  The yardstick,
-    computed here: the error rbd_simulate_contact in fp32 shows against simulate_np.simulate_contact on the same inputs with the feed-forward as constant τ.
-    The bound is 4 × that (the trajectories differ).  Errors: max over q, v, s of max|err| / (1 + max|ref|)."""
+def test_fp32_with_pd(rbd, oracle, walker, parent):
+    """fp32, PD with feed-forward and q_des (no external wrenches: simulate_np.simulate_contact takes none), error against the fp64 numpy step.  The yardstick:
+    the error rbd_simulate_contact showed in fp32 BEFORE the fold (the recorded run without fext, on the recorded states — not the code under test) against
+    simulate_np.simulate_contact on the same inputs with the feed-forward as constant τ.  The bound is 4 × that (the trajectories differ).  Errors: max over
+    q, v, s of max|err| / (1 + max|ref|)."""
     import simulate_np as snp
     w = walker
     err = lambda got, want: max(np.abs((ref.canon(g) if n == "q" else g) - (ref.canon(r) if n == "q" else r)).max() / (1 + np.abs(r).max())
                                 for n, g, r in zip("qvs", got, want))
     want_c = snp.simulate_contact(w["flat"], w["q"], w["v"], w["s"], (w["nsteps"] - 0.5) * DT, DT, w["tau"])[1:]
-    yard = err(simulate_contact(rbd, w, torch.float32, fext=False), want_c)
+    yard = err(recorded(parent, w, "sim_f32_nofext"), thin(parent, want_c))
     want_pd = ref.rollout(oracle, w["flat"], w["q"], w["v"], w["s"], ref.walker_control(w, "pd"), None, w["nsteps"])[:3]
     got = run_case(rbd, w, "pd", dtype=torch.float32, fext=False)
     ours = err(got, want_pd)
-    print("fp32 PD error %.3e  yardstick (rbd_simulate_contact fp32) %.3e  ratio %.2f" % (ours, yard, ours / yard))
+    print("fp32 PD error %.3e  yardstick (rbd_simulate_contact fp32 before the fold, recorded) %.3e  ratio %.2f" % (ours, yard, ours / yard))
     assert all(np.isfinite(g).all() for g in got)
     assert ours <= 4 * yard
+
+
+@pytest.mark.parametrize("layout", ["aos", "soa"])
+def test_dynamics_contact_on_the_head_kernels_export(rbd, oracle, walker, parent, layout):
+    """rbd_dynamics_contact reads contact_head_kernel's export since the fold (run_contact_kinematics; rnea_kernel's before): v̇ and ṡ on the walker's inputs,
+    B = 130 (the head kernel's grid ends in a ragged block), against what the commit before computed — fp64 within 1e-12·(1 + max), fp32 within
+    16·2⁻²³·(1 + max) — and the pairs reset to s == 0 exactly those of oracle.dynamics_contact."""
+    w = walker
+    reset = oracle.dynamics_contact(w["flat"], w["q"], w["v"], w["s"].copy(), w["tau"], w["fext"])[1] == 0
+    assert reset.any() and not reset.all()
+    for dtype, name, tol in ((torch.float64, "f64", 1e-12), (torch.float32, "f32", 16 * 2.0 ** -23)):
+        want = recorded(parent, w, "dyn_" + name, ("vdot", "sdot"))
+        st = rbd.MechanismState(w["flat"], w["B"], dtype=dtype, layout=layout)
+        q, v, s, tau, fe = (dev(w[k], layout, dtype) for k in ("q", "v", "s", "tau", "fext"))
+        vd, sd = torch.empty_like(v), torch.empty_like(s)
+        assert rbd._capi.lib().rbd_dynamics_contact(st.ws.handle, w["B"], ptr(q), ptr(v), ptr(s), ptr(tau), ptr(fe), ptr(vd), None, ptr(sd), None, None,
+                                                    ctypes.byref(st._opts())) == 0
+        assert rbd.sync(st) == 0
+        for what, g, r in zip(("vdot", "sdot"), thin(parent, (host(vd, layout), host(sd, layout))), want):
+            e, bound = np.abs(g - r).max(), tol * (1 + np.abs(r).max())
+            print("dynamics_contact %s %s %-4s max|err| %.3e  max|ref| %.3e  bound %.3e" % (name, layout, what, e, np.abs(r).max(), bound))
+            assert np.isfinite(g).all() and e <= bound, (name, what)
+        assert np.array_equal(host(s, layout) == 0, reset), name
 
 
 def test_one_call_of_three_steps_is_three_calls_of_one(rbd, walker):
