@@ -50,6 +50,11 @@
 #ifndef RBD_BANK_ONE_BASE
 #define RBD_BANK_ONE_BASE RBD_BANK_UNROLLED  // 1: the 6-dof joint's q / v / tau / q̇ elements at one base address plus multiples of the stride
 #endif
+// The dynamics! program, plain and with the integrator stage fused in.  Off in the looped kernels, where the six values more that the kinematics
+// sweep carries around its loop spill the fp64 instantiations to scratch:
+#ifndef RBD_BANK_BIAS_SWEEP
+#define RBD_BANK_BIAS_SWEEP RBD_BANK_UNROLLED  // 1: the bias accelerations are summed on the way down (zt = zt_parent + [Tw_parent, Tw]) and enter the bias force once per
+#endif                                         //    bank (pA += I zt); the recursion then runs with c = 0 on a' = a - zt: no Ia c per hand-off, no a_parent + c per top-down step
 
 // Experiment (scripts/build_bank_variant.sh fixed -DRBD_BANK_FIXED_NL=11 -DRBD_BANK_FIXED_L0=5 "-DRBD_BANK_FIXED_NS=0,3,1,1,3,1,1,1,1,1,1"): the level structure of ONE
 // mechanism as compile-time constants and the level loops unrolled — what a per-mechanism compilation of this kernel (as rbd_jit.hip does for the large-batch
@@ -107,10 +112,13 @@ template <typename T, int N> RBD_DEV void massign(bool m, T* d, const T* s) {  /
 }
 
 // LDS layout, in pairs per lane (pair i of thread t at lds[i * 256 + t]):
-//   parked kinematics of bank 0: R 9, p 3 (pairs 0..5: stay for the 6-dof joints), Tw 6, vJ 6 (pairs 6..11)
-//   parked forward data of bank 1 (after bank 0's Tw, vJ are back in registers): U 6 (6..8), 1/D, u (9), S 6 (10..12), cb 6 (13..15)
-//   exchange column: 14 pairs (a hand-off is 21 + 6 values)
-enum { PK_KIN = 0, PK_FWD = 6, PARK_PAIRS = 16, PK_XCH = 16, XCH_PAIRS = 14, BANK_LDS_PAIRS = PARK_PAIRS + XCH_PAIRS };
+//   parked kinematics of bank 0: R 9, p 3 (pairs 0..5: stay for the 6-dof joints), Tw 6 (pairs 6..8)
+//   parked forward data of bank 1 (after bank 0's Tw is back in registers): U 6 (6..8), 1/D, u (9), S 6 (10..12)
+//   then, by the formulation:
+//     RBD_BANK_BIAS_SWEEP (the programs compiled per mechanism): bank 0's summed bias acceleration zt 6 in pairs 13..15, from the end of its kinematics sweep until its terms()
+//     otherwise (the looped kernels): bank 0's vJ 6 (or the joint velocity) behind Tw in pairs 9..11, bank 1's cb 6 behind S in pairs 13..15
+//   exchange column: 14 pairs (a hand-off is 21 + 6 values; a top-down hop through it is R, p, Tw in pairs 0..8 and zt in pairs 9..11)
+enum { PK_KIN = 0, PK_FWD = 6, PK_ZT = 13, PARK_PAIRS = 16, PK_XCH = 16, XCH_PAIRS = 14, BANK_LDS_PAIRS = PARK_PAIRS + XCH_PAIRS };
 
 template <typename T, int N> RBD_DEV void lds_put(Pair2<T>* col, int pair0, const T* x) {
 #pragma unroll
@@ -143,6 +151,7 @@ template <typename T> struct BankRegs {
   RBD_DEV T* Tw() { return K + 12; }
   RBD_DEV T* vJ() { return K + 18; }
   T S[6], cb[6], IA[21], pA[6], U[6], Dinv, u;
+  T zt[6];  // RBD_BANK_BIAS_SWEEP: the bias accelerations [Tw_parent, Tw] summed from the root down to this body (cb is not used then)
   T tj[6];  // joint torques (6 for the floating joint)
   T acc[6], vd[6];
 };
@@ -199,7 +208,18 @@ template <typename T> RBD_DEV void bank_store_v(const Body<T>& b, T* __restrict_
 // velocity), the joint twist is S v with S = X (a; 0) = (R a; p x R a); S itself and the bias term are formed after the sweep, for every lane
 // at once (terms()).  The new values are computed by EVERY lane and committed in the lanes at level l (massign).
 // RBD_BANK_COMMIT_INPLACE (the unrolled program: nothing is loop-carried): computed and assigned by the lanes at level l alone, under their exec mask.
-template <typename T, bool SIMPLE> RBD_DEV void bank_fk_new(const T* k18 /* the parent's R 9, p 3, Tw 6 */, const T* XR, const T* Xp, const T* tl, T* n) {
+// RBD_BANK_BIAS_SWEEP: the hop also brings the parent's summed bias acceleration (k24 = R 9, p 3, Tw 6, zt 6) and the body forms its own,
+// zt = zt_parent + [Tw_parent, Tw] (= zt_parent + [Tw, vJ], as Tw = Tw_parent + vJ): 18 fused multiply-adds, the same for every joint type (a fixed joint adds
+// [Tw, Tw] = 0); vJ and the joint velocity are then no longer carried (18 values per lane in both forms).
+template <typename T> RBD_DEV void bank_bias_accumulate(const T* zp, const T* x /* Tw_parent */, const T* y /* Tw */, T* z) {
+  z[0] = zp[0] + x[1] * y[2] - x[2] * y[1];
+  z[1] = zp[1] + x[2] * y[0] - x[0] * y[2];
+  z[2] = zp[2] + x[0] * y[1] - x[1] * y[0];
+  z[3] = zp[3] + x[1] * y[5] - x[2] * y[4] + x[4] * y[2] - x[5] * y[1];
+  z[4] = zp[4] + x[2] * y[3] - x[0] * y[5] + x[5] * y[0] - x[3] * y[2];
+  z[5] = zp[5] + x[0] * y[4] - x[1] * y[3] + x[3] * y[1] - x[4] * y[0];
+}
+template <typename T, bool SIMPLE> RBD_DEV void bank_fk_new(const T* k18 /* the parent's R 9, p 3, Tw 6 [, zt 6] */, const T* XR, const T* Xp, const T* tl, T* n, T* nz) {
   const T* pR = k18;
   const T* pp = k18 + 9;
   const T* pT = k18 + 12;
@@ -218,44 +238,57 @@ template <typename T, bool SIMPLE> RBD_DEV void bank_fk_new(const T* k18 /* the 
 #pragma unroll
     for (int k = 0; k < 6; ++k) n[12 + k] = pT[k] + n[18 + k];
   }
+  if (RBD_BANK_BIAS_SWEEP) bank_bias_accumulate(k18 + 18, pT, n + 12, nz);
 }
 template <typename T, bool SIMPLE> RBD_DEV void bank_fk_commit(bool mine, BankRegs<T>& c, const T* k18, const T* XR, const T* Xp, const T* tl) {
-  constexpr int NK = SIMPLE ? 18 : 24;
-  T n[24];
+  constexpr int NK = (SIMPLE || RBD_BANK_BIAS_SWEEP) ? 18 : 24;
+  T n[24], nz[6];
   if (RBD_BANK_COMMIT_INPLACE) {
     if (mine) {
       RBD_KEEP_BRANCH();
-      bank_fk_new<T, SIMPLE>(k18, XR, Xp, tl, n);
+      bank_fk_new<T, SIMPLE>(k18, XR, Xp, tl, n, nz);
 #pragma unroll
       for (int k = 0; k < NK; ++k) c.K[k] = n[k];
+      if (RBD_BANK_BIAS_SWEEP) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) c.zt[k] = nz[k];
+      }
     }
   } else {
-    bank_fk_new<T, SIMPLE>(k18, XR, Xp, tl, n);
+    bank_fk_new<T, SIMPLE>(k18, XR, Xp, tl, n, nz);
     massign<T, NK>(mine, c.K, n);
+    if (RBD_BANK_BIAS_SWEEP) massign<T, 6>(mine, c.zt, nz);
   }
 }
 // level l inside a bank.  On most levels every body is the first child of its parent = the previous lane: (R, p, Tw) arrive by DPP.  On the
 // levels where some body is a later child (perm_down) the parents leave theirs in their exchange column and every child reads its parent's.
 template <typename T, bool SIMPLE> RBD_DEV void bank_fk_step(const BankModel& M, int l, bool perm, BankRegs<T>& c, Pair2<T>* lds, const T* XR, const T* Xp, const T* tl) {
-  T k18[18];
+  T k18[24];
   if (RBD_BANK_FK_LDS || perm) {  // uniform
     if (c.b.level == l - 1 && c.b.nchild >= 1) {
       RBD_KEEP_BRANCH();
       lds_put<T, 18>(lds + threadIdx.x, PK_XCH, c.K);
+      if (RBD_BANK_BIAS_SWEEP) lds_put<T, 6>(lds + threadIdx.x, PK_XCH + 9, c.zt);
     }
     wave_lds_sync();
     lds_get<T, 18>(lds + c.pcol, PK_XCH, k18);  // (lanes that are not at level l read their parent's column too: whatever it holds is dropped)
+    if (RBD_BANK_BIAS_SWEEP) lds_get<T, 6>(lds + c.pcol, PK_XCH + 9, k18 + 18);
     wave_lds_sync();
   } else {
 #pragma unroll
     for (int k = 0; k < 18; ++k) k18[k] = from_prev_lane(c.K[k]);
+    if (RBD_BANK_BIAS_SWEEP) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) k18[18 + k] = from_prev_lane(c.zt[k]);
+    }
   }
   bank_fk_commit<T, SIMPLE>(c.b.level == l, c, k18, XR, Xp, tl);
 }
-// level L0: the parents are bank-0 bodies, whose (R, p, Tw) have just been parked — the children read their parent's parked pairs
+// level L0: the parents are bank-0 bodies, whose (R, p, Tw) [and zt] have just been parked — the children read their parent's parked pairs
 template <typename T, bool SIMPLE> RBD_DEV void bank_fk_cross(int L0, BankRegs<T>& c, const Pair2<T>* lds, const T* XR, const T* Xp, const T* tl) {
-  T k18[18];
+  T k18[24];
   lds_get<T, 18>(lds + c.pcol, PK_KIN, k18);
+  if (RBD_BANK_BIAS_SWEEP) lds_get<T, 6>(lds + c.pcol, PK_ZT, k18 + 18);
   bank_fk_commit<T, SIMPLE>(c.b.level == L0, c, k18, XR, Xp, tl);
 }
 
@@ -274,6 +307,7 @@ template <typename T, bool SIMPLE> RBD_DEV void bank_finish_joint(int l, BankReg
 // taker's exec mask; when some body of level l-1 has more children (ns > 1) every lane also leaves its hand-off in its exchange column and
 // the takers read their later children's columns.  MODE 1, across the banks: every child through the exchange columns.
 // The 27 values are formed, moved and consumed in three chunks (10 + 10 + 7) to bound the temporaries.
+// RBD_BANK_BIAS_SWEEP: the recursion runs with c = 0 (the bias accelerations are in pA already, terms()): pa = pA + U D^-1 u, no Ia cb.
 template <typename T, int MODE> RBD_DEV void bank_handoff(int l, int ns, const BankRegs<T>& gv, BankRegs<T>& tk, Pair2<T>* lds) {
   const bool takes = (tk.b.level == l - 1);
   const bool take0 = takes && tk.b.nchild >= 1;
@@ -290,8 +324,10 @@ template <typename T, int MODE> RBD_DEV void bank_handoff(int l, int ns, const B
     for (int e = 0; e < 10; ++e) {
       const int i = sym_row(c0 + e), j = sym_col(c0 + e);
       g[e] = gv.IA[c0 + e] - W[i] * gv.U[j];
-      Iac[i] += g[e] * gv.cb[j];
-      if (j > i) Iac[j] += g[e] * gv.cb[i];
+      if (!RBD_BANK_BIAS_SWEEP) {
+        Iac[i] += g[e] * gv.cb[j];
+        if (j > i) Iac[j] += g[e] * gv.cb[i];
+      }
       if (MODE == 0) h[e] = from_next_lane(g[e]);
     }
     if (xw) lds_put<T, 10>(mycol, PK_XCH + c0 / 2, g);
@@ -306,9 +342,9 @@ template <typename T, int MODE> RBD_DEV void bank_handoff(int l, int ns, const B
   {
     T g[7], h[7];
     g[0] = gv.IA[20] - W[5] * gv.U[5];
-    Iac[5] += g[0] * gv.cb[5];
+    if (!RBD_BANK_BIAS_SWEEP) Iac[5] += g[0] * gv.cb[5];
 #pragma unroll
-    for (int k = 0; k < 6; ++k) g[1 + k] = gv.pA[k] + Iac[k] + W[k] * gv.u;
+    for (int k = 0; k < 6; ++k) g[1 + k] = RBD_BANK_BIAS_SWEEP ? gv.pA[k] + W[k] * gv.u : gv.pA[k] + Iac[k] + W[k] * gv.u;
     if (MODE == 0) {
 #pragma unroll
       for (int e = 0; e < 7; ++e) h[e] = from_next_lane(g[e]);
@@ -343,11 +379,12 @@ template <typename T, int MODE> RBD_DEV void bank_handoff(int l, int ns, const B
 }
 
 // v̇ = D^-1 (u - U'a'), a = a' + S v̇ with a' = a_parent + cb — computed by every lane, committed in the lanes of `mine`
+// (RBD_BANK_BIAS_SWEEP: acc holds a - zt, and a' = a_parent's: the v̇ are the same)
 // (RBD_BANK_COMMIT_INPLACE: computed and assigned by the lanes of `mine` alone)
 template <typename T> RBD_DEV T bank_joint_accel_new(const BankRegs<T>& r, const T* a_parent, T* n) {
   T ap[6];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) ap[k] = a_parent[k] + r.cb[k];
+  for (int k = 0; k < 6; ++k) ap[k] = RBD_BANK_BIAS_SWEEP ? a_parent[k] : a_parent[k] + r.cb[k];
   const T x = r.Dinv * (r.u - dot6(r.U, ap));
 #pragma unroll
   for (int k = 0; k < 6; ++k) n[k] = ap[k] + r.S[k] * x;
@@ -405,6 +442,8 @@ RBD_DEV void aba_bank_body(const BankModel& M, long B, typename InPtr<T, !FUSED>
                            const T* __restrict__ fext, T* __restrict__ vdot, T* __restrict__ qdot, Layout Lq, Layout Lv, Layout Lf, const MkFuse& F,
                            Pair2<T>* const lds) {
   Pair2<T>* const col = lds + threadIdx.x;
+  constexpr int NPARK = RBD_BANK_BIAS_SWEEP ? 18 : (SIMPLE ? 20 : 24);  // what bank 0 parks of K while bank 1 is swept
+  constexpr int NFWD = RBD_BANK_BIAS_SWEEP ? 14 : 20;                   // what bank 1 parks for its top-down sweep: U, 1/D, u, S [, cb]
   RBD_MARK(0);
   BankRegs<T> r0, r1;
   // ---- per-body set-up (once per bank, every lane busy): joint transform and joint twist in the joint frame ----
@@ -513,7 +552,10 @@ RBD_DEV void aba_bank_body(const BankModel& M, long B, typename InPtr<T, !FUSED>
 #pragma unroll
     for (int i = 0; i < 3; ++i) c.p()[i] = Xp[i];
     xmotion(c.R(), c.p(), tl, c.Tw());
-    if (SIMPLE) {
+    if (RBD_BANK_BIAS_SWEEP) {  // (level 0: [T, T] = 0 for every joint type)
+#pragma unroll
+      for (int i = 0; i < 6; ++i) c.zt[i] = T(0);
+    } else if (SIMPLE) {
       c.K[18] = ta[3];  // the joint velocity, for the bias term
       c.K[19] = T(0);
     } else {
@@ -522,8 +564,17 @@ RBD_DEV void aba_bank_body(const BankModel& M, long B, typename InPtr<T, !FUSED>
     }
   };
   // ---- per-body terms in the root frame: motion subspace, bias acceleration, inertia, bias force ----
-  auto terms = [&](BankRegs<T>& c, bool accumulate) {  // accumulate: IA, pA already hold what the children handed up
+  auto terms = [&](BankRegs<T>& c, bool accumulate) {  // accumulate (bank 0): IA, pA already hold what the children handed up, zt is parked
     const bool floating = c.b.jtype == RBD_JOINT_QUAT_FLOATING;
+    T zt[6];
+    if (RBD_BANK_BIAS_SWEEP) {
+      if (accumulate) {
+        lds_get<T, 6>(col, PK_ZT, zt);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) zt[i] = c.zt[i];
+      }
+    }
     if (SIMPLE) {  // S = X (a; 0) = (R a; p x R a); bias term [T, vJ] = [T, S] v
       const T ax[3] = {c.rb[RB_AXIS], c.rb[RB_AXIS + 1], c.rb[RB_AXIS + 2]};
       matvec3(c.R(), ax, c.S);
@@ -537,7 +588,9 @@ RBD_DEV void aba_bank_body(const BankModel& M, long B, typename InPtr<T, !FUSED>
 #pragma unroll
       for (int i = 0; i < 6; ++i) c.S[i] = T(0);
     }
-    if (SIMPLE) {
+    if (RBD_BANK_BIAS_SWEEP) {
+      // (the bias acceleration was summed by the kinematics sweep: zt)
+    } else if (SIMPLE) {
       se3_comm(c.Tw(), c.S, c.cb);
 #pragma unroll
       for (int i = 0; i < 6; ++i) c.cb[i] *= c.K[18];
@@ -554,6 +607,12 @@ RBD_DEV void aba_bank_body(const BankModel& M, long B, typename InPtr<T, !FUSED>
     T Io[21], po[6];
     sym6_from_inertia(I, Io);
     momentum_cross(I, c.Tw(), po);
+    if (RBD_BANK_BIAS_SWEEP) {  // the recursion runs on a' = a - zt: the body's own I zt joins its bias force here, where every lane is busy
+      T Iz[6];
+      mul_inertia(I, zt, Iz);
+#pragma unroll
+      for (int i = 0; i < 6; ++i) po[i] += Iz[i];
+    }
     bank_load_wrench(c.b, fext, Lf, fe);
     // (lanes without a body are never read by anyone: takers add only what their own children give, under their exec mask)
 #pragma unroll
@@ -597,7 +656,8 @@ RBD_BANK_UNROLL
     setup(r1, qj1, vj1, XR, Xp, tl, ta);
     RBD_MARK(3);
     // bank 0 rests until bank 1 has been swept bottom-up; its parked (R, p, Tw) are what bank 1's first level reads
-    lds_put<T, (SIMPLE ? 20 : 24)>(col, PK_KIN, r0.K);
+    lds_put<T, NPARK>(col, PK_KIN, r0.K);
+    if (RBD_BANK_BIAS_SWEEP) lds_put<T, 6>(col, PK_ZT, r0.zt);
     wave_lds_sync();
     bank_fk_cross<T, SIMPLE>(RBD_BK_L0, r1, lds, XR, Xp, SIMPLE ? ta : tl);
 RBD_BANK_UNROLL
@@ -625,14 +685,18 @@ RBD_BANK_UNROLL
   for (int i = 0; i < 6; ++i) r0.pA[i] = T(0);
   bank_handoff<T, 1>(RBD_BK_L0, RBD_BK_NS(RBD_BK_L0), r1, r0, lds);
   {
-    lds_get<T, (SIMPLE ? 20 : 24)>(col, PK_KIN, r0.K);
+    lds_get<T, NPARK>(col, PK_KIN, r0.K);
     // (bank 0's Tw, vJ pairs are free again: bank 1's set takes them; R, p stay for the 6-dof joints)
-    T f20[20];
+    T fwd[NFWD];
 #pragma unroll
-    for (int i = 0; i < 6; ++i) { f20[i] = r1.U[i]; f20[8 + i] = r1.S[i]; f20[14 + i] = r1.cb[i]; }
-    f20[6] = r1.Dinv;
-    f20[7] = r1.u;
-    lds_put<T, 20>(col, PK_FWD, f20);
+    for (int i = 0; i < 6; ++i) {
+      fwd[i] = r1.U[i];
+      fwd[8 + i] = r1.S[i];
+      if (!RBD_BANK_BIAS_SWEEP) fwd[NFWD - 6 + i] = r1.cb[i];
+    }
+    fwd[6] = r1.Dinv;
+    fwd[7] = r1.u;
+    lds_put<T, NFWD>(col, PK_FWD, fwd);  // (RBD_BANK_BIAS_SWEEP: 14 values, pairs 6..12 — bank 0's zt stays in pairs 13..15 until terms(r0) has read it)
   }
   RBD_MARK(7);
   terms(r0, true);
@@ -684,17 +748,17 @@ RBD_BANK_UNROLL
   if (vdot) bank_store_v(r0.b, vdot, Lv, r0.vd);
   if (FUSED) bank_store_v(r0.b, (T*)F.W.vd[F.stage], Lv, r0.vd);
   {
-    T f20[20];
-    lds_get<T, 20>(col, PK_FWD, f20);
+    T fwd[NFWD];
+    lds_get<T, NFWD>(col, PK_FWD, fwd);
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
-      r1.U[i] = f20[i];
-      r1.S[i] = f20[8 + i];
-      r1.cb[i] = f20[14 + i];
+      r1.U[i] = fwd[i];
+      r1.S[i] = fwd[8 + i];
+      if (!RBD_BANK_BIAS_SWEEP) r1.cb[i] = fwd[NFWD - 6 + i];
       if (!RBD_BANK_LEAN_INIT) { r1.acc[i] = T(0); r1.vd[i] = T(0); }
     }
-    r1.Dinv = f20[6];
-    r1.u = f20[7];
+    r1.Dinv = fwd[6];
+    r1.u = fwd[7];
   }
   {  // across the banks: every bank-0 lane leaves its acceleration in its exchange column, the bodies of level L0 read their parent's
     lds_put<T, 6>(col, PK_XCH, r0.acc);

@@ -3,6 +3,9 @@ library generates for Atlas (floating base) is cross-compiled for gfx950 against
 and the instructions of each kernel are counted per class, with its registers, scratch and LDS.  One wavefront per SIMD runs this code, so every instruction that
 is not arithmetic is issue time (DESIGN.md §3.2's table prices the classes).
 
+After the mix, the waits (a report): for every s_waitcnt that waits for a load its distance, in instructions, from the last load it covers, and how many of
+them follow their load closely (kernel_waits).
+
 usage: python scripts/bank_isa_mix.py [--parent REV] [--variant NAME:-DX=0[,-DY=0]] ... [--kernels aba_bank_spec,...] > profiles/bank_diet_isa.txt
   --parent REV    the revision whose headers make the first column (default HEAD; "none": no parent column)
   --variant ...   further columns: the working tree's headers with the given definitions (a part switched off: -DRBD_BANK_COMMIT_INPLACE=0)
@@ -60,6 +63,55 @@ def kernel_mix(asm_text, kernel):
             if parts[0].startswith(d):
                 mix[d] += 1
     return mix
+
+
+def kernel_body(asm_text, kernel):
+    """(mnemonic, operands) of the instructions between `kernel:` and its .Lfunc_end, in program order"""
+    m = re.search(r"^%s:[^\n]*$(.*?)^\.Lfunc_end\d+:" % re.escape(kernel), asm_text, re.M | re.S)
+    if m is None:
+        raise KeyError(kernel)
+    out = []
+    for line in m.group(1).splitlines():
+        line = line.split(";")[0].strip()
+        if not line or line.endswith(":") or line.startswith("."):
+            continue
+        parts = line.split(None, 1)
+        if classify(parts[0], parts[1] if len(parts) > 1 else "") is not None:
+            out.append((parts[0], parts[1] if len(parts) > 1 else ""))
+    return out
+
+
+NEAR = {"global": 40, "LDS": 12}  # a wait this close behind the load it waits for leaves most of the round trip exposed (one wavefront per SIMD: nobody else issues)
+
+
+def kernel_waits(asm_text, kernel):
+    """For every s_waitcnt of `kernel` that waits for a load: (index of the wait, "global" | "LDS" | "scalar", distance in instructions from the LAST load it
+    covers).  The counters are followed along the program text as if it were straight-line code (branches are not followed: the looped kernels would need that,
+    the unrolled program's branches are short exec-mask skips): vmcnt counts global loads and stores, lgkmcnt LDS operations and scalar loads, both in issue
+    order; `s_waitcnt vmcnt(N)` covers every operation but the N issued last.  A wait that covers no load that an earlier wait has not covered is left out."""
+    queues = {"vm": [], "lgkm": []}  # outstanding operations: (index, kind)
+    waits = []
+    for i, (mn, ops) in enumerate(kernel_body(asm_text, kernel)):
+        if mn.startswith(("global_load", "flat_load", "buffer_load")):
+            queues["vm"].append((i, "global"))
+        elif mn.startswith(("global_store", "flat_store", "buffer_store", "global_atomic")):
+            queues["vm"].append((i, None))
+        elif mn.startswith("ds_"):
+            queues["lgkm"].append((i, "LDS" if mn.startswith(("ds_read", "ds_load", "ds_bpermute", "ds_permute", "ds_swizzle")) else None))
+        elif mn.startswith(("s_load", "s_buffer_load")):
+            queues["lgkm"].append((i, "scalar"))
+        elif mn == "s_waitcnt":
+            for q, name in (("vm", "vmcnt"), ("lgkm", "lgkmcnt")):
+                c = re.search(name + r"\((\d+)\)", ops)
+                if c is None:
+                    continue
+                n = int(c.group(1))
+                covered = queues[q][:len(queues[q]) - n] if n else queues[q]
+                queues[q] = queues[q][len(queues[q]) - n:] if n else []
+                loads = [e for e in covered if e[1] is not None]
+                if loads:
+                    waits.append((i, loads[-1][1], i - loads[-1][0]))
+    return waits
 
 
 def kernel_resources(asm_text, kernel):
@@ -132,8 +184,15 @@ def main():
                 print("%-16s" % "all" + "".join("%22d" % sum(m[c] for c in CLASSES) for m in mixes))
                 for row in DETAIL:
                     print("%-16s" % ("  " + row + "*") + "".join("%22d" % m[row] for m in mixes))
+                waits = [kernel_waits(s, kernel) for s in asms]
+                for kind in ("global", "LDS"):
+                    print("%-16s" % ("waits: " + kind) + "".join("%22d" % sum(1 for w in ws if w[1] == kind) for ws in waits))
+                    print("%-16s" % ("  within %d" % NEAR[kind]) + "".join("%22d" % sum(1 for w in ws if w[1] == kind and w[2] <= NEAR[kind]) for ws in waits))
                 for row, key in (("VGPRs", "vgprs"), ("AGPRs", "agprs"), ("scratch bytes", "scratch"), ("spilled VGPRs", "vgpr_spills"), ("LDS bytes", "lds")):
                     print("%-16s" % row + "".join("%22d" % r[key] for r in res))
+                # every wait: instruction index of the s_waitcnt : distance from the last load it covers (g global, l LDS, s scalar)
+                for c, ws in zip(columns, waits):
+                    print("waits of %s: " % c[0] + " ".join("%d:%s%d" % (w[0], w[1][0].lower(), w[2]) for w in ws))
                 print()
     finally:
         if tmp:
