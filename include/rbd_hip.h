@@ -190,8 +190,8 @@ typedef struct rbd_opts {
  * with a body of more than 8 children (since header 600; refused before), are accepted too and run on one-thread-per-state kernels with an HBM scratch (no speed
  * claim) — rbd_dynamics with its loop branch, rbd_inverse_dynamics[_bodies], rbd_dynamics_bias[_bodies], rbd_mass_matrix[_solve], rbd_mass_matrix_solve_packed,
  * rbd_dynamics_result, rbd_contact_dynamics, rbd_dynamics_contact, rbd_simulate / rbd_simulate_controlled (the PD law included) / rbd_mk_stage (since 500), since 600
- * the kinematics by-products rbd_kinematics, rbd_geometric_jacobian, rbd_momentum, and since 700 the derivative entry points.  rbd_simulate_contact and
- * rbd_cholesky_solve return RBD_ERR_UNSUPPORTED for such a model.  The reference has no size limit (src/mechanism_algorithms.jl:28-50, :80-99, :313-327). */
+ * the kinematics by-products rbd_kinematics, rbd_geometric_jacobian, rbd_momentum, since 700 the derivative entry points, and rbd_cholesky_solve (which
+ * uses nv alone).  rbd_simulate_contact returns RBD_ERR_UNSUPPORTED for such a model.  The reference has no size limit (src/mechanism_algorithms.jl:28-50, :80-99, :313-327). */
 int rbd_model_create(const rbd_flat_model_t* desc, rbd_model_t** out); /* deep-copies desc */
 int rbd_model_destroy(rbd_model_t* model);
 /* Introspection of the chain schedule under the track / walk plans: tracks per state, steps per pass, (lds_fields: 0, kept for ABI
@@ -284,8 +284,12 @@ int rbd_mass_matrix_solve(rbd_ws_t* ws, int32_t B, const void* q, const void* rh
 int rbd_mass_matrix_solve_packed(rbd_ws_t* ws, int32_t B, const void* q, const void* rhs, void* x, void* M_packed_out, const rbd_opts_t* opts);
 
 /* The dense step of dynamics_solve! on its own: L = potrf!('L', M) and x = potrs!(L, rhs) for B caller-provided nv×nv SPD
- * matrices (lower triangles read; device pointers).  L_out (nullable) receives the factor — DynamicsResult.L
- * (src/dynamics_result.jl:32).  fp32 with nv <= 40 runs on the matrix cores (chol_mfma_kernel).                        */
+ * matrices (lower triangles read, the strict upper ones never; device pointers).  L_out (nullable) receives the lower
+ * triangle of the factor in the layout of M — DynamicsResult.L (src/dynamics_result.jl:32); its strict upper triangle
+ * is left untouched.  Only nv of the model is used: every model and every nv is taken.  The kernel by nv: <= 40 the MFMA
+ * tile kernels (chol_mfma_kernel fp32, chol_mfma64_kernel fp64), 41..48 chol_reg_kernel, 49..64 chol_solve_kernel (LDS),
+ * beyond 64 big_chol_solve_kernel (one thread per state).  A matrix that is not positive definite: rbd_sync returns
+ * status 8 once; the other states of the batch are not disturbed.                                                     */
 int rbd_cholesky_solve(rbd_ws_t* ws, int32_t B, const void* M, const void* rhs, void* x, void* L_out, const rbd_opts_t* opts);
 
 /* after rbd_dynamics(..., RBD_ALGO_CRBA_CHOLESKY): copy the DynamicsResult side

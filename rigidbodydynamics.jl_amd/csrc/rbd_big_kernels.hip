@@ -201,6 +201,17 @@ __global__ __launch_bounds__(64) void big_chol_solve_kernel(int nv, long B, cons
   }
 }
 
+// The factor of big_chol_solve_kernel (batch-innermost scratch Lg) into a caller's L_out: the lower triangle only, in the layout of the caller's M
+// (rbd_cholesky_solve beyond 64 coordinates).  Thread = (entry, state) with the state innermost: coalesced reads, the stores as the caller's layout has them.
+template <typename T>
+__global__ __launch_bounds__(256) void big_chol_export_kernel(int nv, long B, const T* __restrict__ Lg, T* __restrict__ Lout, Layout Lm) {
+  const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long)nv * nv * B) return;
+  const long e = t / B, st = t - e * B;
+  const int col = (int)(e / nv), row = (int)(e - (long)col * nv);
+  if (row >= col) Lout[e * Lm.sk + st * Lm.sb] = Lg[t];
+}
+
 // The kinematics by-products on trees of any size (round 6; rbd_kinematics / rbd_geometric_jacobian / rbd_momentum of trees the lane-per-body kin_kernel does
 // not take): momentum_matrix! (src/mechanism_algorithms.jl:313-327), center_of_mass (:28-50), kinetic_energy / gravitational_potential_energy
 // (src/mechanism_state.jl:886-903), geometric_jacobian! of path(base -> target) (:80-99), momentum / momentum_rate_bias (src/mechanism_state.jl:975-987).
@@ -446,11 +457,18 @@ hipError_t launch_big_chol_solve(int nv, long B, const void* Mg, void* Lg, const
   hipLaunchKernelGGL(big_chol_solve_kernel<T>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, nv, B, (const T*)Mg, (T*)Lg, (const T*)rhs, (const T*)c, (T*)x, Lm, Lv, notpd);
   return hipGetLastError();
 }
+template <typename T>
+hipError_t launch_big_chol_export(int nv, long B, const void* Lg, void* Lout, Layout Lm, hipStream_t s) {
+  const long total = (long)nv * nv * B;
+  hipLaunchKernelGGL(big_chol_export_kernel<T>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, nv, B, (const T*)Lg, (T*)Lout, Lm);
+  return hipGetLastError();
+}
 #define RBD_BIG_INST(T)                                                                                                                                     \
   template hipError_t launch_big_rnea<T>(const BigModel&, long, const void*, const void*, const void*, const void*, void*, void*, void*, void*, void*, Layout, \
                                          Layout, Layout, hipStream_t);                                                                                       \
   template hipError_t launch_big_crba<T>(const BigModel&, long, const void*, void*, void*, Layout, Layout, hipStream_t);                                    \
-  template hipError_t launch_big_chol_solve<T>(int, long, const void*, void*, const void*, const void*, void*, Layout, Layout, int*, hipStream_t);
+  template hipError_t launch_big_chol_solve<T>(int, long, const void*, void*, const void*, const void*, void*, Layout, Layout, int*, hipStream_t);     \
+  template hipError_t launch_big_chol_export<T>(int, long, const void*, void*, Layout, hipStream_t);
 RBD_BIG_INST(double)
 RBD_BIG_INST(float)
 

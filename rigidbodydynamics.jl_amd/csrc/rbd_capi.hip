@@ -1644,6 +1644,20 @@ static int check_solve(rbd_ws* w, long B, const void* dq, const void* dtau, cons
   }, same);
 }
 
+int dense_solve(rbd_ws* w, long B, const void* M, const void* rhs, const void* c, void* x, void* L_out, Layout Lm, Layout Lv, DevBuf& factor) {
+  const int nv = w->model->nv;
+  int* const notpd = (int*)w->d_notpd.p;
+  if (!chol_beyond_lanes(nv)) {
+    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_chol_solve<decltype(t)>(nv, B, M, rhs, c, x, L_out, Lm, Lv, notpd, w->stream); }));
+    return RBD_OK;
+  }
+  const bool wants_copy = L_out && L_out != factor.p;  // (asked before the buffer may move: a caller that passed factor.p reads factor.p afterwards)
+  if (int st = ensure(factor, esize(w) * (size_t)nv * nv * B)) return st;
+  HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_big_chol_solve<decltype(t)>(nv, B, M, factor.p, rhs, c, x, Lm, Lv, notpd, w->stream); }));
+  if (wants_copy) HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_big_chol_export<decltype(t)>(nv, B, factor.p, L_out, Lm, w->stream); }));
+  return RBD_OK;
+}
+
 // mass_matrix! into dM (caller's layout) followed by the Cholesky solve of M x = tau - c (either may be null).  Large batches
 // build M with one lane per state; for an AOS caller that kernel writes a batch-innermost staging copy which the tile Cholesky
 // reads (coalesced) and re-emits as the caller's M.
@@ -1652,11 +1666,9 @@ static int run_crba_chol(rbd_ws* w, int32_t B, int layout, const void* dq, void*
   const rbd_model* m = w->model;
   const size_t es = esize(w);
   int st;
-  if (m->big) {  // any-size fallback: M into dM (never null here), then one thread per state factors a COPY (the reference's result.L, :763-764) and solves
+  if (m->big) {  // any-size fallback: M into dM (never null here), then the dense solve factors a COPY (the reference's result.L, :763-764)
     if ((st = run_crba(w, B, layout, dq, dM, Lq, Lm))) return st;
-    if ((st = ensure(w->d_big_L, es * (size_t)m->nv * m->nv * B))) return st;
-    HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_big_chol_solve<decltype(t)>(m->nv, B, dM, w->d_big_L.p, dtau, dc, dx, Lm, Lv, (int*)w->d_notpd.p, w->stream); }));
-    return RBD_OK;
+    return dense_solve(w, B, dM, dtau, dc, dx, nullptr, Lm, Lv, w->d_big_L);
   }
   const bool state = B >= w->mass_solve_min_batch;  // (below state_min_batch: only with both kernels compiled for the mechanism — spec_route)
   if (state && layout == RBD_LAYOUT_AOS && chol_copies_m((int)es, m->nv)) {
@@ -1696,7 +1708,7 @@ lanes:
     dM = w->d_M.p;
   }
   if ((st = run_crba(w, B, layout, dq, dM, Lq, Lm))) return st;
-  HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_chol_solve<decltype(t)>(m->nv, B, dM, dtau, dc, dx, nullptr, Lm, Lv, (int*)w->d_notpd.p, w->stream); }));
+  if ((st = dense_solve(w, B, dM, dtau, dc, dx, nullptr, Lm, Lv, w->d_big_L))) return st;
   w->last_kernel = strstr(w->last_kernel, "crba_spec") ? "crba_spec (compiled for the mechanism at run time) + chol kernel"
                    : strstr(w->last_kernel, "crba_state") ? "crba_state_kernel + chol kernel" : "crba_kernel + chol kernel";
   return RBD_OK;
@@ -2273,15 +2285,14 @@ int rbd_simulate_contact_controlled(rbd_ws_t* w, int32_t B, void* q, void* v, vo
 
 int rbd_cholesky_solve(rbd_ws_t* w, int32_t B, const void* M, const void* rhs, void* x, void* L_out, const rbd_opts_t* opts) {
   Opts o;
-  if (int st = begin_call(w, B, opts, kUpTo64Bodies, &o)) return st;
+  if (int st = begin_call(w, B, opts, kAnySize, &o)) return st;  // (only nv is used: the solve has no size limit)
   if (!M || !rhs || !x || o.memory != RBD_MEM_DEVICE) return RBD_ERR_INVALID_ARGUMENT;
   if (B == 0) return RBD_OK;
   HIP_TRY(hipSetDevice(w->device));
   const rbd_model* m = w->model;
   const Layout Lv = layout_of(o.layout, m->nv, B), Lm = layout_of(o.layout, (long)m->nv * m->nv, B);
   Timed t(w);
-  HIP_TRY(by_dtype(w->dtype, [&](auto t) { return launch_chol_solve<decltype(t)>(m->nv, B, M, rhs, nullptr, x, L_out, Lm, Lv, (int*)w->d_notpd.p, w->stream); }));
-  return RBD_OK;
+  return dense_solve(w, B, M, rhs, nullptr, x, L_out, Lm, Lv, w->d_big_L);
 }
 
 

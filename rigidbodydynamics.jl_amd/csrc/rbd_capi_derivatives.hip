@@ -91,7 +91,7 @@ int tan_ensure(rbd_ws* w, int ntan) {
     if ((st = ensure(w->d_tan_scratch, per * threads))) return st;
     w->tan_threads = threads;
     if ((st = ensure(w->d_tan_rhs, es * std::max<size_t>(1, (size_t)m->nv * ntan * B)))) return st;
-    if (m->nv > 64 && (st = ensure(w->d_tan_x, es * (size_t)m->nv * ntan * B))) return st;
+    if (chol_beyond_lanes(m->nv) && (st = ensure(w->d_tan_x, es * (size_t)m->nv * ntan * B))) return st;
     w->tan_ntan = ntan;
   }
   return RBD_OK;
@@ -129,10 +129,8 @@ template <typename T> int tan_dynamics_value(rbd_ws* w, int32_t B, int layout, c
     HIP_TRY(launch_rnea<T>(w->dm, B, q, v, nullptr, fext, w->d_tan_c.p, nullptr, nullptr, Lq, Lv, Lf, w->stream));
     HIP_TRY(launch_crba<T>(w->dm, B, q, w->d_tan_M.p, Lq, Lm, 1, w->stream));
   }
-  // (the wavefront Cholesky kernels hold one row per lane: beyond 64 coordinates the one-thread-per-state factorisation of the any-size route)
-  if (m->nv > 64) HIP_TRY(launch_big_chol_solve<T>(m->nv, B, w->d_tan_M.p, w->d_tan_L.p, tau, w->d_tan_c.p, vd, Lm, Lv, (int*)w->d_notpd.p, w->stream));
-  else HIP_TRY(launch_chol_solve<T>(m->nv, B, w->d_tan_M.p, tau, w->d_tan_c.p, vd, w->d_tan_L.p, Lm, Lv, (int*)w->d_notpd.p, w->stream));
-  return RBD_OK;
+  // the factor stays in d_tan_L (batch-innermost, as M) for the solves that follow
+  return dense_solve(w, B, w->d_tan_M.p, tau, w->d_tan_c.p, vd, w->d_tan_L.p, Lm, Lv, w->d_tan_L);
 }
 
 template <typename T>
@@ -236,7 +234,7 @@ int adj_ensure(rbd_ws* w) {
   if ((st = adj_scratch_ensure(w))) return st;
   if ((st = ensure(w->d_adj_rhs, es * std::max<size_t>(1, nv * B))) || (st = ensure(w->d_adj_lam, es * std::max<size_t>(1, nv * B))))
     return st;
-  if (m->nv > 64 && (st = ensure(w->d_adj_x, es * nv * B))) return st;
+  if (chol_beyond_lanes(m->nv) && (st = ensure(w->d_adj_x, es * nv * B))) return st;
   w->adj_ready = true;
   return RBD_OK;
 }

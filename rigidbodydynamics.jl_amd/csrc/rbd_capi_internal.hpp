@@ -253,6 +253,11 @@ struct Timed {
 
 // at least `need` bytes: grows only — the old buffer freed before the larger one is allocated, the buffer left empty when that fails
 int ensure(DevBuf& b, size_t need);
+// The dense step of dynamics_solve! for a system of any size, in the workspace's scalar type: L = chol(M) (lower triangle of M read, layout Lm),
+// x = M⁻¹(rhs − c) (rhs, c nullable; layout Lv), not positive definite ⇒ w->d_notpd.  Up to 64 coordinates: launch_chol_solve, L_out (nullable) in the layout
+// of M.  Beyond (chol_beyond_lanes): launch_big_chol_solve with the factor in `factor` (batch-innermost; the workspace's d_big_L, or the derivative layer's
+// d_tan_L), grown here to B states; an L_out that is not that buffer then gets the lower triangle copied, in the layout of M.
+int dense_solve(rbd_ws* w, long B, const void* M, const void* rhs, const void* c, void* x, void* L_out, Layout Lm, Layout Lv, DevBuf& factor);
 // a table copied to a fresh buffer of its size (16 bytes for an empty one); upload_real: real numbers, in the scalar type of `dtype`
 int upload(DevBuf& dst, const void* src, size_t bytes);
 int upload_real(DevBuf& dst, const std::vector<double>& src, int dtype);

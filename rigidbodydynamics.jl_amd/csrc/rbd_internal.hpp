@@ -19,6 +19,9 @@ namespace rbd {
 template <typename T>
 hipError_t launch_chol_solve(int nv, long B, const void* M, const void* tau, const void* c, void* x, void* Lout, Layout Lm, Layout Lv,
                              int* notpd, hipStream_t s, void* Mcopy = nullptr, Layout Lc = Layout{0, 0});
+// THE size decision of the dense solve: launch_chol_solve's kernels keep one matrix row per lane of a wavefront, so it refuses (hipErrorInvalidValue) what
+// this says yes to, and the C API's dense_solve (rbd_capi_internal.hpp) sends those systems to launch_big_chol_solve.  The number of bodies plays no part.
+inline bool chol_beyond_lanes(int nv) { return nv > 64; }
 bool chol_copies_m(int element_size, int nv);  // the kernel launch_chol_solve picks can also write M in a second layout (Mcopy)
 // the lower triangle of B nv x nv matrices (column-major per state, layout Lm) as LAPACK's packed 'L' storage (layout Lp over nv (nv + 1) / 2 values per state)
 template <typename T> hipError_t launch_pack_lower(int nv, long B, const void* M, void* P, Layout Lm, Layout Lp, hipStream_t s);
@@ -129,6 +132,8 @@ hipError_t launch_big_pd_control(const BigModel& M, long B, const void* q, const
                                  void* tau_out, Layout Lq, Layout Lv, hipStream_t s);
 template <typename T>
 hipError_t launch_big_chol_solve(int nv, long B, const void* Mg, void* Lg, const void* rhs, const void* c, void* x, Layout Lm, Layout Lv, int* notpd, hipStream_t s);
+// the lower triangle of that factor (Lg: batch-innermost) into a buffer of the layout Lm
+template <typename T> hipError_t launch_big_chol_export(int nv, long B, const void* Lg, void* Lout, Layout Lm, hipStream_t s);
 // rbd_tangent_kernels.hip, rbd_point_kernels.hip: the derivative kernels (arguments: rbd_tangent.hpp, rbd_tangent_mk.hpp, rbd_adjoint.hpp, rbd_adjoint_mk.hpp,
 // rbd_point.hpp — their callers include those)
 template <typename T> struct ColOut; template <typename T> struct TanArgs; template <typename T> struct MkTanArgs; template <typename T> struct AdjArgs;

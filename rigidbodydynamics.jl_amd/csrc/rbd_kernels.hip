@@ -951,7 +951,7 @@ __global__ __launch_bounds__(256) void chol_solve_kernel(int nv, int stride, lon
   (void)bc;
 }
 
-// Register-resident variant used for nv <= 64: lane i keeps row i of the matrix in VGPRs (statically indexed, loops fully
+// Register-resident variant, used for nv 41..48 (NVP = 48, its only instantiation: launch_chol_solve): lane i keeps row i of the matrix in VGPRs (statically indexed, loops fully
 // unrolled over the padded size NVP = nv rounded up to a multiple of 8; the padding is an identity block so no guards are
 // needed).  Right-looking: column j is scaled by 1/sqrt(pivot), then every lane updates its own row with the column entries
 // L[k][j] broadcast by v_readlane (uniform lane index) — no LDS traffic and no waits inside the factorization.  The factor
@@ -1411,18 +1411,17 @@ template <> struct MfmaChol<float> {
 template <typename T>
 hipError_t launch_chol_solve(int nv, long B, const void* M, const void* tau, const void* c, void* x, void* Lout, Layout Lm, Layout Lv,
                              int* notpd, hipStream_t s, void* Mcopy, Layout Lc) {
-  if (MfmaChol<T>::launch(nv, B, M, tau, c, x, Lout, Lm, Lv, notpd, s, Mcopy, Lc)) return hipGetLastError();  // fp32, nv <= 40: matrix cores
+  // Every kernel below holds one matrix row per lane (or per lane of a quad): 64 rows at most.  Larger systems are the caller's to route
+  // (dense_solve, rbd_capi.hip: the one-thread-per-state kernel of rbd_big_kernels.hip); nothing is launched that cannot do the job.
+  if (chol_beyond_lanes(nv)) return hipErrorInvalidValue;
+  if (MfmaChol<T>::launch(nv, B, M, tau, c, x, Lout, Lm, Lv, notpd, s, Mcopy, Lc)) return hipGetLastError();  // nv <= 40: matrix cores (fp64: without Mcopy)
   if (Mcopy) return hipErrorInvalidValue;  // only the tile kernel re-emits M (chol_copies_m())
-  const dim3 grid4((unsigned)((B + 3) / 4));
-#define RBD_CHOL_REG(NVP)                                                                                                      \
-  if (nv <= NVP) {                                                                                                            \
-    hipLaunchKernelGGL((chol_reg_kernel<T, NVP>), grid4, dim3(256), 0, s, nv, B, (const T*)M, (const T*)tau, (const T*)c, (T*)x, \
-                       (T*)Lout, Lm, Lv, notpd);                                                                              \
-    return hipGetLastError();                                                                                                 \
+  if (nv <= 48) {  // nv 41..48 (the tile kernels take everything smaller in both types: the register kernel has this one size)
+    hipLaunchKernelGGL((chol_reg_kernel<T, 48>), dim3((unsigned)((B + 3) / 4)), dim3(256), 0, s, nv, B, (const T*)M, (const T*)tau, (const T*)c, (T*)x,
+                       (T*)Lout, Lm, Lv, notpd);
+    return hipGetLastError();
   }
-  RBD_CHOL_REG(8) RBD_CHOL_REG(16) RBD_CHOL_REG(24) RBD_CHOL_REG(32) RBD_CHOL_REG(40) RBD_CHOL_REG(48)
-#undef RBD_CHOL_REG
-  // larger systems: the LDS-resident kernel
+  // nv 49..64: the LDS-resident kernel
   int stride = ((nv + 3) / 4) * 4;  // 4*odd words: 16-byte row alignment, rows spread over the banks
   if (((stride / 4) & 1) == 0) stride += 4;
   int wpb = 4;

@@ -15,7 +15,7 @@ import oracle  # noqa: E402
 import rbd_amd as rbd  # noqa: E402
 from conftest import LIMBS, build_models, rand_inputs  # noqa: E402
 from derivative_parity import cond_M, fp64_chain_rule, fp64_chain_rule_jvp, jvp_directions, solve_loss  # noqa: E402
-from test_derivatives_gpu import FD_MODELS, model  # noqa: E402
+from test_derivatives_gpu import FD_MODELS, NV_OVER_64, model  # noqa: E402
 
 B, SEED = 8, 11  # the states of tests/test_derivatives_gpu.py::test_jacobians_against_the_quad_oracle (its first 8) and of test_jvp_against_the_quad_oracle
 
@@ -37,7 +37,7 @@ def main():
     print("# against the quad derivative of dynamics.  Columns: dvdot/dq, dvdot/dv, dvdot/dtau = M^-1 (a state's matrix as one vector),")
     print("# the directional derivatives along (dq, dv, dtau, dfext) on the states of the JVP test (4096 for atlas_floating, else 16), the model's constant = the largest of the four, max cond2(M).")
     worst = 0.0
-    for name in FD_MODELS + ["tree20"] + LIMBS:
+    for name in FD_MODELS + ["tree20"] + LIMBS + NV_OVER_64:
         flat = model(rbd, models, name)
         q, v, tau, fext = rand_inputs(rbd, flat, B, SEED, fext=True)
         ref = oracle.jacobians(flat, oracle.WHAT_DYNAMICS, q, v, tau, fext)

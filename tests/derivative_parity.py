@@ -15,7 +15,7 @@ MARGIN = 8.0  # the C of test_gpu_parity.assert_fp32_forward
 FP64_LOSS = {"atlas_floating": 2.755e-02, "atlas_fixed": 2.619e-02, "valkyrie_floating": 4.171e-02, "double_pendulum": 2.360e+00,
              "randmech1": 1.539e-01, "randmech2": 2.620e-01, "randmech3": 2.774e-01, "inner_floating": 1.333e+00, "mixed20": 7.901e-01,
              "chain70": 1.118e-02, "tree20": 2.929e-02, "limbs_humanoid": 3.405e-02, "limbs_only_children": 2.258e+00, "limbs_quadruped": 5.183e-01,
-             "limbs_three": 2.773e-01}
+             "limbs_three": 2.773e-01, "nv66_spherical": 1.784e-01, "nv65_mixed": 2.919e-02}
 
 
 def C_solve(name):

@@ -12,7 +12,19 @@ pytestmark = pytest.mark.gpu
 
 FD_MODELS = ["atlas_floating", "atlas_fixed", "valkyrie_floating", "double_pendulum", "randmech1", "randmech2", "randmech3", "inner_floating", "mixed20", "chain70"]
 
+# trees of at most 64 bodies with more than 64 velocity coordinates: the lane-per-body kernels take them, the dense solve does not hold a row per lane
+NV_OVER_64 = ["nv66_spherical", "nv65_mixed"]
+NV_OVER_64_TYPES = {"nv66_spherical": ["QuaternionSpherical"] * 22,
+                    "nv65_mixed": ["QuaternionFloating"] + ["QuaternionSpherical"] * 12 + ["Planar"] * 5 + ["Revolute"] * 6 + ["Prismatic"] * 2}
+
+
+def at_most_3_children(m, r):
+    return m.bodies[max(1, len(m.bodies) - 1 - int(r.integers(0, 3)))]
+
+
 def model(rbd, models, name):
+    if name in NV_OVER_64_TYPES:
+        return rbd.flatten(rbd.rand_tree_mechanism(np.random.default_rng(5), NV_OVER_64_TYPES[name], at_most_3_children))
     if name == "chain70":  # a tree of more than 64 bodies: the any-size tables
         return rbd.flatten(rbd.rand_tree_mechanism(np.random.default_rng(70), ["QuaternionFloating"] + ["Revolute", "Prismatic", "SinCosRevolute", "Revolute"] * 17 + ["Revolute"]))
     if name == "tree20":  # test/test_mechanism_algorithms.jl:618: rand_tree_mechanism with 10 revolute and 10 prismatic joints
@@ -82,7 +94,7 @@ def jacobians(rbd, s, flat, vd, tau, fext=None):
 
 
 @pytest.mark.parametrize("layout", ["aos", "soa"])
-@pytest.mark.parametrize("name", FD_MODELS + LIMBS)
+@pytest.mark.parametrize("name", FD_MODELS + LIMBS + NV_OVER_64)
 def test_jacobians_against_the_quad_oracle(rbd, oracle, models, name, layout):
     """The full Jacobians of both entry points, external wrenches present, against unit-direction derivatives of the quad-precision oracle in raw coordinates:
     ∂τ/∂(q, v, v̇) at 1e-10, ∂v̇/∂(q, v, τ) state by state at the model's C · cond₂(M_b) · eps64.  8 states: a full Jacobian costs ~2 (nq + 2 nv) quad evaluations."""

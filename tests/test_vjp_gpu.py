@@ -10,7 +10,7 @@ import torch
 
 from conftest import rand_inputs
 from derivative_parity import assert_no_solve, assert_solve_forward, cond_M
-from test_derivatives_gpu import close, dev, host, jacobians, make_state, model
+from test_derivatives_gpu import NV_OVER_64, close, dev, host, jacobians, make_state, model
 
 pytestmark = pytest.mark.gpu
 
@@ -78,7 +78,7 @@ def quad_transposed(oracle, flat, q, v, vd, tau, fext, lam, w, wrench=False):
 
 
 @pytest.mark.parametrize("layout", ["aos", "soa"])
-@pytest.mark.parametrize("name", MODELS)
+@pytest.mark.parametrize("name", MODELS + NV_OVER_64)
 def test_vjp_against_the_quad_oracle(rbd, oracle, models, name, layout):
     """(q̄, v̄, v̇̄ / τ̄, f̄ext) against Jᵀλ from the QUAD Jacobians, external wrenches present: inverse dynamics at 1e-10, dynamics state by state at the model's
     C · cond₂(M_b) · eps64 (profiles/derivative_parity.txt).  f̄ext on the small models (6 n_bodies more directions)."""
